@@ -13,9 +13,15 @@ anything touches the GPU -- and exits with their code.  --scaling strong (defaul
 dealt out to the ranks longest-first by band cells, no data-path collective; --scaling weak: every rank
 runs the whole config's number of pairs.  value = cells of all ranks / max-over-ranks time.
 
-Besides the kernel-only `value` the line carries `value_e2e` (SURVEY 8d's wall clock: problems in host memory ->
-result lists in host memory; steady state of a pipeline two batches deep, every stage of every batch inside the clock)
-and `e2e` with the unpipelined stages and the pipeline's fill and drain.
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, the roofline of the
+timed launches).  --full adds everything else the benchmark measures or checks: `value_e2e` (SURVEY 8d's wall clock:
+problems in host memory -> result lists in host memory; steady state of a pipeline two batches deep, every stage of every
+batch inside the clock) and `e2e` with the unpipelined stages and the pipeline's fill and drain, the CPU baseline, the
+parity spot check against the oracle and, in the default run, short passes of configs A, 4 and 5 (`other_configs`).
+
+--dump-outputs DIR: after the timed steps, what the last step computed goes to DIR/<name>.npy (float64): the result
+lists of a fixed, seeded sample of the batch's problems, or the expectation counts of config 5 (rank 0's share when
+N > 1).  The workload is seeded, so two builds given the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -33,6 +39,9 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, _p)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_SEED = 0xD0D0          # which problems --dump-outputs samples: a function of this seed and the batch size alone
+DUMP_MAX_PROBLEMS = 512
+DUMP_MAX_BYTES = 60 << 20   # every array of a dump together
 KERNEL_SOURCES = ["cpecan_kernels.hip", "cpk_device_common.inl", "cpk_sweep.inl", "cpk_team.inl", "cpk_packed.inl",
                   "cpk_table_gather.inl", "cpk_post.inl", "cpk_cells.inl", "cpecan_band.inl", "cpecan_internal.h"]
 
@@ -144,7 +153,7 @@ def other_configs(names):
     for name in names:
         t0 = time.perf_counter()
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", "3", "--warmup", "1",
-               "--no-cpu-baseline", "--e2e-batches", "25" if name == "4" else "5", "--no-other-configs"]
+               "--full", "--no-cpu-baseline", "--e2e-batches", "25" if name == "4" else "5", "--no-other-configs"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
             line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
@@ -157,6 +166,40 @@ def other_configs(names):
     return res
 
 
+def dump_outputs(out_dir, batch, mine, acc):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy files.
+    Expectation step: the counts (transitions, emissions, likelihood).  Otherwise: the (score, x, y) lists of a seeded
+    sample of the batch's problems, concatenated, with the problems' indices and list lengths beside them, and the
+    batch's total of emitted pairs."""
+    import numpy as np
+    from cpecan_amd import workload
+    os.makedirs(out_dir, exist_ok=True)
+    if acc is not None:
+        S = acc.stateNumber
+        arrays = {"expectation_transitions": np.array(acc.transitions[:S * S], dtype=np.float64),
+                  "expectation_emissions": np.array(acc.emissions[:S * 16], dtype=np.float64),
+                  "expectation_likelihood": np.array([acc.likelihood], dtype=np.float64)}
+    else:
+        n = len(mine)
+        keys = workload.splitmix64(DUMP_SEED, np.arange(n, dtype=np.uint64))
+        pick = np.sort(np.argsort(keys, kind="stable")[:min(n, DUMP_MAX_PROBLEMS)])
+        lists, taken, nbytes = [], [], 0
+        for i in pick:
+            r = batch.result(int(i))
+            if nbytes + r.shape[0] * 3 * 8 > DUMP_MAX_BYTES - 2 * 8 * len(pick) - 1024:
+                break  # the sample ends at the byte budget (the same place for two builds that compute the same lists)
+            lists.append(r.astype(np.float64))
+            taken.append(int(i))
+            nbytes += r.shape[0] * 3 * 8
+        arrays = {"sample_problems": np.asarray(mine, dtype=np.int64)[taken].astype(np.float64),
+                  "sample_list_lengths": np.array([a.shape[0] for a in lists], dtype=np.float64),
+                  "aligned_pairs": (np.concatenate(lists) if lists else np.zeros((0, 3))).astype(np.float64),
+                  "batch_pairs_emitted": np.array([batch.stats().pairs], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -166,12 +209,17 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
                     help="default: strong when --gpus > 1 (the config's batch dealt out over the ranks)")
     ap.add_argument("--pairs", type=int, default=0, help="override the config's number of pairs (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the end-to-end pipeline, the CPU baseline, the parity spot check and, in the default run, "
+                         "the other configs; a plain run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--anchor-triples", action="store_true",
                     help="config 4: hand the anchors over as one (x, y, expansion) triple per column instead of as runs")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host to host) measurements")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the end-to-end (host to host) measurements")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default run (config B, one GPU) appends short passes of configs A, 4 and 5 as `other_configs`; skip them")
+                    help="the default --full run (config B, one GPU) appends short passes of configs A, 4 and 5 as `other_configs`; skip them")
     ap.add_argument("--e2e-batches", type=int, default=0, help="batches pushed through the pipeline (odd: the steady state is read over an even number of batch intervals); 0: nine, or as many as make the section last ~0.5 s (short batches: one hiccup of a few ms must not decide the figure)")
     ap.add_argument("--e2e-depth", type=int, default=0, help="batches in flight in the end-to-end pipeline; 0: two, or three where the host's packing and planning takes at least half as long as sweep + download and three batches fit in half the device memory")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -180,6 +228,9 @@ def main():
                     help="no GPU work: partition the batch, run the rendezvous and the reductions, print the line "
                          "(value null) -- checks the N > 1 launch path where there is no GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -275,6 +326,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = {"acc": None}  # the counts of the latest expectation step (--dump-outputs)
+
     def step():
         batch.run(stream.cuda_stream)
         if expect:
@@ -284,6 +337,7 @@ def main():
             batch.expectations(acc)
             if world > 1:
                 cdist.allreduce_hmm(acc, red_dev)
+            last["acc"] = acc
 
     for _ in range(args.warmup):
         step()
@@ -323,20 +377,26 @@ def main():
         dist.all_reduce(n, op=dist.ReduceOp.SUM)
         total_pairs = int(n.item())
 
-    # ---- results back on the host once: PCIe + list assembly (not in `value`), and a parity spot check below ----
-    t1 = time.perf_counter()
-    batch.download()
-    d2h_s = time.perf_counter() - t1
+    # ---- results back on the host once: PCIe + list assembly (not in `value`), for --dump-outputs and --full ----
+    e2e = {"plan_upload_s": upload_s}
+    if full or (args.dump_outputs and not expect):
+        t1 = time.perf_counter()
+        batch.download()
+        e2e["download_and_assemble_s"] = time.perf_counter() - t1
     st = batch.stats()
+    if full or args.dump_outputs:
+        e2e["pairs_emitted"] = int(st.pairs)
+    e2e.update({"device_bytes": int(st.deviceBytes), "waves": int(st.wavesPerLaunch),
+                # which form the widest size class ran in: the split forms hold whole regions' forward values (cpecan_hip.h)
+                "launch_form": {0: "one wave per region", 1: "two launches", 2: "one launch"}[int(st.launchForm) & 3] +
+                               (", absolute positions" if int(st.launchForm) & 4 else "")})
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, batch, mine, last["acc"] if expect else None)
 
-    # ---- SURVEY 8d's wall clock: problems resident in host memory -> result lists materialised in host memory ----
-    e2e = {"plan_upload_s": upload_s, "download_and_assemble_s": d2h_s, "pairs_emitted": int(st.pairs),
-           "device_bytes": int(st.deviceBytes), "waves": int(st.wavesPerLaunch),
-           # which form the widest size class ran in: the split forms hold whole regions' forward values (cpecan_hip.h)
-           "launch_form": {0: "one wave per region", 1: "two launches", 2: "one launch"}[int(st.launchForm) & 3] +
-                          (", absolute positions" if int(st.launchForm) & 4 else "")}
+    # ---- (--full) SURVEY 8d's wall clock: problems resident in host memory -> result lists materialised in host memory ----
     value_e2e = None
-    if not args.no_e2e:
+    if full and not args.no_e2e:
         # the timed batch goes first: a config-B batch in its one-launch form holds the forward values of every region
         # (68 GB at config B); the pipeline below gets that memory for its own batches
         spot = [] if expect else [batch.result(i) for i in range(min(4, len(problems)))]  # for the parity spot check below
@@ -516,7 +576,9 @@ def main():
             "value_e2e": value_e2e,
             "e2e": e2e,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if full and not args.no_cpu_baseline and world == 1:
             # (rank 0, N=1 only) every core the box gives this process: its affinity mask cut to its cgroup CPU quota (a
             # one-GPU box hands out a 16-core share of one socket; BASELINE.md section 3 asks for a whole socket's cores)
             threads = int(os.environ.get("CPECAN_BENCH_CPU_THREADS", usable_cores()))
@@ -560,8 +622,8 @@ def main():
                     assert abs(acc.emissions[i] - oacc.E[i]) <= 1e-5 * abs(oacc.E[i]) + 1e-9, ("E", i)
                 assert abs(acc.likelihood - oacc.likelihood) <= 1e-9 * abs(oacc.likelihood)
                 out["parity_spot_check"] = "expectation counts of %d problems match the oracle to 1e-5" % nchk
-        if (args.config == "B" and world == 1 and not args.pairs and not args.no_other_configs and not args.no_e2e):
-            # the driver's default run sees the other BASELINE configs too -- short passes (3 steps, a
+        if (full and args.config == "B" and world == 1 and not args.pairs and not args.no_other_configs and not args.no_e2e):
+            # the default --full run sees the other BASELINE configs too -- short passes (3 steps, a
             # five-batch pipeline) as child processes once this process has given its device memory back
             if batch is not None:
                 batch.close()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # config 4 end to end under environment settings: tools/ab_e2e4.sh VAR=a VAR=b ...
 for rep in 1 2; do for kv in "$@"; do
-  env $kv timeout -k 10 300 python bench.py --config 4 --steps 4 --warmup 1 --no-cpu-baseline --no-other-configs --e2e-batches 13 2>/dev/null > /tmp/e4.json || { echo "$kv failed"; exit 1; }
+  env $kv timeout -k 10 300 python bench.py --full --config 4 --steps 4 --warmup 1 --no-cpu-baseline --no-other-configs --e2e-batches 13 2>/dev/null > /tmp/e4.json || { echo "$kv failed"; exit 1; }
   python - "$kv" <<'PY'
 import sys, json
 d = json.loads(open('/tmp/e4.json').read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ DEPTH=${2:-0}
 OUT=$R/gpurun_out/timeline_bench_$CFG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/t -- python3 $R/bench.py --config $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --e2e-batches 9 --e2e-depth $DEPTH > $OUT.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/t -- python3 $R/bench.py --full --config $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --e2e-batches 9 --e2e-depth $DEPTH > $OUT.log 2>&1
 python3 - $OUT <<'PY'
 import csv, glob, sys
 out = sys.argv[1]
