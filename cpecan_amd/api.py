@@ -101,6 +101,7 @@ EXPORTS = [
     "cpecan_identity_scores", "cpecan_filter_pairs_ordered", "cpecan_batch_add_many",
     "cpecan_filter_to_remove_overlap", "cpecan_cache_trim", "cpecan_ref_cells",
     "cpecan_batch_add_many_runs", "cpecan_anchor_runs", "cpecan_anchor_runs_from_alignment",
+    "cpecan_batch_set_model",
 ]
 OP_MATCH, OP_INDEL_X, OP_INDEL_Y = 0, 1, 2
 POST_REWEIGHT, POST_MEA, POST_LEFT_SHIFT, POST_ORDERED = 1, 2, 4, 8
@@ -142,6 +143,7 @@ def lib():
     L.cpecan_batch_upload.argtypes = [vp]
     L.cpecan_batch_run.argtypes = [vp, vp]
     L.cpecan_batch_download.argtypes = [vp]
+    L.cpecan_batch_set_model.argtypes = [vp, C.POINTER(StateMachine)]
     L.cpecan_batch_download_begin.argtypes = [vp]
     L.cpecan_batch_download_end.argtypes = [vp]
     L.cpecan_batch_result.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(i32p), i64p]
@@ -402,6 +404,11 @@ class Batch:
 
     def run(self, stream=None):
         _check(lib().cpecan_batch_run(self._h, C.c_void_p(stream or 0)), "cpecan_batch_run")
+
+    def set_model(self, sM):
+        """Swaps the model of the uploaded batch for the next run(); nothing is planned or uploaded again."""
+        _check(lib().cpecan_batch_set_model(self._h, C.byref(sM)), "cpecan_batch_set_model")
+        self._sM = sM
 
     def download(self):
         _check(lib().cpecan_batch_download(self._h), "cpecan_batch_download")

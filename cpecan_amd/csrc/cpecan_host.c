@@ -1657,6 +1657,29 @@ int cpecan_batch_run(cpecan_batch *b, void *stream) {
     return rc;
 }
 
+int cpecan_batch_set_model(cpecan_batch *b, const cpecan_model *m) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !m) return CPECAN_EINVAL;
+    if (!(is_five(m->type) || is_three(m->type)) || is_five(m->type) != is_five(b->model.type)) {
+        cpk_set_error("set_model: a model of %d states for a batch planned for %d", is_five(m->type) ? 5 : 3,
+                      is_five(b->model.type) ? 5 : 3);
+        return CPECAN_EINVAL;
+    }
+    if (!b->frozen) {
+        cpk_set_error("set_model before upload");
+        return CPECAN_ESTATE;
+    }
+    if (b->nRegions > 0) {
+        CpkModel km;
+        kernel_model(m, b->params.threshold, &km);
+        const int rc = cpk_device_set_model(b->dev, &km);
+        if (rc != CPECAN_OK) return rc;
+    }
+    b->model = *m;
+    b->ran = 0; /* a run not downloaded yet belongs to the old model: the next download needs a new run */
+    return CPECAN_OK;
+}
+
 /* The copy plan of cpk_device_gather for the whole batch: per list, problems in order, regions in order, traceback
  * segments in DEScending order (each traceback's pairs are prepended, pairwiseAligner.c:1415-1417), every triple shifted
  * by its region's offset (:1411-1418).  Sets the per-problem result pointers into b->results. */

@@ -166,6 +166,9 @@ int cpk_device_upload(CpkDevice *dev, const CpkGeometry *geo, const CpkModel *mo
                       int64_t outTriplesPerList, int nLists, int64_t dbgCells, int64_t dbgDiags, double *h2dMs);
 double cpk_device_h2d_ms(CpkDevice *dev); /* the upload's copy time; waits for the copies */
 int cpk_device_update_regions(CpkDevice *dev, const CpkRegion *regions, const CpkSegment *segs, int64_t outTriplesPerList);
+/* Replaces the model the next cpk_device_run uses (kernel-argument transitions and the device CpkModel); the copy is
+ * ordered behind the last run on the batch's own stream and in front of the next sweep. */
+int cpk_device_set_model(CpkDevice *dev, const CpkModel *model);
 int cpk_device_run(CpkDevice *dev, void *stream);
 int cpk_device_form(const CpkDevice *dev); /* CPECAN_FORM_* of the batch's last (widest) size class */
 /* Once more on the stream of the last run (after an output overflow); kernel times of a batch's launches add up. */

@@ -662,6 +662,9 @@ struct CpkDevice {
     hipEvent_t evStart = nullptr, evStop = nullptr;
     hipEvent_t evA = nullptr, evB = nullptr;  // copy timing (owned by the shell: nothing to leak on an error path)
     hipEvent_t evUp0 = nullptr, evUp1 = nullptr;  // around the upload's copies; the sweep waits for evUp1 (cpk_device_run)
+    // cpk_device_set_model: the pinned source of the last model copy and the event that says it has been read
+    CpkModel *hModel = nullptr;
+    hipEvent_t evModel = nullptr;
     bool uploadTimed = true;
     double h2dMs = 0.0;
     hipStream_t lastStream = nullptr;
@@ -703,6 +706,8 @@ static void shell_delete(CpkDevice *d) {  // the shell's device is current
     if (d->evB) (void)hipEventDestroy(d->evB);
     if (d->evUp0) (void)hipEventDestroy(d->evUp0);
     if (d->evUp1) (void)hipEventDestroy(d->evUp1);
+    if (d->evModel) (void)hipEventDestroy(d->evModel);
+    if (d->hModel) (void)hipHostFree(d->hModel);
     if (d->io) (void)hipStreamDestroy(d->io);
     for (int k = 0; k < kMaxClasses; k++) {
         if (d->sideStream[k]) (void)hipStreamDestroy(d->sideStream[k]);
@@ -1745,6 +1750,32 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     d->uploadTimed = false;
     d->h2dMs = 0.0;
     if (h2dMs) *h2dMs = 0.0;  // known once the copies are done: cpk_device_download reports it
+    return CPECAN_OK;
+}
+
+// A new model for the next run of an uploaded batch.  The transitions travel in the kernel arguments (d->kc, read at the
+// next launch); the priors and padded emissions are copied into dModel on the batch's own stream, behind the stop event
+// of the last run -- a sweep still in flight reads the old table to its end -- and the next sweep waits for the copy
+// through evUp1, as it waits for the upload's copies.
+extern "C" int cpk_device_set_model(CpkDevice *d, const CpkModel *model) {
+    CPK_ON_DEVICE(d->device);
+    if (!d->dModel) {
+        cpk_set_error("set_model before upload");
+        return CPECAN_ESTATE;
+    }
+    if (!d->hModel) HIP_TRY(hipHostMalloc(&d->hModel, sizeof(CpkModel), hipHostMallocDefault));
+    if (!d->evModel) HIP_TRY(hipEventCreateWithFlags(&d->evModel, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(d->evModel));  // the previous model copy has left the pinned block
+    *d->hModel = *model;
+    hipStream_t io = d->io;
+    if (d->ran) HIP_TRY(hipStreamWaitEvent(io, d->evStop, 0));
+    HIP_TRY(hipMemcpyAsync(d->dModel, d->hModel, sizeof(CpkModel), hipMemcpyHostToDevice, io));
+    HIP_TRY(hipEventRecord(d->evModel, io));
+    HIP_TRY(hipEventRecord(d->evUp1, io));
+    d->kc = KConsts{model->matchContinue, model->matchFromShortX, model->matchFromShortY, model->matchFromLongX,
+                    model->matchFromLongY, model->shortOpenX, model->shortOpenY, model->shortExtendX,
+                    model->shortExtendY, model->shortSwitchToX, model->shortSwitchToY, model->longOpenX,
+                    model->longOpenY, model->longExtendX, model->longExtendY, model->threshold};
     return CPECAN_OK;
 }
 

@@ -1116,6 +1116,100 @@ int cpecan_realigner_realign(cpecan_realigner *r, const cpecan_cigar *in, int64_
     return rc;
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * A resident set of alignments for expectation maximisation: the cigars are prepared, planned and uploaded once (one
+ * EXPECT batch per shard), and every E-step after that is set_model + run + download on the same batches.
+ * ---------------------------------------------------------------------------------------------- */
+struct cpecan_expect_set {
+    int nShards;
+    int32_t type;                                /* the model type the batches were planned for */
+    cpecan_batch *batches[CPK_REALIGN_MAX_DEVICES]; /* NULL: an empty shard */
+    int devices[CPK_REALIGN_MAX_DEVICES];
+};
+
+void cpecan_expect_set_destroy(cpecan_expect_set *s) {
+    if (!s) return;
+    for (int k = 0; k < s->nShards; k++) cpecan_batch_destroy(s->batches[k]);
+    free(s);
+}
+
+static int expect_shard_create(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int device, cpecan_batch **out) {
+    cpecan_batch *b = NULL;
+    int rc = cpecan_batch_create(&b, &r->model, &r->opt.params, CPECAN_EMIT_EXPECT, device);
+    Item *items = rc == CPECAN_OK ? calloc((size_t)n, sizeof(Item)) : NULL;
+    if (rc == CPECAN_OK && !items) rc = CPECAN_ENOMEM;
+    if (rc == CPECAN_OK) rc = prepare_and_add(r, in, n, items, b);
+    for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
+    free(items);
+    if (rc == CPECAN_OK) {
+        rc = cpecan_batch_upload(b);
+        if (rc == CPECAN_ENOMEM) {
+            cpecan_stats st;
+            cpecan_batch_stats(b, &st);
+            cpk_set_error("the %lld sampled alignments (%lld band cells) do not fit in the memory of device %d as one "
+                          "resident batch: lower maxAlignmentLengthToSample or add devices",
+                          (long long)n, (long long)st.cells, device);
+        }
+    }
+    if (rc != CPECAN_OK) {
+        cpecan_batch_destroy(b);
+        return rc;
+    }
+    *out = b;
+    return CPECAN_OK;
+}
+
+int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n) {
+    if (!out || !r || (!in && n > 0) || n < 0) return CPECAN_EINVAL;
+    *out = NULL;
+    cpecan_expect_set *s = calloc(1, sizeof *s);
+    if (!s) return CPECAN_ENOMEM;
+    s->type = r->model.type;
+    s->nShards = r->nDevices > 1 ? r->nDevices : 1;
+    int64_t bounds[CPK_REALIGN_MAX_DEVICES + 1];
+    int rc = cpecan_realign_shard_bounds(in, n, r->opt.params.diagonalExpansion, s->nShards, bounds);
+    for (int k = 0; rc == CPECAN_OK && k < s->nShards; k++) {
+        s->devices[k] = r->nDevices > 1 ? r->devices[k] : r->device;
+        if (bounds[k + 1] > bounds[k])
+            rc = expect_shard_create(r, in + bounds[k], bounds[k + 1] - bounds[k], s->devices[k], &s->batches[k]);
+    }
+    if (rc != CPECAN_OK) {
+        cpecan_expect_set_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return CPECAN_OK;
+}
+
+int cpecan_expect_set_run(cpecan_expect_set *s, const cpecan_model *m, cpecan_hmm *acc) {
+    if (!s || !m || !acc) return CPECAN_EINVAL;
+    /* every shard's kernels are queued before the first download waits: the devices work side by side */
+    for (int k = 0; k < s->nShards; k++) {
+        if (!s->batches[k]) continue;
+        int rc = cpecan_batch_set_model(s->batches[k], m);
+        if (rc == CPECAN_OK) rc = cpecan_batch_run(s->batches[k], NULL);
+        if (rc != CPECAN_OK) return rc;
+    }
+    for (int k = 0; k < s->nShards; k++) { /* summed in shard order, as cpecan_realigner_expectations does */
+        if (!s->batches[k]) continue;
+        int rc = cpecan_batch_download(s->batches[k]);
+        if (rc == CPECAN_OK) rc = cpecan_batch_expectations(s->batches[k], acc);
+        if (rc != CPECAN_OK) return rc;
+    }
+    return CPECAN_OK;
+}
+
+int cpecan_expect_set_stats(const cpecan_expect_set *s, int shard, cpecan_stats *st) {
+    if (!s || !st || shard < 0 || shard >= s->nShards) return CPECAN_EINVAL;
+    if (!s->batches[shard]) {
+        memset(st, 0, sizeof *st);
+        return CPECAN_OK;
+    }
+    return cpecan_batch_stats(s->batches[shard], st);
+}
+
+int cpecan_expect_set_shards(const cpecan_expect_set *s) { return s ? s->nShards : CPECAN_EINVAL; }
+
 int cpecan_realigner_expectations(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_hmm *acc) {
     if (!r || (!in && n > 0) || n < 0 || !acc) return CPECAN_EINVAL;
     if (r->nDevices <= 1 || n < 2) return expectations_on_device(r, in, n, acc);

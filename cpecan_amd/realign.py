@@ -14,6 +14,8 @@ EXPORTS = [
     "cpecan_realigner_add_sequence", "cpecan_realigner_read_fasta", "cpecan_realigner_set_posterior_files",
     "cpecan_realigner_realign", "cpecan_realigner_expectations",
     "cpecan_realigner_set_devices", "cpecan_realign_shard_bounds",
+    "cpecan_expect_set_create", "cpecan_expect_set_run", "cpecan_expect_set_shards", "cpecan_expect_set_stats",
+    "cpecan_expect_set_destroy",
 ]
 
 

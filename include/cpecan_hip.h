@@ -231,6 +231,15 @@ int cpecan_batch_upload(cpecan_batch *b);
  * already resident; asynchronous. May be called repeatedly (bench). */
 int cpecan_batch_run(cpecan_batch *b, void *stream);
 
+/* Replaces the model of an uploaded batch (any emitter) for the next cpecan_batch_run, without planning or uploading
+ * anything else: band tables, traceback schedules, symbols, size classes, launch forms and wave counts stay as they are.
+ * The model must have the state count of the batch's model (CPECAN_EINVAL otherwise); the threshold stays the batch's
+ * parameter.  The device copy is ordered behind any run still in flight, so a sweep never sees the table change under it.
+ * A run that has not been downloaded belongs to the old model: after this call cpecan_batch_download needs a new run.
+ * This is the inner loop of expectation maximisation (include/cpecan_em.h): plan and upload once, then per iteration
+ * set_model + run + download + cpecan_batch_expectations. */
+int cpecan_batch_set_model(cpecan_batch *b, const cpecan_model *m);
+
 /* Waits for the run, copies results to the host and orders them as the reference's lists. */
 int cpecan_batch_download(cpecan_batch *b);
 /* The same on a helper thread of the batch's own: _begin returns at once, _end waits for the helper and returns what

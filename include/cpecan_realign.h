@@ -93,6 +93,22 @@ int cpecan_realigner_realign(cpecan_realigner *r, const cpecan_cigar *in, int64_
  * caller made with cpecan_hmm_init(acc, type, 0.000000000001) (:497) and writes with cpecan_hmm_write (:612). */
 int cpecan_realigner_expectations(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_hmm *acc);
 
+/* The E-step of expectation maximisation on a RESIDENT set of alignments (include/cpecan_em.h).  _create prepares the n
+ * cigars as cpecan_realigner_expectations does (exact-match anchors, diagonalExpansion, splitMatrixBiggerThanThis,
+ * constraintDiagonalTrim of the realigner's options), cuts them into the realigner's device shards
+ * (cpecan_realign_shard_bounds) and plans and uploads one EXPECT batch per shard, once.  A set that does not fit in a
+ * device's memory fails with CPECAN_ENOMEM and a message that names the limit; nothing is re-planned.  _run then adds the
+ * expectation counts of all n alignments under model m to *acc -- the result of cpecan_realigner_expectations with a
+ * realigner of model m -- by swapping the model of the resident batches (cpecan_batch_set_model) and running only the
+ * kernels.  m must have the state count of the realigner's model. */
+typedef struct cpecan_expect_set cpecan_expect_set;
+int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n);
+int cpecan_expect_set_run(cpecan_expect_set *s, const cpecan_model *m, cpecan_hmm *acc);
+int cpecan_expect_set_shards(const cpecan_expect_set *s);
+/* Statistics of shard k's batch (launch form, waves, cells, kernel time of the last run); zeros for an empty shard. */
+int cpecan_expect_set_stats(const cpecan_expect_set *s, int shard, cpecan_stats *st);
+void cpecan_expect_set_destroy(cpecan_expect_set *s);
+
 #ifdef __cplusplus
 }
 #endif
