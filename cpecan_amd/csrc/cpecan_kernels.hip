@@ -42,6 +42,7 @@
 #include <atomic>
 #include <utility>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "cpecan_internal.h"
@@ -82,38 +83,7 @@ extern "C" const char *cpk_last_error(void) { return g_err; }
 // ------------------------------------------------------------------------------------------------
 // host side of the HIP TU: memory, launch, timing
 // ------------------------------------------------------------------------------------------------
-using KernelFn = void (*)(const KArgs);
-constexpr int kMaxClasses = CPK_WIDE_CLASSES + 6;  // wide classes + three packed ones, each of which may run as a split and a whole part
-
-// One kernel launch of a run: the regions [regionBase, regionBase + regionCount) of the device order, which share one
-// size class, with LDS, occupancy and per-wave scratch sized for the largest of THEM.
-struct LaunchClass {
-    bool packed = false;
-    int k = 0;           // class index within its kind (wide 0..3, packed 0..2)
-    KernelFn fn = nullptr;
-    CpkGeometry geo{};   // what the kernel reads: the scalar fields describe this class
-    int waves = 0;       // workgroups of the launch
-    int threads = CPK_WAVE;  // threads per workgroup: one wave, or the waves of a team
-    int64_t subSlots = 0;  // scratch slots: one per wave (sweep) or one per region group of a wave (packed)
-    size_t ldsBytes = 0;
-    size_t ldsBytesFwd = 0;  // split, two launches: the forward launch's own LDS size (no candidate ring)
-    int regionBase = 0, regionCount = 0;
-    // A SPLIT class (fewer regions than wave slots): launch 1 = forward sweeps of whole regions into per-REGION rings,
-    // launch 2 = one queue item per (region, traceback segment); see kModeForward / kModeTrace in cpk_sweep.inl.
-    bool split = false;
-    bool dense = false;  // three-state match kernels allocated for three waves per SIMD (WPS = 3)
-    bool fused = false;  // split, as ONE launch (kModeFused): regions and their traceback items in one queue
-    bool abs = false;    // split, with the sweeps over absolute positions (cpk_sweep.inl "Absolute-position sweeps")
-    KernelFn fnTrace = nullptr;
-    int wavesTrace = 0;
-    int64_t itemBase = 0, itemCount = 0;  // its items in dItems
-    int64_t ringTotal = 0;                // doubles of all its regions' rings (ringEl is 0 then: nothing per slot)
-    int64_t ringEl = 0, candEl = 0, refEl = 0, totEl = 0, bringEl = 0, grollEl = 0;  // elements per scratch slot
-    int64_t oRing = 0, oCand = 0, oRef = 0, oTot = 0, oBring = 0, oGroll = 0, oExpect = 0;  // element offsets of the class
-    double slotBytes() const {
-        return 8.0 * ringEl + (double)sizeof(Candidate) * candEl + 16.0 * refEl + 8.0 * totEl + 8.0 * bringEl + 8.0 * grollEl;
-    }
-};
+#include "cpk_plan.inl"
 
 // ------------------------------------------------------------------------------------------------
 // Device memory and device shells are recycled: a batch of one small problem (the single-call entry points, a caller's
@@ -875,126 +845,6 @@ static void dev_release(CpkDevice *d, void *p) {
         }
 }
 
-static KernelFn pick_packed_kernel(const CpkGeometry &g, int cls, bool dynamic) {  // class k: groups of 8 << k lanes
-    const bool five = g.nStates == 5;
-#define CPK_PICK_PACKED(E, D)                                                                                               \
-    if (g.emit == (E) && dynamic == (D)) switch (cls) {                                                                     \
-            case 0: return five ? cpecan_pairhmm_packed<5, 8, (E), (D)> : cpecan_pairhmm_packed<3, 8, (E), (D)>;            \
-            case 1: return five ? cpecan_pairhmm_packed<5, 16, (E), (D)> : cpecan_pairhmm_packed<3, 16, (E), (D)>;          \
-            case 2: return five ? cpecan_pairhmm_packed<5, 32, (E), (D)> : cpecan_pairhmm_packed<3, 32, (E), (D)>;          \
-        }
-    CPK_PICK_PACKED(CPECAN_EMIT_MATCH, false)
-    CPK_PICK_PACKED(CPECAN_EMIT_INDEL, false)
-    CPK_PICK_PACKED(CPECAN_EMIT_EXPECT, false)
-    CPK_PICK_PACKED(CPECAN_EMIT_MATCH, true)  // per-anchor expansions
-    CPK_PICK_PACKED(CPECAN_EMIT_INDEL, true)
-    CPK_PICK_PACKED(CPECAN_EMIT_EXPECT, true)
-#undef CPK_PICK_PACKED
-    return nullptr;
-}
-// the two kernels of a split packed class (match emitter, fixed expansion; cpk_packed.inl, MODE)
-static void pick_packed_split_kernels(const CpkGeometry &g, int cls, KernelFn *fwd, KernelFn *trace) {
-    const bool five = g.nStates == 5;
-#define CPK_PICK_PACKED_SPLIT(GW)                                                                                                \
-    {                                                                                                                            \
-        *fwd = five ? cpecan_pairhmm_packed<5, GW, CPECAN_EMIT_MATCH, false, kModeForward> : cpecan_pairhmm_packed<3, GW, CPECAN_EMIT_MATCH, false, kModeForward>; \
-        *trace = five ? cpecan_pairhmm_packed<5, GW, CPECAN_EMIT_MATCH, false, kModeTrace> : cpecan_pairhmm_packed<3, GW, CPECAN_EMIT_MATCH, false, kModeTrace>;   \
-    }
-    switch (cls) {
-        case 0: CPK_PICK_PACKED_SPLIT(8) break;
-        case 1: CPK_PICK_PACKED_SPLIT(16) break;
-        default: CPK_PICK_PACKED_SPLIT(32) break;
-    }
-#undef CPK_PICK_PACKED_SPLIT
-}
-
-// the two kernels of a split class (match emitter)
-// Doubles of the ring a split region keeps its forward values in.  The match emitter stores the match row of every
-// diagonal and every state only where the traceback reads it back: diagonal 0, the refresh diagonals of the emitting
-// segment (one in CPK_REFRESH_PERIOD) and the two diagonals a forward sweep would resume from -- the table builder lays
-// the diagonals end to end with exactly that many doubles each (cpk_table_gather.inl); this is the upper bound it stays
-// below.  (Every state of every cell, as the per-wave rings are sized, is 204 GB for BASELINE config B; this is 62.)
-static int64_t split_ring_doubles(const CpkRegion &rg, int S) {
-    const int64_t N = (int64_t)rg.lX + rg.lY;
-    const int64_t fullDiags = N / CPK_REFRESH_PERIOD + 3 * (int64_t)rg.nSeg + 4;  // refresh points + two resume diagonals per segment
-    // + one double of padding per diagonal (match rows start and end on even doubles); an even total keeps the next region's ring aligned
-    return ((int64_t)rg.cells + (N + 1) + (int64_t)(S - 1) * rg.maxWidth * fullDiags + S + 1) & ~(int64_t)1;
-}
-// dense: the three-state match kernels allocated for three waves per SIMD (cpk_sweep.inl, WPS)
-static KernelFn pick_fused_kernel(const CpkGeometry &g, bool dense, bool abs, bool three = false) {
-    const bool fast = !g.useGlobalRoll;
-    if (abs && fast) {
-        // three (round 4): built for three waves per SIMD, for classes whose LDS lets nine or more waves onto a CU
-        if (g.nStates == 5)
-            return three ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeFused, 3, true>
-                         : cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeFused, CPK_SWEEP_WAVES, true>;
-        return dense ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused, 3, true>
-                     : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused, CPK_SWEEP_WAVES, true>;
-    }
-    if (g.nStates == 5)
-        return fast ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeFused> : cpecan_pairhmm_sweep<5, false, CPECAN_EMIT_MATCH, kModeFused>;
-    if (dense)
-        return fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeFused, 3>;
-    return fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeFused>;
-}
-static void pick_split_kernels(const CpkGeometry &g, bool dense, bool abs, KernelFn *fwd, KernelFn *trace, bool fwd3 = false,
-                               bool trace3 = false) {
-    const bool fast = !g.useGlobalRoll;
-    if (abs && fast) {
-        // fwd3: the forward launch has no candidate ring and 120 VGPRs or fewer; where its LDS lets nine or more waves
-        // onto a CU it runs the build for three waves per SIMD (profiles/r03_occupancy_3_waves_per_simd.txt)
-        if (g.nStates == 5) {
-            *fwd = fwd3 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeForward, 3, true>
-                        : cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeForward, CPK_SWEEP_WAVES, true>;
-            // trace3 (round 4): the traceback launch built for three waves per SIMD (168 VGPRs), for classes whose LDS lets
-            // nine or more waves onto a CU
-            *trace = trace3 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true>
-                            : cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeTrace, CPK_SWEEP_WAVES, true>;
-        } else {
-            *fwd = fwd3 ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeForward, 3, true>
-                        : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeForward, CPK_SWEEP_WAVES, true>;
-            *trace = dense ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true>
-                           : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace, CPK_SWEEP_WAVES, true>;
-        }
-        return;
-    }
-    if (g.nStates == 5) {
-        *fwd = fast ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeForward> : cpecan_pairhmm_sweep<5, false, CPECAN_EMIT_MATCH, kModeForward>;
-        *trace = fast ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeTrace> : cpecan_pairhmm_sweep<5, false, CPECAN_EMIT_MATCH, kModeTrace>;
-    } else {
-        // the forward-only kernel needs 70 VGPRs: one variant
-        *fwd = fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeForward> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeForward>;
-        if (dense)
-            *trace = fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeTrace, 3>;
-        else
-            *trace = fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeTrace>;
-    }
-}
-static KernelFn pick_dense_kernel(const CpkGeometry &g) {  // one wave per region, three-state match emitter
-    return !g.useGlobalRoll ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeWhole, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeWhole, 3>;
-}
-
-static KernelFn pick_kernel(const CpkGeometry &g) {
-    const bool fast = !g.useGlobalRoll;  // second template argument = FAST (LDS rolling buffers + LDS symbol strings)
-    if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep == 1)  // no diagonal wider than one 64-lane group
-        return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1>
-                              : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1>;
-    if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep)
-        return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2>
-                              : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2>;
-#define CPK_PICK(E)                                                                                          \
-    if (g.emit == (E)) {                                                                                     \
-        if (g.nStates == 5) return fast ? cpecan_pairhmm_sweep<5, true, (E)> : cpecan_pairhmm_sweep<5, false, (E)>; \
-        return fast ? cpecan_pairhmm_sweep<3, true, (E)> : cpecan_pairhmm_sweep<3, false, (E)>;              \
-    }
-    CPK_PICK(CPECAN_EMIT_MATCH)
-    CPK_PICK(CPECAN_EMIT_INDEL)
-    CPK_PICK(CPECAN_EMIT_EXPECT)
-    CPK_PICK(kEmitForward)
-#undef CPK_PICK
-    return nullptr;
-}
-
 // Queues dst <- src (host) on the batch's stream through the shell's pinned buffer; `at` is the running offset in it.
 constexpr size_t kStageMaxCopy = (size_t)64 << 20;  // larger sources are never copied through the shell's staging buffer
 static int staged_h2d(CpkDevice *d, void *dst, const void *src, size_t bytes, size_t *at) {
@@ -1028,6 +878,34 @@ static int stage_reserve(CpkDevice *d, size_t bytes) {
     return CPECAN_OK;
 }
 
+// split classes: the regions get rings of their own (no wrap: every segment stays readable) and their tracebacks
+// become queue items, longest first
+static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regions, const CpkSegment *segs, int S, std::vector<CpkItem> *items) {
+    for (LaunchClass &c : classes) {
+        if (!c.split) continue;
+        int64_t ringAt = 0;  // in doubles, from the class's ring pointer (dRing + oRing)
+        c.itemBase = (int64_t)items->size();
+        std::vector<std::pair<int64_t, CpkItem>> byCost;
+        for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) {
+            CpkRegion &rg = regions[di];
+            rg.ringCap = 0x7fffffff;  // never wraps: the ring holds every diagonal of the region
+            rg.ringBase = ringAt;
+            rg.split = 1;
+            ringAt += split_ring_doubles(rg, S);
+            for (int32_t si = 0; si < rg.nSeg; si++) {
+                const CpkSegment &sg = segs[rg.segOff + si];
+                // fused: a segment's forward values exist when the forward wave has passed its top diagonal -- items in
+                // the order in which they become ready (that diagonal), longest first among equals
+                const int64_t cost = (int64_t)(sg.dTop - sg.tbPrev) * rg.maxWidth;
+                byCost.push_back({c.fused ? ((int64_t)0x7fffffff - sg.dTop) * ((int64_t)1 << 32) + (cost >> 8) : cost, CpkItem{(int32_t)di, si}});
+            }
+        }
+        std::stable_sort(byCost.begin(), byCost.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
+        for (const auto &e : byCost) items->push_back(e.second);
+        c.itemCount = (int64_t)items->size() - c.itemBase;
+    }
+}
+
 extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const CpkModel *model, CpkRegion *regions,
                                  const cpk_anchor_t *anchors, int anchorStride, int64_t nAnchors, const int32_t *runs, int64_t nRuns,
                                  int64_t nDiags, int64_t expansion, int dynamic,
@@ -1052,532 +930,15 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     ran_set(d, false);
     const int S = geo->nStates;
 
-    // ---- the launches of a run: one per size class that has regions ----
-    d->classes.clear();
-    // Resident single-wave workgroups per CU.  hipOccupancyMaxActiveBlocksPerMultiprocessor answers 3 for these
-    // 64-thread kernels (it reports waves per SIMD), so the bound is computed from the register file and LDS
-    // directly (MI355X_MICROARCH.md: 512 VGPRs per lane per SIMD in granules of 8, 4 SIMDs, 32 waves, 160 KiB LDS).
-    // Over-estimating is harmless: surplus workgroups simply queue, every wave exits when the work queue is empty.
-    auto wavesPerCU = [&](KernelFn fn, size_t ldsBytes, int *out) -> int {
-        hipFuncAttributes attr;
-        HIP_TRY(hipFuncGetAttributes(&attr, (const void *)fn));
-        const int vgprAlloc = ((attr.numRegs > 0 ? attr.numRegs : 128) + 7) / 8 * 8;
-        int perSimd = 512 / vgprAlloc;
-        if (perSimd > 8) perSimd = 8;
-        if (perSimd < 1) perSimd = 1;
-        int perCU = 4 * perSimd;
-        const size_t ldsTotal = ldsBytes + (size_t)attr.sharedSizeBytes;
-        const int byLds = (int)((160 * 1024) / (ldsTotal ? ldsTotal : 1));
-        if (byLds < perCU) perCU = byLds;
-        if (perCU > 32) perCU = 32;
-        if (const char *cap = getenv("CPECAN_MAX_WAVES_PER_CU")) {  // tuning/diagnostic knob
-            const int c = atoi(cap);
-            if (c >= 1 && c < perCU) perCU = c;
-        }
-        *out = perCU;
-        return CPECAN_OK;
-    };
-    const int nCandLists = geo->emit == CPECAN_EMIT_INDEL ? 3 : 1;
-    const bool expect = geo->emit == CPECAN_EMIT_EXPECT;
-    int regionAt = 0;
-    std::vector<LaunchClass> packedSplit, packedWhole;
-    for (int k = 0; k < 3; k++) {  // narrow regions come first in the device order: the packed kernel, 64 / GW to a wave
-        if (geo->nPacked[k] <= 0) continue;
-        LaunchClass c;
-        c.packed = true;
-        c.k = k;
-        c.fn = pick_packed_kernel(*geo, k, dynamic != 0);
-        if (!c.fn) {
-            cpk_set_error("no packed kernel for emitter %d", geo->emit);
-            return CPECAN_EINVAL;
-        }
-        const int GW = 8 << k, G = CPK_WAVE / GW;
-        c.geo = *geo;
-        c.geo.ringCells = geo->pRingCells[k];
-        c.geo.fbCells = geo->pFbCells[k];
-        c.geo.maxRefresh = geo->pMaxRefresh[k];
-        c.geo.refreshCells = (int64_t)GW * geo->pMaxRefresh[k];
-        c.ldsBytes = sizeof(double) * (size_t)(kLdsCubics + kLdsEm + kLdsWeights + (expect ? kExpectCopies * 80 : 0)) +
-                     (size_t)G * pack_group_bytes(S, GW);
-        int perCU = 0;
-        if (int rc = wavesPerCU(c.fn, c.ldsBytes, &perCU)) return rc;
-        const int64_t slots = (int64_t)perCU * d->numCUs;
-        c.ringEl = c.geo.ringCells * S;
-        c.candEl = c.geo.fbCells;
-        c.refEl = c.geo.refreshCells;
-        c.totEl = c.geo.maxRefresh;
-        // B of a segment's emitted cells: the expectation step's second pass, the indel emitter's list pass (cpk_packed.inl)
-        c.bringEl = (expect || geo->emit == CPECAN_EMIT_INDEL) ? c.geo.fbCells * S : 0;
-        if (geo->emit == CPECAN_EMIT_INDEL) c.candEl = 0;  // no candidates
-        // Split (round 4, cpk_packed.inl "MODE"): forward sweeps into rings of the regions' own, then one queue item per
-        // (region, traceback segment).  Worth it where ONE group's walk through the longest region -- its forward and its
-        // backward steps, one after the other -- is what a launch of whole regions waits for: a realign-style batch of
-        // 100-5000 bp alignments took 20 ms with 6 000 pairs and 29 with 50 000 (profiles/r04_config4_chain_bound.txt).
-        // Then the LONG regions of the class -- the device order is longest first -- become a split class of their own,
-        // launched first: their forward chains (half the steps) run beside the whole-region waves of the shorter ones, and
-        // their tracebacks, side by side, behind.  Long: more than half the diagonals of the longest, so that the whole
-        // regions' chains (2 N steps) are no longer than the longest forward chain.  CPECAN_PACKED_SPLIT=1 / 0 (tests, A/B
-        // runs): every region of every packed class / none; CPECAN_PACKED_SPLIT_FROM=<diagonals>: regions longer than that.
-        const int64_t base = regionAt, n = geo->nPacked[k];
-        regionAt += geo->nPacked[k];
-        int64_t cut = 0;  // the first `cut` regions of the class run split
-        {
-            int64_t stepsAll = 0, nMax = 0;
-            int32_t segMax = 0;
-            for (int64_t di = base; di < base + n; di++) {
-                const int64_t N = (int64_t)regions[di].lX + regions[di].lY;
-                segMax = regions[di].nSeg > segMax ? regions[di].nSeg : segMax;
-                stepsAll += 2 * N;
-                nMax = N > nMax ? N : nMax;
-            }
-            const char *env = getenv("CPECAN_PACKED_SPLIT"), *fromEnv = getenv("CPECAN_PACKED_SPLIT_FROM");
-            const bool eligible = geo->emit == CPECAN_EMIT_MATCH && !dynamic && !geo->debug;
-            // (the steps of a wave if the class's steps were dealt out evenly over every wave slot of the chip)
-            const int64_t balanced = stepsAll / (G * slots) + 1;
-            // ... and only for a batch that has the device to itself: with other batches of the process in flight (a
-            // pipeline) their waves fill the slots a chain leaves idle, and the split form -- rings of whole regions in HBM
-            // instead of a cache-resident ring per group, six launches instead of two -- costs throughput: config 4 end to end,
-            // four batches in flight, 35-37 ms per batch with whole regions against 43 split (profiles/r04_config4_chain_bound.txt)
-            const bool lone = !(d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0);
-            if (eligible && env && atoi(env) != 0) cut = n;
-            else if (eligible && !(env && atoi(env) == 0) && (fromEnv || (lone && segMax >= 3 && 2 * nMax * 2 >= balanced * 3))) {
-                const int64_t from = fromEnv ? atoll(fromEnv) : nMax / 2;
-                for (int64_t di = base; di < base + n; di++)  // (ordered by cells, not by diagonals: up to the last long one)
-                    if ((int64_t)regions[di].lX + regions[di].lY > from) cut = di - base + 1;
-            }
-        }
-        for (int part = 0; part < 2; part++) {
-            const int64_t pBase = part == 0 ? base : base + cut, pCount = part == 0 ? cut : n - cut;
-            if (pCount <= 0) continue;
-            LaunchClass cc = c;
-            cc.regionBase = (int)pBase;
-            cc.regionCount = (int)pCount;
-            int64_t waves = (pCount + G - 1) / G;
-            if (waves > slots) waves = slots;
-            cc.waves = (int)waves;
-            cc.subSlots = waves * G;
-            if (part == 0) {
-                int64_t nSegPart = 0;
-                for (int64_t di = pBase; di < pBase + pCount; di++) nSegPart += regions[di].nSeg;
-                cc.split = true;
-                pick_packed_split_kernels(cc.geo, k, &cc.fn, &cc.fnTrace);
-                int64_t wt = (nSegPart + G - 1) / G;
-                if (wt > slots) wt = slots;
-                cc.wavesTrace = (int)wt;
-                if (wt * G > cc.subSlots) cc.subSlots = wt * G;
-                cc.itemCount = nSegPart;
-            }
-            if (getenv("CPECAN_TRACE_HOST"))
-                fprintf(stderr, "cpecan packed class %d: %d regions in groups of %d lanes, LDS %zu B, waves %d / %d, %s\n", k, cc.regionCount, GW,
-                        cc.ldsBytes, cc.waves, cc.wavesTrace, cc.split ? "two launches" : "whole regions");
-            (part == 0 ? packedSplit : packedWhole).push_back(cc);
-        }
-    }
-    {
-        // With other batches of the process alive (a pipeline) the packed launches of a batch SHARE the chip's wave slots in
-        // proportion to what each would ask for alone, instead of each asking for all of them, and one slot per CU in eight
-        // stays free: the waves are persistent, so fewer of them lose nothing, nothing waits in the hardware queues behind
-        // them, and the small kernels of the batches around this one (fills, table build, gather, consumers) find a slot
-        // without waiting for a class to drain.  BASELINE config 4 end to end, six batches in flight, ten runs each over four
-        // calls: 2.16e10 -> 2.33e10 cells/s on average, single runs spread +-10 % either way
-        // (profiles/r04_config4_chain_bound.txt).  CPECAN_PACKED_SHARE=0: as before.
-        const char *shareEnv = getenv("CPECAN_PACKED_SHARE");
-        if (!(shareEnv && atoi(shareEnv) == 0) && d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0) {
-            int64_t total = 0, room = 0;
-            for (const LaunchClass &cc : packedSplit) total += cc.waves;
-            for (const LaunchClass &cc : packedWhole) total += cc.waves;
-            int perCU0 = 0;
-            for (const LaunchClass &cc : packedSplit) if (!perCU0) wavesPerCU(cc.fnTrace, cc.ldsBytes, &perCU0);
-            for (const LaunchClass &cc : packedWhole) if (!perCU0) wavesPerCU(cc.fn, cc.ldsBytes, &perCU0);
-            room = (int64_t)perCU0 * d->numCUs - d->numCUs / 8;
-            if (total > room && room > 0) {
-                auto scale = [&](LaunchClass &cc) {
-                    const int G = CPK_WAVE / (8 << cc.k);
-                    int64_t w = (int64_t)cc.waves * room / total;
-                    cc.waves = (int)(w < 1 ? 1 : w);
-                    if (cc.split) {
-                        int64_t wt = (int64_t)cc.wavesTrace * room / total;
-                        cc.wavesTrace = (int)(wt < cc.waves ? cc.waves : wt);
-                        if (cc.wavesTrace > (int)((cc.itemCount + G - 1) / G)) cc.wavesTrace = (int)((cc.itemCount + G - 1) / G);
-                    }
-                    const int64_t mx = cc.waves > cc.wavesTrace ? cc.waves : cc.wavesTrace;
-                    cc.subSlots = mx * G;
-                };
-                for (LaunchClass &cc : packedSplit) scale(cc);
-                for (LaunchClass &cc : packedWhole) scale(cc);
-            }
-        }
-    }
-    // the split parts first: their forward chains are the longest thing in the batch and start before anything else
-    for (const LaunchClass &cc : packedSplit) d->classes.push_back(cc);
-    for (const LaunchClass &cc : packedWhole) d->classes.push_back(cc);
-    // The LDS of one wave of the class: tables, rolling rows, candidate stage, symbols -- by the form of its sweeps.
-    // Absolute positions (cpk_sweep.inl): two arrays of S rows with a few positions of slack, a stage of 64
-    // candidates, and the symbols of one traceback segment at a time instead of both whole strings.
-    auto setForm = [&](LaunchClass &cc, bool abs) {
-        cc.abs = abs;
-        cc.geo.rollStride = cc.geo.maxWidth + (abs ? kAbsSlack : 1);
-        const char *winEnv = getenv("CPECAN_ABS_WINDOWS");  // 0: the absolute-position sweeps stage whole strings (diagnostics, tests)
-        cc.geo.reserved0 = (abs && winEnv && atoi(winEnv) == 0) ? 1 : 0;
-        cc.geo.seqLdsBytes = (abs && !cc.geo.reserved0) ? geo->wWinLdsBytes[cc.k] : geo->wSeqLdsBytes[cc.k];
-        cc.geo.rollDoubles = (int64_t)(abs ? 2 * S : 2 * S + 1) * cc.geo.rollStride;
-        const size_t header = sizeof(double) * (lds_header_doubles(geo->emit) + lds_stage_doubles(geo->emit, abs));
-        cc.ldsBytes = cc.geo.useGlobalRoll ? header
-                                           : header + sizeof(double) * (size_t)cc.geo.rollDoubles + (size_t)((cc.geo.seqLdsBytes + 15) / 16 * 16);
-    };
-    for (int k = 0; k < CPK_WIDE_CLASSES; k++) {  // then the wide ones: the sweep kernel, one region per wave at a time
-        if (geo->nWide[k] <= 0) continue;
-        LaunchClass c;
-        c.k = k;
-        c.geo = *geo;
-        c.geo.maxWidth = geo->wMaxWidth[k];
-        c.geo.maxRefresh = geo->wMaxRefresh[k];
-        c.geo.ringCells = geo->wRingCells[k];
-        c.geo.fbCells = geo->wFbCells[k];
-        c.geo.seqLdsBytes = geo->wSeqLdsBytes[k];
-        c.geo.rollStride = c.geo.maxWidth + 1;
-        // Will the class run split (its tracebacks as queue items; decided below, once the occupancy is known)?  Then, with
-        // a fixed expansion and bands whose edges move one step per diagonal (CpkRegion::absOk), its sweeps index the
-        // rolling rows by absolute position (cpk_sweep.inl): the rows need a few positions of slack.
-        // CPECAN_ABS=0: never (A/B runs, tests of the other form).
-        int64_t nSegClass = 0;
-        bool absOk = geo->emit == CPECAN_EMIT_MATCH && !dynamic;
-        for (int64_t di = regionAt; di < regionAt + geo->nWide[k]; di++) {
-            nSegClass += regions[di].nSeg;
-            absOk = absOk && regions[di].absOk;
-        }
-        {
-            const char *env = getenv("CPECAN_SPLIT"), *absEnv = getenv("CPECAN_ABS");
-            const bool splitLikely = geo->emit == CPECAN_EMIT_MATCH && (!geo->debug || env) && nSegClass > 0 &&
-                                     (env ? atoi(env) != 0 : nSegClass * 4 >= (int64_t)geo->nWide[k] * 5);
-            c.abs = splitLikely && absOk && !(absEnv && atoi(absEnv) == 0);
-        }
-        c.geo.refreshCells = (int64_t)c.geo.maxWidth * c.geo.maxRefresh;
-        if (c.geo.refreshCells < 1) c.geo.refreshCells = 1;
-        // LDS budget: beyond 64 KiB per wave (rolling buffers + symbol strings, in the form every class can fall back
-        // to: one wave per region) the class takes the global-memory path
-        const bool absWanted = c.abs;
-        c.geo.useGlobalRoll = 0;
-        setForm(c, false);
-        c.geo.useGlobalRoll = c.ldsBytes + 16 > 64 * 1024;
-        setForm(c, absWanted && !c.geo.useGlobalRoll);  // absolute positions are a form of the LDS rows
-        {
-            // Expectation emitter, every diagonal of the class within two 64-lane groups: the events are formed inside the
-            // traceback (Sweep::tracebackExpect) from three forward diagonals kept in LDS, instead of a second pass over B
-            // values parked in global memory.  CPECAN_EXP_INSWEEP=0 (tests, A/B runs): the second pass everywhere; 2: inside
-            // the traceback whatever the LDS costs.
-            const char *env = getenv("CPECAN_EXP_INSWEEP");
-            c.geo.expInSweep = expect && !c.geo.useGlobalRoll && c.geo.maxWidth <= 2 * CPK_WAVE /* Sweep::kExpGroups */ && !(env && atoi(env) == 0);
-            // 1: the build unrolled for ONE group per diagonal (classes up to 64 cells -- the host gives the expectation
-            // emitter a size class of its own there, cpecan_host.c); 2: for two.  CPECAN_EXP_ONE_GROUP=0: always the latter.
-            const char *oneEnv = getenv("CPECAN_EXP_ONE_GROUP");
-            if (c.geo.expInSweep) c.geo.expInSweep = (c.geo.maxWidth <= CPK_WAVE && !(oneEnv && atoi(oneEnv) == 0)) ? 1 : 2;
-            if (c.geo.expInSweep) {
-                const size_t with = c.ldsBytes + sizeof(double) * (size_t)3 * (c.geo.maxWidth + 1) * S + sizeof(double) * kExpectWinCopies * 80 -
-                                    sizeof(double) * (size_t)(lds_header_doubles(geo->emit) - lds_header_doubles(geo->emit, true));
-                // ... as long as the three forward diagonals in LDS do not cost a resident wave: the kernel's registers
-                // allow eight per CU (five-state: bands up to 74 cells, three-state: up to ~120; measured at 66 and 106)
-                if (with <= 160 * 1024 / 8 || (env && atoi(env) >= 2)) c.ldsBytes = with;
-                else c.geo.expInSweep = 0;
-            }
-        }
-        c.fn = pick_kernel(c.geo);
-        if (!c.fn) {
-            cpk_set_error("no kernel for emitter %d", geo->emit);
-            return CPECAN_EINVAL;
-        }
-        int perCU = 0;
-        // Bands of several hundred cells: a team of kTeamWaves waves per region (cpk_team.inl) instead of one wave
-        constexpr int kTeamWaves = 4;
-        // (the team kernel stages both whole strings and keeps 3 S rows of maxWidth + 1 positions, whatever form of the
-        // rows the class would take with one wave per region: NOT c.geo.seqLdsBytes / rollStride, which setForm() above
-        // may have set to the symbol windows and slack of the absolute-position sweeps)
-        const int teamStride = c.geo.maxWidth + 1;
-        const size_t teamLds = sizeof(double) * ((size_t)team_header_doubles(expect) + (size_t)3 * S * teamStride) +
-                               (size_t)((geo->wSeqLdsBytes[k] + 15) / 16 * 16);
-        // A class goes to teams where one wave per region is down to three waves per CU or fewer (measured: at four per
-        // CU, ~400-cell bands, the single wave still wins by 13 %; at three, ~450 cells, the team wins by 30 %), or on
-        // the global-memory variant.  CPECAN_TEAM=<cells> (tests, diagnostics): from that band width instead; 0: never.
-        const char *teamEnv = getenv("CPECAN_TEAM");
-        int soloPerCU = 0;
-        if (int rc = wavesPerCU(c.fn, c.ldsBytes, &soloPerCU)) return rc;
-        const bool wanted = teamEnv ? (atoi(teamEnv) > 0 && c.geo.maxWidth >= atoi(teamEnv))
-                                    : (c.geo.maxWidth > 256 && (soloPerCU <= 3 || c.geo.useGlobalRoll));
-        // one workgroup per CU is all the LDS allows from ~660 cells: then eight waves share the region
-        const bool big = 2 * teamLds > 160 * 1024;
-        if (wanted && (geo->emit == CPECAN_EMIT_MATCH || geo->emit == CPECAN_EMIT_INDEL || expect) && !geo->debug &&
-            c.geo.maxWidth <= CPK_WAVE * kTeamWaves * (big ? 2 : 1) * kTeamGroups && teamLds <= 160 * 1024) {
-            if (expect)  // (round 4: the expectation emitter -- its second pass shared by the team's waves)
-                c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_EXPECT> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_EXPECT>)
-                              : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_EXPECT> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_EXPECT>);
-            else if (geo->emit == CPECAN_EMIT_INDEL)  // (round 4: the three lists of the indel emitter from the team as well)
-                c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_INDEL> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_INDEL>)
-                              : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_INDEL> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_INDEL>);
-            else
-            c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves> : cpecan_pairhmm_team<5, kTeamWaves>)
-                          : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves> : cpecan_pairhmm_team<3, kTeamWaves>);
-            c.threads = CPK_WAVE * kTeamWaves * (big ? 2 : 1);
-            c.geo.useGlobalRoll = 0;
-            c.abs = false;
-            c.geo.reserved0 = 0;
-            c.geo.expInSweep = 0;  // (the team's expectation emitter is the second pass: B of the emitted cells in `bring`)
-            c.geo.rollStride = teamStride;
-            c.geo.seqLdsBytes = geo->wSeqLdsBytes[k];
-            c.geo.rollDoubles = (int64_t)(2 * S + 1) * c.geo.rollStride;
-            c.ldsBytes = teamLds;
-            c.grollEl = 0;
-            hipFuncAttributes attr;
-            HIP_TRY(hipFuncGetAttributes(&attr, (const void *)c.fn));
-            const int vgprAlloc = ((attr.numRegs > 0 ? attr.numRegs : 128) + 7) / 8 * 8;
-            int perSimd = 512 / vgprAlloc;  // a team of four puts one wave on every SIMD, a team of eight two
-            if (perSimd > 8) perSimd = 8;
-            if (big) perSimd /= 2;
-            const int byLds = (int)((160 * 1024) / (teamLds + (size_t)attr.sharedSizeBytes));
-            perCU = perSimd < byLds ? perSimd : byLds;
-            if (perCU < 1) perCU = 1;
-        } else {
-            perCU = soloPerCU;
-            // Three-state match classes with more regions than two waves per SIMD hold take the kernels allocated for
-            // three (168 VGPRs, a handful of spills): 4000 pairs of 1 kb -9 to -19 %, 2500 of 2 kb -17 %, with one wave
-            // per region -34 %; a class that leaves slots empty anyway loses 3-10 % to the spills and the fuller SIMDs
-            // (config A, 1000 pairs: 3.68 -> 4.07 ms) and keeps the 2-wave kernels.  CPECAN_DENSE=1 / 0: always / never.
-            const char *denseEnv = getenv("CPECAN_DENSE");
-            if (S == 3 && geo->emit == CPECAN_EMIT_MATCH && !geo->debug &&
-                (denseEnv ? atoi(denseEnv) != 0 : geo->nWide[k] >= (int64_t)soloPerCU * d->numCUs)) {
-                KernelFn f3 = pick_dense_kernel(c.geo);
-                int p3 = 0;
-                if (int rc = wavesPerCU(f3, c.ldsBytes, &p3)) return rc;
-                if (p3 > perCU) {
-                    c.fn = f3;
-                    c.dense = true;
-                    perCU = p3;
-                }
-            }
-        }
-        if (perCU < 1) {
-            cpk_set_error("kernel does not fit on a CU (LDS %zu bytes)", c.ldsBytes);
-            return CPECAN_EHIP;
-        }
-        const int64_t n = geo->nWide[k];
-        int64_t waves = (int64_t)perCU * d->numCUs;
-        if (waves > n) waves = n;
-        {
-            // Even out the rounds: with R = ceil(regions / waves) rounds, ceil(regions / R) waves do the same work in the
-            // same number of rounds with fewer waves competing per SIMD (10 000 equal pairs: 1667 waves x 6 pairs instead
-            // of 1792 waves of which 1044 do 6 and 748 do 5).
-            const int64_t rounds = (n + waves - 1) / waves;
-            const int64_t even = (n + rounds - 1) / rounds;
-            if (even >= 1 && even < waves) waves = even;
-        }
-        c.waves = (int)waves;
-        c.subSlots = waves;
-        c.regionBase = regionAt;
-        c.regionCount = geo->nWide[k];
-        regionAt += geo->nWide[k];
-        {
-            // Split the class when its regions do not fill the chip and have tracebacks to hand out: the segments of a
-            // region are independent once its forward values exist.  CPECAN_SPLIT=1 / 0 (tests, diagnostics): always / never.
-            int64_t maxRing = 0;
-            for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) {
-                const int64_t rd = split_ring_doubles(regions[di], S);
-                if (rd > maxRing) maxRing = rd;
-            }
-            const char *env = getenv("CPECAN_SPLIT");
-            const int64_t slots = (int64_t)perCU * d->numCUs;
-            // (debug buffers: split only where CPECAN_SPLIT asks for it -- the per-cell parity tests of the split forms)
-            const bool eligible = c.threads == CPK_WAVE && geo->emit == CPECAN_EMIT_MATCH && (!geo->debug || env) && nSegClass > 0;
-            // Regions with tracebacks to hand out (1.25 segments on average and more) run split whenever their rings fit:
-            // measured against one wave per region on 600 to 10 000 pairs of 1-4 kb and bands of 55-124 cells per diagonal,
-            // one of the two split forms won every time (tools/split_forms.py, profiles/r02_split_forms.txt).  Which one:
-            // the ONE-launch form fills the partly empty last round of forward sweeps with traceback items and wins where a
-            // region has many segments (2 kb and longer: -20 to -40 %); with two or three segments per region (1 kb
-            // pairs, config A) its device-scope ring accesses and waiting waves cost more than that gains (+7 to +19 %) and the
-            // two launches win.  The rings of whole regions are given up first when device memory is short (below).
-            const bool manySegs = nSegClass * 4 >= n * 5;
-            const bool wanted = env ? atoi(env) != 0 : manySegs;
-            // ... and up to ~4.5 rounds of forward sweeps: beyond, every region ticket is drawn before the first item anyway,
-            // the overlap is down to the seam between the two phases, and the launches' plain ring stores win against
-            // the one launch's write-through ones (2 kb pairs, band 100: 5000 / 6500 / 8000 pairs -8 / -8 / -2 % for the one
-            // launch, 10 000 pairs -- config B -- +1.7 %: 89.3 against 87.6 ms, and 90.2 against 87.3 ms per pipelined batch)
-            // (round 4, both forms at ten waves per CU: 5000 pairs -3 % for the one launch, 7000 pairs +3 %: ~3.25 rounds)
-            const bool oneLaunch = nSegClass * 2 >= n * 7 /* 3.5 segments per region and more */ && n * 4 < slots * 13;
-            if (eligible && wanted) {
-                c.split = true;
-                // CPECAN_SPLIT=2 / 1: force the one-launch (kModeFused) / two-launch form
-                // (the one-launch form addresses a region's ring with 32-bit byte offsets: Sweep::ringPut)
-                c.fused = (env ? atoi(env) == 2 : oneLaunch) && maxRing < ((int64_t)1 << 28);
-                if (c.fused) {
-                    // an item polls this often (s_sleep between polls: seconds in all) for its region's forward values; a
-                    // count that never comes is reported and the class re-run in two launches (cpk_device_download).
-                    // CPECAN_FUSED_SPIN: tests force that path with a bound of a few polls.
-                    const char *spinEnv = getenv("CPECAN_FUSED_SPIN");
-                    c.geo.fusedSpin = spinEnv ? atoi(spinEnv) : (1 << 24);
-                    c.fn = pick_fused_kernel(c.geo, c.dense, c.abs);
-                    int64_t slotsF = slots;
-                    {
-                        const char *t3e = getenv("CPECAN_FUSED3");  // 0: never the three-waves-per-SIMD build
-                        if (c.abs && S == 5 && !(t3e && atoi(t3e) == 0) && (160 * 1024) / c.ldsBytes >= 9) {
-                            KernelFn f3 = pick_fused_kernel(c.geo, c.dense, c.abs, true);
-                            int p3 = 0;
-                            if (int rc = wavesPerCU(f3, c.ldsBytes, &p3)) return rc;
-                            if (p3 > perCU) {
-                                c.fn = f3;
-                                slotsF = (int64_t)p3 * d->numCUs;
-                            }
-                        }
-                    }
-                    // One CU in eight keeps a wave slot (and its 19 KB of LDS) free: a launch that fills every slot to its
-                    // end starves the small kernels of the batch before it -- the list consumers need a few KB of LDS --
-                    // until it drains, and a pipeline two batches deep then idles between sweeps (82 ms measured).
-                    // ... so the slots are left free when another batch of this process has run on the device and is still
-                    // alive; a batch on its own takes them all (config B: 90.3 -> 89.5 ms).
-                    const int64_t spare = (d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0) ? d->numCUs / 8 : 0;
-                    const int64_t room = slotsF - spare > 0 ? slotsF - spare : slotsF;
-                    int64_t wt = room < n + nSegClass ? room : n + nSegClass;
-                    c.waves = (int)wt;
-                    c.subSlots = wt;
-                } else {
-                    pick_split_kernels(c.geo, c.dense, c.abs, &c.fn, &c.fnTrace);
-                    int64_t wt = slots < nSegClass ? slots : nSegClass;
-                    c.wavesTrace = (int)wt;
-                    if (wt > c.subSlots) c.subSlots = wt;
-                    // the forward launch: no candidate ring in its LDS, and with absolute positions few enough registers
-                    // for three waves per SIMD -- more waves per CU where that LDS allows them (CPECAN_FWD3=0: never)
-                    c.ldsBytesFwd = c.geo.useGlobalRoll ? c.ldsBytes : c.ldsBytes - sizeof(double) * lds_stage_doubles(geo->emit, c.abs);
-                    // ... and so does the traceback launch of a five-state class since round 4 (CPECAN_TRACE3=0: never)
-                    const char *t3e = getenv("CPECAN_TRACE3");
-                    if (c.abs && S == 5 && !(t3e && atoi(t3e) == 0) && (160 * 1024) / c.ldsBytes >= 9) {
-                        KernelFn f2 = nullptr, tr3 = nullptr;
-                        pick_split_kernels(c.geo, c.dense, c.abs, &f2, &tr3, false, true);
-                        int p3 = 0;
-                        if (int rc = wavesPerCU(tr3, c.ldsBytes, &p3)) return rc;
-                        if (p3 > perCU) {
-                            c.fnTrace = tr3;
-                            int64_t w3 = (int64_t)p3 * d->numCUs;
-                            if (w3 > nSegClass) w3 = nSegClass;
-                            c.wavesTrace = (int)w3;
-                            if (w3 > c.subSlots) c.subSlots = w3;
-                        }
-                    }
-                    const char *f3e = getenv("CPECAN_FWD3");
-                    if (c.abs && !(f3e && atoi(f3e) == 0) && (160 * 1024) / c.ldsBytesFwd >= 9) {
-                        KernelFn f3 = nullptr, tr = nullptr;
-                        pick_split_kernels(c.geo, c.dense, c.abs, &f3, &tr, true);
-                        int p3 = 0;
-                        if (int rc = wavesPerCU(f3, c.ldsBytesFwd, &p3)) return rc;
-                        if (p3 > perCU) {
-                            c.fn = f3;
-                            int64_t wf = (int64_t)p3 * d->numCUs;
-                            if (wf > n) wf = n;
-                            const int64_t rounds = (n + wf - 1) / wf, even = (n + rounds - 1) / rounds;
-                            if (even >= 1 && even < wf) wf = even;
-                            c.waves = (int)wf;  // forward waves touch no per-slot scratch: subSlots stays as it is
-                        }
-                    }
-                }
-                c.itemCount = nSegClass;
-            } else if (c.abs) {
-                // one wave per region: the other form of the rows (a class that went to a team of waves keeps the team's LDS)
-                if (c.threads == CPK_WAVE) setForm(c, false);
-                else c.abs = false;
-            }
-        }
-        if (getenv("CPECAN_TRACE_HOST"))
-            fprintf(stderr, "cpecan class %d: %d regions, widest diagonal %d, LDS %zu B (forward launch %zu B), waves %d / %d, %s%s%s%s\n", k,
-                    c.regionCount, c.geo.maxWidth, c.ldsBytes, c.ldsBytesFwd, c.waves, c.wavesTrace,
-                    c.split ? (c.fused ? "one launch" : "two launches") : (c.threads > CPK_WAVE ? "a team of waves per region" : "one wave per region"),
-                    c.abs ? ", absolute positions" : "",
-                    c.dense ? ", three waves per SIMD" : "", c.geo.expInSweep ? ", expectation events inside the traceback" : "");
-        c.ringEl = c.geo.ringCells * S;
-        c.candEl = c.geo.fbCells * nCandLists;
-        c.refEl = c.geo.refreshCells;
-        c.totEl = c.geo.maxRefresh;
-        c.bringEl = expect ? (c.geo.expInSweep ? (int64_t)c.geo.maxRefresh * 96 /* Sweep::kWinDoubles */ : c.geo.fbCells * S) : 0;
-        c.grollEl = (c.geo.useGlobalRoll && c.threads == CPK_WAVE) ? c.geo.rollDoubles : 0;
-        d->classes.push_back(c);
-    }
-    if ((int)d->classes.size() > kMaxClasses || regionAt != geo->nRegions) {
-        cpk_set_error("internal: the size classes do not cover the regions (%d of %d)", regionAt, geo->nRegions);
-        return CPECAN_ESTATE;
-    }
-    // Every resident wave owns scratch sized for its class's LARGEST region (forward ring of one traceback segment,
-    // candidates, refresh series).  One unanchored 3000 x 3000 region (a single segment: 360 MB of ring) in a class of
-    // its own is one wave's worth; where a class still asks for more than the device has free, it keeps as many
-    // waves as fit and the rest of its regions queue behind them.
-    {
-        double fixed = (double)sizeof(CpkRegion) * geo->nRegions + (double)(sizeof(CpkDiag) + sizeof(int32_t)) * nDiags +
-                       (double)sizeof(CpkSegment) * nSegs + (double)nSymbolBytes + 24.0 * nAnchors +
-                       2.0 * 12.0 * nLists * outTriplesPerList /* the triples and their compact copy */;
-        size_t freeB = 0, totalB = 0;
-        HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-        double budget = 0.9 * ((double)freeB + (double)cache_bytes(d->device));  // idle cached blocks are ours to reuse or drop
-        if (const char *mb = getenv("CPECAN_MEM_BUDGET_MB")) budget = 1048576.0 * atof(mb);  // test / diagnostic knob
-        // split classes keep one ring per REGION (it holds every segment of the region), nothing per slot
-        auto planSplit = [&]() {
-            for (LaunchClass &c : d->classes) {
-                if (!c.split) continue;
-                c.ringTotal = 0;
-                for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) c.ringTotal += split_ring_doubles(regions[di], S);
-                c.ringEl = 0;
-            }
-        };
-        auto unsplit = [&]() {  // back to one wave per region with a per-wave ring
-            for (LaunchClass &c : d->classes) {
-                if (!c.split) continue;
-                c.split = false;
-                c.fused = false;
-                c.fnTrace = nullptr;
-                c.itemCount = 0;
-                c.ringTotal = 0;
-                c.ringEl = c.geo.ringCells * S;
-                if (c.packed) {
-                    c.fn = pick_packed_kernel(c.geo, c.k, false);
-                    c.subSlots = (int64_t)c.waves * (CPK_WAVE / (8 << c.k));
-                    continue;
-                }
-                if (c.abs) setForm(c, false);
-                c.fn = c.dense ? pick_dense_kernel(c.geo) : pick_kernel(c.geo);
-                c.subSlots = c.waves;
-            }
-        };
-        planSplit();
-        // The rings of whole regions are a fixed share of the device at most (CPECAN_SPLIT_BUDGET_FRAC, default 0.45: two
-        // pipelined batches fit whatever is free at this moment), so that the same batch always runs in the same form.
-        double splitBudget = 0.45 * (double)totalB;
-        if (const char *fr = getenv("CPECAN_SPLIT_BUDGET_FRAC")) splitBudget = atof(fr) * (double)totalB;
-        double need = 0, floorNeed = 0;
-        auto tally = [&]() {
-            need = floorNeed = fixed;
-            for (const LaunchClass &c : d->classes) {
-                need += c.slotBytes() * (double)c.subSlots + 8.0 * (double)c.ringTotal;
-                floorNeed += c.slotBytes() * (double)(c.subSlots / (c.waves > 0 ? c.waves : 1)) + 8.0 * (double)c.ringTotal;
-            }
-        };
-        tally();
-        if (need > budget || need > splitBudget) {  // whole-region rings are a luxury: give them up before giving up resident waves
-            unsplit();
-            tally();
-        }
-        if (floorNeed > budget) {
-            cpk_set_error("out of device memory: the batch needs %.0f MB with one resident wave per size class, %.0f MB are free",
-                          floorNeed / 1048576.0, budget / 1048576.0);
-            return CPECAN_ENOMEM;
-        }
-        if (need > budget) {
-            // the narrow and less wide classes first: they hold most of the regions
-            double left = budget - floorNeed;
-            for (LaunchClass &c : d->classes) {
-                const int64_t perWave = c.subSlots / c.waves;
-                const double waveBytes = c.slotBytes() * (double)perWave;
-                int64_t extra = waveBytes > 0 ? (int64_t)(left / waveBytes) : c.waves - 1;
-                if (extra > c.waves - 1) extra = c.waves - 1;
-                if (extra < 0) extra = 0;
-                left -= waveBytes * (double)extra;
-                c.waves = (int)(1 + extra);
-                c.subSlots = perWave * c.waves;
-            }
-        }
-    }
+    // ---- the launches of a run: planned (cpk_plan.inl), then carried out ----
+    const PlanKnobs knobs;  // (reads the environment)
+    PlanDevice dev;
+    dev.numCUs = d->numCUs;
+    HIP_TRY(hipMemGetInfo(&dev.freeBytes, &dev.totalBytes));
+    dev.idleCachedBytes = cache_bytes(d->device);
+    dev.othersAlive = d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0;  // (this batch no longer counts: ran_set above)
+    const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
+    if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, &d->classes)) return rc;
     d->totalWaves = 0;
     {
         // (the rings start 64 doubles into their block and the block ends 256 doubles behind them: the streamed traceback's
@@ -1600,7 +961,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
             oGroll += c.subSlots * c.grollEl;
             oExpect += (int64_t)c.waves * (c.threads / CPK_WAVE) * 128;  // a partial result per wave
             d->totalWaves += (c.split && c.wavesTrace > c.waves ? c.wavesTrace : c.waves) * (c.threads / CPK_WAVE);
-            if (c.ldsBytes > 64 * 1024) {
+            if (c.ldsBytes > kLdsPathMaxBytes) {
                 HIP_TRY(hipFuncSetAttribute((const void *)c.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
                 if (c.fnTrace)
                     HIP_TRY(hipFuncSetAttribute((const void *)c.fnTrace, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
@@ -1644,34 +1005,8 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         d->dSegStarts = d->dCounts + (nC + 63) / 64 * 64;
         d->dSegCounts = d->dSegStarts + (nS + 63) / 64 * 64;
     }
-    // split classes: the regions get rings of their own (no wrap: every segment stays readable) and their tracebacks
-    // become queue items, longest first
     std::vector<CpkItem> items;
-    {
-        for (LaunchClass &c : d->classes) {
-            if (!c.split) continue;
-            int64_t ringAt = 0;  // in doubles, from the class's ring pointer (dRing + oRing)
-            c.itemBase = (int64_t)items.size();
-            std::vector<std::pair<int64_t, CpkItem>> byCost;
-            for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) {
-                CpkRegion &rg = regions[di];
-                rg.ringCap = 0x7fffffff;  // never wraps: the ring holds every diagonal of the region
-                rg.ringBase = ringAt;
-                rg.split = 1;
-                ringAt += split_ring_doubles(rg, S);
-                for (int32_t si = 0; si < rg.nSeg; si++) {
-                    const CpkSegment &sg = segs[rg.segOff + si];
-                    // fused: a segment's forward values exist when the forward wave has passed its top diagonal -- items in
-                    // the order in which they become ready (that diagonal), longest first among equals
-                    const int64_t cost = (int64_t)(sg.dTop - sg.tbPrev) * rg.maxWidth;
-                    byCost.push_back({c.fused ? ((int64_t)0x7fffffff - sg.dTop) * ((int64_t)1 << 32) + (cost >> 8) : cost, CpkItem{(int32_t)di, si}});
-                }
-            }
-            std::stable_sort(byCost.begin(), byCost.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
-            for (const auto &e : byCost) items.push_back(e.second);
-            c.itemCount = (int64_t)items.size() - c.itemBase;
-        }
-    }
+    build_item_queue(d->classes, regions, segs, S, &items);
     if (int rc = dev_alloc(d, &d->dItems, items.empty() ? 1 : items.size())) return rc;
     {
         bool anyFused = false;
@@ -1903,7 +1238,7 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
         }
         hipStream_t cs = onCaller ? st : d->sideStream[i];
         if (!onCaller) HIP_TRY(hipStreamWaitEvent(cs, d->evStart, 0));
-        hipLaunchKernelGGL(c.fn, dim3((unsigned)c.waves), dim3((unsigned)c.threads), (c.split && !c.fused && c.ldsBytesFwd) ? c.ldsBytesFwd : c.ldsBytes, cs, p);
+        hipLaunchKernelGGL(c.fn, dim3((unsigned)c.waves), dim3((unsigned)c.threads), c.firstLdsBytes(), cs, p);
         HIP_TRY(hipGetLastError());
         if (c.split && !c.fused) {  // the tracebacks of the class's regions, one queue item each, behind the forward launch
             KArgs t = p;
@@ -1951,10 +1286,7 @@ extern "C" int cpk_device_download(CpkDevice *d, int32_t *counts, int32_t *segSt
             for (LaunchClass &c : d->classes) {
                 if (!c.fused) continue;
                 any = true;
-                c.fused = false;
-                pick_split_kernels(c.geo, c.dense, c.abs, &c.fn, &c.fnTrace);
-                c.wavesTrace = c.waves;
-                if (c.waves > c.regionCount) c.waves = c.regionCount;
+                unfuse(c);
             }
             if (!any || d->fusedRetried) {
                 cpk_set_error("fused launch: a traceback item waited in vain for its region's forward sweep");
