@@ -77,6 +77,34 @@ class ProblemRuns(C.Structure):
                 ("raggedLeft", C.c_int32), ("raggedRight", C.c_int32)]
 
 
+class AnchorParams(C.Structure):
+    """cpecan_anchor_params: seed, substitution scores and thresholds of the anchor finder."""
+    _fields_ = [("seed", C.c_char * 32), ("maxSeedOccurrences", C.c_int32), ("scores", C.c_int32 * 25),
+                ("xDrop", C.c_int32), ("hspThreshold", C.c_int32), ("maxHsps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AnchorProblem(C.Structure):
+    """cpecan_anchor_problem: one element of cpecan_find_anchor_runs_many."""
+    _fields_ = [("sX", C.c_char_p), ("lX", C.c_int64), ("sY", C.c_char_p), ("lY", C.c_int64)]
+
+
+class AnchorStats(C.Structure):
+    """cpecan_anchor_stats."""
+    _fields_ = [("hits", C.c_int64), ("hsps", C.c_int64), ("chained", C.c_int64), ("runs", C.c_int64),
+                ("anchorColumns", C.c_int64), ("subProblems", C.c_int64), ("largestGapTop", C.c_int64),
+                ("largestGap", C.c_int64), ("capped", C.c_int32), ("reserved", C.c_int32), ("kernelMs", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+# pairwiseAlignmentBandingParameters_construct (impl/pairwiseAligner.c:1340-1342): the fields of the reference's
+# PairwiseAlignmentParameters that only the anchoring reads
+CONSTRAINT_DIAGONAL_TRIM = 14
+ANCHOR_MATRIX_BIGGER_THAN_THIS = 500 * 500
+REPEAT_MASK_MATRIX_BIGGER_THAN_THIS = 500 * 500
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("problems", C.c_int64), ("regions", C.c_int64), ("cells", C.c_int64), ("diagonals", C.c_int64),
@@ -102,6 +130,7 @@ EXPORTS = [
     "cpecan_filter_to_remove_overlap", "cpecan_cache_trim", "cpecan_ref_cells",
     "cpecan_batch_add_many_runs", "cpecan_anchor_runs", "cpecan_anchor_runs_from_alignment",
     "cpecan_batch_set_model",
+    "cpecan_anchor_params_default", "cpecan_find_anchor_runs_many", "cpecan_find_anchor_runs", "cpecan_find_anchor_runs_once",
 ]
 OP_MATCH, OP_INDEL_X, OP_INDEL_Y = 0, 1, 2
 POST_REWEIGHT, POST_MEA, POST_LEFT_SHIFT, POST_ORDERED = 1, 2, 4, 8
@@ -191,6 +220,13 @@ def lib():
     L.cpecan_get_shifted_mea_alignment.argtypes = [
         C.POINTER(StateMachine), C.c_char_p, C.c_char_p, i64p, C.c_int64, C.POINTER(PairwiseAlignmentParameters),
         C.c_float, C.c_int, C.c_int, C.POINTER(i32p), i64p, dp]
+    L.cpecan_anchor_params_default.argtypes = [C.POINTER(AnchorParams)]
+    L.cpecan_find_anchor_runs_many.argtypes = [C.POINTER(AnchorProblem), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                               C.POINTER(AnchorParams), C.c_int, C.POINTER(i64p), i64p, C.POINTER(AnchorStats)]
+    L.cpecan_find_anchor_runs.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                          C.POINTER(AnchorParams), C.POINTER(i64p), i64p, C.POINTER(AnchorStats)]
+    L.cpecan_find_anchor_runs_once.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                               C.POINTER(AnchorParams), C.POINTER(i64p), i64p]
     _lib = L
     return L
 
@@ -308,6 +344,94 @@ def cache_trim(device=-1):
     return int(lib().cpecan_cache_trim(device))
 
 
+def anchor_params_default(**overrides):
+    """cpecan_anchor_params_default, with fields replaced by keyword (seed as str or bytes, scores as 25 ints)."""
+    q = AnchorParams()
+    _check(lib().cpecan_anchor_params_default(C.byref(q)), "cpecan_anchor_params_default")
+    for k, v in overrides.items():
+        if not hasattr(q, k):
+            raise AttributeError(k)
+        if k == "seed":
+            v = _bytes(v)
+        elif k == "scores":
+            v = (C.c_int32 * 25)(*[int(x) for x in v])
+        setattr(q, k, v)
+    return q
+
+
+def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
+                          anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
+                          repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0):
+    """cpecan_find_anchor_runs_many on (sX, sY, ...) tuples: ([int64[nRuns, 4] per problem], [statistics dict per problem])."""
+    problems = list(problems)
+    n = len(problems)
+    arr = (AnchorProblem * max(1, n))()
+    keep = []
+    for i, pr in enumerate(problems):
+        sx, sy = _bytes(pr[0]), _bytes(pr[1])
+        keep.append((sx, sy))
+        arr[i].sX, arr[i].lX, arr[i].sY, arr[i].lY = sx, len(sx), sy, len(sy)
+    i64p = C.POINTER(C.c_int64)
+    runs = (i64p * max(1, n))()
+    counts = (C.c_int64 * max(1, n))()
+    stats = (AnchorStats * max(1, n))()
+    _check(lib().cpecan_find_anchor_runs_many(arr, n, trim, expansion, anchorMatrixBiggerThanThis,
+                                              repeatMaskMatrixBiggerThanThis, C.byref(params) if params is not None else None,
+                                              device, runs, counts, stats), "cpecan_find_anchor_runs_many")
+    out = []
+    for i in range(n):
+        c = counts[i]
+        if c:
+            out.append(np.ctypeslib.as_array(runs[i], shape=(c * 4,)).copy().reshape(c, 4))
+        else:
+            out.append(np.zeros((0, 4), dtype=np.int64))
+        if runs[i]:
+            lib().cpecan_free(C.cast(runs[i], C.c_void_p))
+    return out, [stats[i].as_dict() for i in range(n)]
+
+
+def find_anchor_runs(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
+                     anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
+                     repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None):
+    """cpecan_find_anchor_runs: (int64[nRuns, 4] of (x, y, length, expansion), statistics dict), on the current device."""
+    sx, sy = _bytes(sX), _bytes(sY)
+    runs, cnt, st = C.POINTER(C.c_int64)(), C.c_int64(), AnchorStats()
+    _check(lib().cpecan_find_anchor_runs(sx, len(sx), sy, len(sy), trim, expansion, anchorMatrixBiggerThanThis,
+                                         repeatMaskMatrixBiggerThanThis, C.byref(params) if params is not None else None,
+                                         C.byref(runs), C.byref(cnt), C.byref(st)), "cpecan_find_anchor_runs")
+    out = np.zeros((0, 4), dtype=np.int64)
+    if cnt.value:
+        out = np.ctypeslib.as_array(runs, shape=(cnt.value * 4,)).copy().reshape(cnt.value, 4)
+    if runs:
+        lib().cpecan_free(C.cast(runs, C.c_void_p))
+    return out, st.as_dict()
+
+
+def find_anchor_runs_once(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20, softMask=True, params=None):
+    """cpecan_find_anchor_runs_once: steps 1-5 alone (one getBlastPairs call of the reference), int64[nRuns, 4]."""
+    sx, sy = _bytes(sX), _bytes(sY)
+    runs, cnt = C.POINTER(C.c_int64)(), C.c_int64()
+    _check(lib().cpecan_find_anchor_runs_once(sx, len(sx), sy, len(sy), trim, expansion, int(softMask),
+                                              C.byref(params) if params is not None else None, C.byref(runs), C.byref(cnt)),
+           "cpecan_find_anchor_runs_once")
+    out = np.zeros((0, 4), dtype=np.int64)
+    if cnt.value:
+        out = np.ctypeslib.as_array(runs, shape=(cnt.value * 4,)).copy().reshape(cnt.value, 4)
+    if runs:
+        lib().cpecan_free(C.cast(runs, C.c_void_p))
+    return out
+
+
+def runs_to_anchors(runs):
+    """(x, y, length, expansion) runs as the int64[n, 3] anchor list they stand for."""
+    runs = np.asarray(runs, dtype=np.int64).reshape(-1, 4)
+    if runs.shape[0] == 0:
+        return np.zeros((0, 3), dtype=np.int64)
+    k = np.concatenate([np.arange(l) for l in runs[:, 2]])
+    rep = np.repeat(runs, runs[:, 2], axis=0)
+    return np.stack([rep[:, 0] + k, rep[:, 1] + k, rep[:, 3]], axis=1)
+
+
 class Batch:
     """N independent alignment problems on one GPU (cpecan_batch_*)."""
 
@@ -392,6 +516,26 @@ class Batch:
     def add_many_runs(self, problems):
         arr, n, _keep = self.prepare_problems_runs(problems)
         return self.add_prepared(arr, n)
+
+    def add_many_unanchored(self, problems, trim=CONSTRAINT_DIAGONAL_TRIM,
+                            anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
+                            repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0):
+        """problems: iterable of (sX, sY[, raggedLeft, raggedRight]) without anchors: the anchors of all of them are found
+        in one anchor batch on `device` (the batch's device) with the batch's diagonalExpansion, then the problems are added
+        as runs.  Returns (index of the first, anchor statistics per problem)."""
+        problems = list(problems)
+        runs, stats = find_anchor_runs_many(problems, trim, self._p.diagonalExpansion, anchorMatrixBiggerThanThis,
+                                            repeatMaskMatrixBiggerThanThis, params, device)
+        arr = (ProblemRuns * max(1, len(problems)))()
+        keep = []
+        for i, pr in enumerate(problems):
+            sx, sy = _bytes(pr[0]), _bytes(pr[1])
+            keep.append((sx, sy))
+            arr[i].sX, arr[i].lX, arr[i].sY, arr[i].lY = sx, len(sx), sy, len(sy)
+            arr[i].runs, arr[i].nRuns = runs[i].ctypes.data_as(C.POINTER(C.c_int64)), runs[i].shape[0]
+            arr[i].raggedLeft = int(pr[2]) if len(pr) > 2 else 0
+            arr[i].raggedRight = int(pr[3]) if len(pr) > 3 else 0
+        return self.add_prepared(arr, len(problems)), stats
 
     def add_many(self, problems):
         """problems: iterable of (sX, sY, anchorPairs[, raggedLeft, raggedRight]); cut, converted and copied in parallel
@@ -485,6 +629,41 @@ def getAlignedPairsUsingAnchors(sM, sX, sY, anchorPairs, p, alignmentHasRaggedLe
     res = np.ctypeslib.as_array(out, shape=(max(cnt.value, 1) * 3,))[:cnt.value * 3].copy().reshape(cnt.value, 3)
     lib().cpecan_free(C.cast(out, C.c_void_p))
     return res
+
+
+def getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, constraintDiagonalTrim=CONSTRAINT_DIAGONAL_TRIM,
+                                                anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
+                                                repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS,
+                                                anchorParams=None):
+    """impl/pairwiseAligner.c:1162 with this library's anchor finder in lastz's place: int64[n, 3] anchors (x, y,
+    p.diagonalExpansion); none up to anchorMatrixBiggerThanThis."""
+    if len(_bytes(sX)) * len(_bytes(sY)) <= anchorMatrixBiggerThanThis:
+        return np.zeros((0, 3), dtype=np.int64)
+    runs, _ = find_anchor_runs(sX, sY, constraintDiagonalTrim, p.diagonalExpansion, anchorMatrixBiggerThanThis,
+                               repeatMaskMatrixBiggerThanThis, anchorParams)
+    return runs_to_anchors(runs)
+
+
+def getAlignedPairs(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False, **anchoring):
+    """impl/pairwiseAligner.c:1481: getAlignedPairsUsingAnchors with the anchors found from the two sequences.  anchoring:
+    constraintDiagonalTrim, anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis (the reference's defaults),
+    anchorParams."""
+    anchors = getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, **anchoring)
+    return getAlignedPairsUsingAnchors(sM, sX, sY, anchors, p, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd)
+
+
+def getAlignedPairsWithIndels(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False, **anchoring):
+    """impl/pairwiseAligner.c:1489."""
+    anchors = getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, **anchoring)
+    return getAlignedPairsWithIndelsUsingAnchors(sM, sX, sY, anchors, p, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd)
+
+
+def getExpectations(sM, hmmExpectations, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False,
+                    **anchoring):
+    """impl/pairwiseAligner.c:1507."""
+    anchors = getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, **anchoring)
+    return getExpectationsUsingAnchors(sM, hmmExpectations, sX, sY, anchors, p, alignmentHasRaggedLeftEnd,
+                                       alignmentHasRaggedRightEnd)
 
 
 def _take_list(ptr, n):

@@ -1,0 +1,228 @@
+/*
+ * cpecan_align -- command line of cPecanAlign (cPecanAlign.c:91-164): every query sequence against every target
+ * sequence, five-state default model, getAlignedPairs with both ends ragged, reweightAlignedPairs2 with gapGamma, ordered
+ * filter at 0.9, one cigar per pair on stdout.  Unlike the reference's loop, the anchors of all pairs are found in one
+ * anchor batch (cpecan_find_anchor_runs_many) and all pairs are aligned in one DP batch.  Output order: queries in file
+ * order, for each the targets in file order (the reference iterates hash tables, so it defines no order).
+ */
+#define _POSIX_C_SOURCE 200809L
+#include <ctype.h>
+#include <getopt.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "cpecan_realign.h"
+
+typedef struct {
+    char *name, *seq;
+    int64_t length;
+} Record;
+
+typedef struct {
+    Record *r;
+    int64_t n, cap;
+} Records;
+
+static void usage(void) {
+    fprintf(stderr, "cpecan_align [options] target.fa query.fa > cigars\n"
+                    "-y --loadHmm FILE  -g --device N  -h --help\n");
+}
+
+static int fail(const char *what) {
+    const char *e = cpecan_last_error();
+    fprintf(stderr, "cpecan_align: %s: %s\n", what, e ? e : "");
+    return 1;
+}
+
+/* fastaRead + the first white-space delimited token of the header as the name (cPecanAlign.c:17-37) */
+static int read_fasta(const char *path, Records *out) {
+    FILE *f = fopen(path, "r");
+    if (!f) return -1;
+    char *line = NULL;
+    size_t lineCap = 0;
+    int64_t seqCap = 0;
+    int rc = 0;
+    Record *cur = NULL;
+    while (getline(&line, &lineCap, f) >= 0) {
+        if (line[0] == '>') {
+            if (out->n == out->cap) {
+                out->cap = out->cap ? 2 * out->cap : 16;
+                Record *g = realloc(out->r, sizeof *g * (size_t)out->cap);
+                if (!g) { rc = -1; break; }
+                out->r = g;
+            }
+            cur = &out->r[out->n++];
+            const size_t len = strcspn(line + 1, " \t\r\n");
+            cur->name = strndup(line + 1, len);
+            cur->seq = NULL;
+            cur->length = 0;
+            seqCap = 0;
+            if (!cur->name) { rc = -1; break; }
+        } else if (cur) {
+            for (const char *p = line; *p; p++) {
+                if (isspace((unsigned char)*p)) continue;
+                if (cur->length + 1 >= seqCap) {
+                    seqCap = seqCap ? 2 * seqCap : 1024;
+                    char *g = realloc(cur->seq, (size_t)seqCap);
+                    if (!g) { rc = -1; break; }
+                    cur->seq = g;
+                }
+                cur->seq[cur->length++] = *p;
+            }
+            if (rc) break;
+        }
+    }
+    for (int64_t i = 0; rc == 0 && i < out->n; i++) {
+        if (!out->r[i].seq && !(out->r[i].seq = malloc(1))) rc = -1;
+        if (rc == 0) out->r[i].seq[out->r[i].length] = 0;
+    }
+    free(line);
+    fclose(f);
+    return rc;
+}
+
+static void free_records(Records *a) {
+    for (int64_t i = 0; i < a->n; i++) {
+        free(a->r[i].name);
+        free(a->r[i].seq);
+    }
+    free(a->r);
+}
+
+static int by_x(const void *a, const void *b) {
+    const int64_t *p = a, *q = b;
+    return p[0] < q[0] ? -1 : p[0] > q[0];
+}
+
+int main(int argc, char **argv) {
+    const char *hmmFile = NULL;
+    long long device = 0;
+    static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
+                                       {"loadHmm", required_argument, 0, 'y'},
+                                       {"device", required_argument, 0, 'g'},
+                                       {0, 0, 0, 0}};
+    for (int key; (key = getopt_long(argc, argv, "hy:g:", longOpts, NULL)) != -1;) {
+        switch (key) {
+        case 'h': usage(); return 0;
+        case 'y': hmmFile = optarg; break;
+        case 'g': if (sscanf(optarg, "%lld", &device) != 1) { usage(); return 1; } break;
+        default: usage(); return 1;
+        }
+    }
+    if (argc - optind != 2) { /* cPecanAlign.c:93-96 */
+        usage();
+        return 1;
+    }
+    cpecan_model model;
+    if (hmmFile) {
+        cpecan_hmm hmm;
+        if (cpecan_hmm_load(&hmm, hmmFile) != CPECAN_OK || cpecan_model_from_hmm(&model, &hmm) != CPECAN_OK) return fail("loadHmm");
+    } else if (cpecan_model_default(&model, CPECAN_FIVE_STATE) != CPECAN_OK) { /* :100 */
+        return fail("model");
+    }
+    cpecan_params params;
+    cpecan_params_default(&params); /* :102 */
+    const int64_t trim = 14, anchorMatrix = 500 * 500, repeatMaskMatrix = 500 * 500; /* pairwiseAligner.c:1340-1342 */
+    const double gapGamma = 0.5;                                                     /* :1345 */
+    Records targets = {0}, queries = {0};
+    if (read_fasta(argv[optind], &targets) != 0) {
+        fprintf(stderr, "cpecan_align: cannot read %s\n", argv[optind]);
+        return 1;
+    }
+    if (read_fasta(argv[optind + 1], &queries) != 0) {
+        fprintf(stderr, "cpecan_align: cannot read %s\n", argv[optind + 1]);
+        return 1;
+    }
+    const int64_t n = targets.n * queries.n;
+    int status = 0;
+    cpecan_anchor_problem *ap = calloc((size_t)(n ? n : 1), sizeof *ap);
+    cpecan_problem_runs *pr = calloc((size_t)(n ? n : 1), sizeof *pr);
+    int64_t **runs = calloc((size_t)(n ? n : 1), sizeof *runs), *nRuns = calloc((size_t)(n ? n : 1), sizeof *nRuns);
+    cpecan_batch *b = NULL;
+    if (!ap || !pr || !runs || !nRuns) status = 1;
+    for (int64_t q = 0, i = 0; status == 0 && q < queries.n; q++) /* :110-114 */
+        for (int64_t t = 0; t < targets.n; t++, i++) {
+            ap[i].sX = targets.r[t].seq; /* :123: the target is X */
+            ap[i].lX = targets.r[t].length;
+            ap[i].sY = queries.r[q].seq;
+            ap[i].lY = queries.r[q].length;
+        }
+    if (status == 0 && n > 0) {
+        if (cpecan_find_anchor_runs_many(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix, NULL, (int)device,
+                                         runs, nRuns, NULL) != CPECAN_OK)
+            status = fail("anchors");
+    }
+    if (status == 0 && n > 0) {
+        for (int64_t i = 0; i < n; i++) {
+            pr[i].sX = ap[i].sX;
+            pr[i].lX = ap[i].lX;
+            pr[i].sY = ap[i].sY;
+            pr[i].lY = ap[i].lY;
+            pr[i].runs = runs[i];
+            pr[i].nRuns = nRuns[i];
+            pr[i].raggedLeft = pr[i].raggedRight = 1; /* :125 */
+        }
+        if (cpecan_batch_create(&b, &model, &params, CPECAN_EMIT_MATCH, (int)device) != CPECAN_OK) status = fail("batch");
+        else if (cpecan_batch_set_post(b, CPECAN_POST_REWEIGHT | CPECAN_POST_ORDERED, gapGamma) != CPECAN_OK ||
+                 cpecan_batch_set_match_gamma(b, 0.9f) != CPECAN_OK) /* :129-139 */
+            status = fail("consumers");
+        else if (cpecan_batch_add_many_runs(b, pr, n) < 0) status = fail("add");
+        else if (cpecan_batch_upload(b) != CPECAN_OK) status = fail("upload");
+        else if (cpecan_batch_run(b, NULL) != CPECAN_OK) status = fail("run");
+        else if (cpecan_batch_download(b) != CPECAN_OK) status = fail("download");
+    }
+    char *text = NULL;
+    int64_t textCap = 0;
+    for (int64_t i = 0; status == 0 && i < n; i++) {
+        const int32_t *tr = NULL;
+        int64_t cnt = 0;
+        if (cpecan_batch_result(b, i, 3, &tr, &cnt) != CPECAN_OK) {
+            status = fail("result");
+            break;
+        }
+        int64_t *xy = malloc(sizeof *xy * 2 * (size_t)(cnt ? cnt : 1));
+        if (!xy) {
+            status = 1;
+            break;
+        }
+        for (int64_t k = 0; k < cnt; k++) { /* :144-145 */
+            xy[2 * k] = tr[3 * k + 1];
+            xy[2 * k + 1] = tr[3 * k + 2];
+        }
+        qsort(xy, (size_t)cnt, sizeof *xy * 2, by_x);
+        cpecan_cigar c;
+        memset(&c, 0, sizeof c);
+        if (cpecan_cigar_from_aligned_pairs(targets.r[i % targets.n].name, queries.r[i / targets.n].name, 0.0, ap[i].lX, ap[i].lY, xy,
+                                            cnt, &c) != CPECAN_OK) {
+            status = fail("cigar");
+        } else {
+            const int64_t need = cpecan_cigar_format(&c, NULL, 0) + 1;
+            if (need > textCap) {
+                char *g = realloc(text, (size_t)(2 * need));
+                if (g) {
+                    text = g;
+                    textCap = 2 * need;
+                } else {
+                    status = 1;
+                }
+            }
+            if (status == 0) {
+                cpecan_cigar_format(&c, text, textCap);
+                puts(text); /* :149 */
+            }
+            cpecan_cigar_clear(&c);
+        }
+        free(xy);
+    }
+    free(text);
+    if (b) cpecan_batch_destroy(b);
+    for (int64_t i = 0; runs && i < n; i++) cpecan_free(runs[i]);
+    free(runs);
+    free(nRuns);
+    free(ap);
+    free(pr);
+    free_records(&targets);
+    free_records(&queries);
+    return status;
+}

@@ -538,31 +538,54 @@ stList *filterPairwiseAlignmentToMakePairsOrdered(stList *alignedPairs, const ch
     stList_destruct(alignedPairs); /* "Destroys input list of aligned pairs in process" (multipleAligner.c:943) */
     return l;
 }
-/* getBlastPairsForPairwiseAlignmentParameters (:1162-1166) up to the size at which the reference turns to lastz */
-static stList *no_anchors_or_die(const char *sX, const char *sY, const PairwiseAlignmentParameters *p, const char *what) {
-    const int64_t lX = (int64_t)strlen(sX), lY = (int64_t)strlen(sY);
-    if (lX * lY > p->anchorMatrixBiggerThanThis)
-        die("cpecan_hip: %s on a %lld x %lld matrix needs lastz anchors (anchorMatrixBiggerThanThis = %lld), which this "
-            "library does not compute: use the *UsingAnchors entry point",
-            what, (long long)lX, (long long)lY, (long long)p->anchorMatrixBiggerThanThis);
-    return stList_construct();
+/* getBlastPairs (:1005): one search of the whole matrix; the anchor finder of this library stands where lastz does */
+static stList *list_of_runs(const int64_t *runs, int64_t nRuns) {
+    stList *l = stList_construct3(0, (void (*)(void *))stIntTuple_destruct);
+    for (int64_t i = 0; i < nRuns; i++)
+        for (int64_t k = 0; k < runs[4 * i + 2]; k++)
+            stList_append(l, stIntTuple_construct3(runs[4 * i] + k, runs[4 * i + 1] + k, runs[4 * i + 3]));
+    return l;
+}
+stList *getBlastPairs(const char *sX, const char *sY, int64_t lX, int64_t lY, int64_t trim, int64_t diagonalExpansion,
+                      bool repeatMask) {
+    int64_t *runs = NULL, nRuns = 0;
+    check(cpecan_find_anchor_runs_once(sX, lX, sY, lY, trim, diagonalExpansion, repeatMask, NULL, &runs, &nRuns), "getBlastPairs");
+    stList *l = list_of_runs(runs, nRuns);
+    cpecan_free(runs);
+    return l;
+}
+/* getBlastPairsForPairwiseAlignmentParameters (:1162-1196): nothing up to anchorMatrixBiggerThanThis, beyond it the
+ * top-level search and one level of recursion into the gaps */
+stList *getBlastPairsForPairwiseAlignmentParameters(const char *sX, const char *sY, const int64_t lX, const int64_t lY,
+                                                    PairwiseAlignmentParameters *p) {
+    if (lX * lY <= p->anchorMatrixBiggerThanThis) return stList_construct();
+    int64_t *runs = NULL, nRuns = 0;
+    check(cpecan_find_anchor_runs(sX, lX, sY, lY, p->constraintDiagonalTrim, p->diagonalExpansion, p->anchorMatrixBiggerThanThis,
+                                  p->repeatMaskMatrixBiggerThanThis, NULL, &runs, &nRuns, NULL),
+          "getBlastPairsForPairwiseAlignmentParameters");
+    stList *l = list_of_runs(runs, nRuns);
+    cpecan_free(runs);
+    return l;
+}
+static stList *anchors_for(const char *sX, const char *sY, PairwiseAlignmentParameters *p) {
+    return getBlastPairsForPairwiseAlignmentParameters(sX, sY, (int64_t)strlen(sX), (int64_t)strlen(sY), p);
 }
 stList *getAlignedPairs(StateMachine *sM, const char *sX, const char *sY, PairwiseAlignmentParameters *p, bool raggedLeft,
                         bool raggedRight) {
-    stList *anchors = no_anchors_or_die(sX, sY, p, "getAlignedPairs");
+    stList *anchors = anchors_for(sX, sY, p);
     stList *l = getAlignedPairsUsingAnchors(sM, sX, sY, anchors, p, raggedLeft, raggedRight);
     stList_destruct(anchors);
     return l;
 }
 void getAlignedPairsWithIndels(StateMachine *sM, const char *sX, const char *sY, PairwiseAlignmentParameters *p,
                                stList **alignedPairs, stList **gapXPairs, stList **gapYPairs, bool raggedLeft, bool raggedRight) {
-    stList *anchors = no_anchors_or_die(sX, sY, p, "getAlignedPairsWithIndels");
+    stList *anchors = anchors_for(sX, sY, p);
     getAlignedPairsWithIndelsUsingAnchors(sM, sX, sY, anchors, p, alignedPairs, gapXPairs, gapYPairs, raggedLeft, raggedRight);
     stList_destruct(anchors);
 }
 void getExpectations(StateMachine *sM, Hmm *hmmExpectations, const char *sX, const char *sY, PairwiseAlignmentParameters *p,
                      bool raggedLeft, bool raggedRight) {
-    stList *anchors = no_anchors_or_die(sX, sY, p, "getExpectations");
+    stList *anchors = anchors_for(sX, sY, p);
     getExpectationsUsingAnchors(sM, hmmExpectations, sX, sY, anchors, p, raggedLeft, raggedRight);
     stList_destruct(anchors);
 }

@@ -224,6 +224,34 @@ int cpk_device_waves(const CpkDevice *dev);
 void cpk_set_error(const char *fmt, ...);
 int cpk_host_threads(void); /* threads of the host's parallel loops (cpecan_host.c) */
 
+/* ---- the anchor finder (cpk_anchor.inl; host side in cpecan_anchor.c) ---- */
+/* One problem of an anchor pass: two substrings of the context's symbol buffer.  The host fills the first block, the
+ * device layer sizes the lists (second block) and the kernels leave the counts (third block). */
+typedef struct {
+    int64_t xOff, yOff; /* first symbol of X / Y in the context's buffer */
+    int32_t lX, lY;
+    int32_t softMask;   /* windows with a lower-case base at a seed position are skipped */
+    int32_t capX, capY; /* key slots: the window counts rounded up to a power of two */
+    int32_t hspCap;     /* HSP slots: the hit count rounded up to a power of two */
+    int64_t keyXOff, keyYOff, hspOff;
+    int32_t hits, hsps, chained, nRuns, capped, pad;
+    int64_t columns;
+} CpkAnchorProblem;
+
+typedef struct {
+    int32_t scores[25]; /* [a*5+b], symbols a c g t n */
+    int32_t maxSeedOccurrences, xDrop, hspThreshold, maxHsps;
+} CpkAnchorParams;
+
+typedef struct CpkAnchorCtx CpkAnchorCtx;
+/* Copies the nBytes raw sequence bytes to `device` and packs them into symbols there. */
+int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes);
+/* Steps 1-5 of the anchor finder on n problems.  seed: '0' / '1' string.  *runs receives a malloc'd array of triples
+ * (x, y, length) relative to each problem; problem i owns triples hspOff .. hspOff + nRuns - 1.  *ms: kernel time added. */
+int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, CpkAnchorProblem *probs, int64_t n,
+                    int32_t trim, int32_t **runs, double *ms);
+void cpk_anchor_close(CpkAnchorCtx *c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,7 @@ extern "C" const char *cpk_last_error(void) { return g_err; }
 #include "cpk_packed.inl"
 #include "cpk_post.inl"
 #include "cpk_cells.inl"
+#include "cpk_anchor.inl"
 
 // ------------------------------------------------------------------------------------------------
 // host side of the HIP TU: memory, launch, timing
@@ -1600,3 +1601,168 @@ extern "C" int cpk_device_form(const CpkDevice *d) {
     return (c.split ? (c.fused ? CPECAN_FORM_FUSED : CPECAN_FORM_SPLIT) : CPECAN_FORM_WHOLE) | (c.abs ? CPECAN_FORM_ABS : 0);
 }
 extern "C" int cpk_device_waves(const CpkDevice *d) { return d->totalWaves; }
+
+// ------------------------------------------------------------------------------------------------
+// The anchor finder (cpk_anchor.inl).  A context holds the packed symbols of one call; a pass runs steps 1-5 on a list of
+// problems (the top level, then the gaps of the recursion).  The host sizes lists and launches; two small copies per pass
+// come back in the middle (the hit counts size the HSP lists).
+// ------------------------------------------------------------------------------------------------
+struct CpkAnchorCtx {
+    int device = 0;
+    PostScratch *sc = nullptr;
+    uint8_t *dSym = nullptr;
+    int64_t nSym = 0;
+    hipEvent_t evA = nullptr, evB = nullptr;
+};
+
+static int anchor_pow2(int64_t v) {
+    int64_t c = 1;
+    while (c < v) c <<= 1;
+    return (int)c;
+}
+
+extern "C" void cpk_anchor_close(CpkAnchorCtx *c) {
+    if (!c) return;
+    DeviceGuard guard(c->device);
+    if (c->evA) (void)hipEventDestroy(c->evA);
+    if (c->evB) (void)hipEventDestroy(c->evB);
+    delete c->sc;
+    delete c;
+}
+
+extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes) {
+    const int nDev = cpk_device_count();
+    if (nDev <= 0 || device < 0 || device >= nDev) {
+        cpk_set_error("no usable HIP device (count=%d, requested=%d): the HIP path has no CPU fallback", nDev, device);
+        return CPECAN_ENODEVICE;
+    }
+    CPK_ON_DEVICE(device);
+    CpkAnchorCtx *c = new CpkAnchorCtx;
+    c->device = device;
+    c->sc = new PostScratch(nullptr);
+    *out = c;  // the caller closes it on every path
+    if (!c->sc->stream) {
+        cpk_set_error("hipStreamCreate failed in the anchor finder");
+        return CPECAN_EHIP;
+    }
+    HIP_TRY(hipEventCreate(&c->evA));
+    HIP_TRY(hipEventCreate(&c->evB));
+    c->nSym = nBytes;
+    uint8_t *dRaw = nullptr;
+    if (int rc = c->sc->alloc(&dRaw, (size_t)nBytes)) return rc;
+    if (int rc = c->sc->alloc(&c->dSym, (size_t)((nBytes + 1) / 2))) return rc;
+    if (nBytes > 0) {
+        HIP_TRY(hipMemcpyAsync(dRaw, bytes, (size_t)nBytes, hipMemcpyHostToDevice, c->sc->stream));
+        const unsigned blocks = (unsigned)std::min<int64_t>(((nBytes + 1) / 2 + 255) / 256, 65535);
+        hipLaunchKernelGGL(cpk_anchor_pack, dim3(blocks), dim3(256), 0, c->sc->stream, dRaw, nBytes, c->dSym);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->sc->stream));  // `bytes` is the caller's again
+    }
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seedText, CpkAnchorProblem *probs,
+                               int64_t n, int32_t trim, int32_t **runsOut, double *ms) {
+    *runsOut = nullptr;
+    if (n <= 0) return CPECAN_OK;
+    CpkAnchorSeed seed = {};
+    seed.span = (int32_t)strlen(seedText);
+    for (int i = 0; i < seed.span; i++) {
+        if (seedText[i] == '1') {
+            if (seed.weight < CPK_ANCHOR_MAX_WEIGHT) seed.pos[seed.weight] = (uint8_t)i;
+            seed.weight++;
+        } else if (seedText[i] != '0') {
+            seed.weight = 0;
+            break;
+        }
+    }
+    if (seed.span < 1 || seed.span > 31 || seed.weight < 1 || seed.weight > CPK_ANCHOR_MAX_WEIGHT || prm->maxSeedOccurrences < 1 ||
+        prm->maxHsps < 1 || prm->xDrop < 0 || trim < 0) {
+        cpk_set_error("anchor parameters: the seed is 1..31 characters of 0 / 1 with 1..%d ones; maxSeedOccurrences, maxHsps >= 1; "
+                      "xDrop, trim >= 0", CPK_ANCHOR_MAX_WEIGHT);
+        return CPECAN_EINVAL;
+    }
+    CPK_ON_DEVICE(c->device);
+    PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
+    hipStream_t st = sc.stream;
+    int64_t nKeys = 0;
+    int maxCap = 1;
+    for (int64_t i = 0; i < n; i++) {
+        CpkAnchorProblem &p = probs[i];
+        if (p.lX < 0 || p.lY < 0 || p.xOff < 0 || p.yOff < 0 || p.xOff + p.lX > c->nSym || p.yOff + p.lY > c->nSym ||
+            p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * prm->maxSeedOccurrences > (1 << 30)) {
+            cpk_set_error("anchor problem %lld: sequences outside the buffer, longer than 2^24, or too many seed occurrences allowed",
+                          (long long)i);
+            return CPECAN_EINVAL;
+        }
+        p.capX = anchor_pow2(std::max(p.lX - seed.span + 1, 1));
+        p.capY = anchor_pow2(std::max(p.lY - seed.span + 1, 1));
+        p.keyXOff = nKeys;
+        p.keyYOff = nKeys + p.capX;
+        nKeys += (int64_t)p.capX + p.capY;
+        maxCap = std::max(maxCap, std::max(p.capX, p.capY));
+        p.hits = p.hsps = p.chained = p.nRuns = p.capped = p.pad = 0;
+        p.columns = 0;
+        p.hspCap = 0;
+        p.hspOff = 0;
+    }
+    CpkAnchorProblem *dProbs = nullptr;
+    unsigned long long *dKeys = nullptr;
+    if (int rc = sc.alloc(&dProbs, (size_t)n)) return rc;
+    if (int rc = sc.alloc(&dKeys, (size_t)nKeys)) return rc;
+    const unsigned chunks = (unsigned)std::min(64, (maxCap + 1023) / 1024);
+    float part = 0.f;
+    HIP_TRY(hipMemcpyAsync(dProbs, probs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(c->evA, st));
+    hipLaunchKernelGGL(cpk_anchor_words, dim3((unsigned)n, chunks, 2), dim3(256), 0, st, dProbs, c->dSym, seed, dKeys);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpk_anchor_sort_keys, dim3((unsigned)n, 2), dim3(maxCap >= 4096 ? 1024 : 256), 0, st, dProbs, dKeys);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpk_anchor_hits<false>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
+                       (int4 *)nullptr, (int32_t *)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evB, st));
+    HIP_TRY(hipMemcpyAsync(probs, dProbs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&part, c->evA, c->evB));
+    *ms += part;
+    int64_t nSlots = 0;
+    for (int64_t i = 0; i < n; i++) {
+        probs[i].hspCap = anchor_pow2(std::max(probs[i].hits, 1));
+        probs[i].hspOff = nSlots;
+        nSlots += probs[i].hspCap;
+    }
+    int4 *dHsps = nullptr;
+    int32_t *dCount = nullptr, *dBest = nullptr, *dPred = nullptr, *dRuns = nullptr;
+    if (int rc = sc.alloc(&dHsps, (size_t)nSlots)) return rc;
+    if (int rc = sc.alloc(&dCount, (size_t)n)) return rc;
+    if (int rc = sc.alloc(&dBest, (size_t)nSlots)) return rc;
+    if (int rc = sc.alloc(&dPred, (size_t)nSlots)) return rc;
+    if (int rc = sc.alloc(&dRuns, (size_t)nSlots * 3)) return rc;
+    HIP_TRY(hipMemcpyAsync(dProbs, probs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dCount, 0, sizeof(int32_t) * (size_t)n, st));
+    HIP_TRY(hipEventRecord(c->evA, st));
+    hipLaunchKernelGGL(cpk_anchor_hits<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
+                       dHsps, dCount);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cpk_anchor_chain, dim3((unsigned)n), dim3(256), 0, st, dProbs, dHsps, dCount, dBest, dPred, dRuns,
+                       prm->maxHsps, trim);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evB, st));
+    int32_t *runs = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)nSlots);
+    if (!runs) {
+        cpk_set_error("out of memory");
+        return CPECAN_ENOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(probs, dProbs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(runs, dRuns, sizeof(int32_t) * 3 * (size_t)nSlots, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&part, c->evA, c->evB);
+    if (e != hipSuccess) {
+        free(runs);
+        HIP_TRY(e);
+    }
+    *ms += part;
+    *runsOut = runs;
+    return CPECAN_OK;
+}

@@ -1,0 +1,296 @@
+// cpk_anchor.inl -- the anchor finder (include/cpecan_hip.h: cpecan_find_anchor_runs_many).
+// Integer work over a batch of sequence pairs: spaced-seed words, a k-mer join on sorted (word, position) keys, ungapped
+// x-drop extension with one hit per lane, and per-problem sort / duplicate removal / chaining with one workgroup per
+// problem.  Every result is defined on sets and sorted orders: the atomics below only hand out slots of lists that are
+// sorted before anything reads their order.
+//
+// Symbols are held as in stage_symbols (cpk_device_common.inl): two to a byte, low nibble = even index; the code is
+// 0..3 = a c g t, CPK_SYM_N = anything else, and bit 3 marks a lower-case (soft-masked) base.  X and Y strings of all
+// problems share one buffer and are addressed by global symbol index, so a sub-problem of the recursion is an offset
+// and a length, not a copy.
+
+#define CPK_ANCHOR_LOWER 8
+#define CPK_ANCHOR_MAX_WEIGHT 15 /* word < 2^30: a key (word << 32 | position) never equals the all-ones filler */
+#define CPK_ANCHOR_KEY_NONE (~0ull)
+#define CPK_ANCHOR_NO_KEY (-0x7fffffffffffffffLL - 1)
+
+struct CpkAnchorSeed {
+    int32_t span, weight;
+    uint8_t pos[16]; /* offsets of the seed's 1 positions inside the window */
+};
+
+__device__ __forceinline__ int anchor_sym(const uint8_t *sym, int64_t g) { return (sym[g >> 1] >> ((int)(g & 1) * 4)) & 15; }
+
+// raw bytes -> packed symbols; one output byte per thread (the partner of a last odd symbol is N)
+__global__ void __launch_bounds__(256) cpk_anchor_pack(const uint8_t *raw, int64_t n, uint8_t *sym) {
+    const int64_t nOut = (n + 1) >> 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nOut; i += (int64_t)gridDim.x * blockDim.x) {
+        int nib[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int64_t g = 2 * i + h;
+            const int c = g < n ? raw[g] : 'N';
+            const int u = c & ~32;
+            const int code = u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : CPK_SYM_N;
+            nib[h] = code | ((code != CPK_SYM_N && (c & 32)) ? CPK_ANCHOR_LOWER : 0);
+        }
+        sym[i] = (uint8_t)(nib[0] | (nib[1] << 4));
+    }
+}
+
+// Step 1a: one key per window slot of X (blockIdx.z == 0) or Y (1): word << 32 | position, or the filler for a window
+// that is skipped (N or, with softMask, a lower-case base at a 1 position) and for the slots that pad to a power of two.
+__global__ void __launch_bounds__(256) cpk_anchor_words(const CpkAnchorProblem *probs, const uint8_t *sym, CpkAnchorSeed seed,
+                                                        unsigned long long *keys) {
+    const CpkAnchorProblem pr = probs[blockIdx.x];
+    const int side = blockIdx.z;
+    const int cap = side ? pr.capY : pr.capX, l = side ? pr.lY : pr.lX;
+    const int64_t off = side ? pr.yOff : pr.xOff;
+    unsigned long long *out = keys + (side ? pr.keyYOff : pr.keyXOff);
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < cap; i += gridDim.y * blockDim.x) {
+        unsigned long long key = CPK_ANCHOR_KEY_NONE;
+        if (i + seed.span <= l) {
+            unsigned word = 0;
+            bool ok = true;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                if (k < seed.weight) {
+                    const int s = anchor_sym(sym, off + i + seed.pos[k]);
+                    if ((s & 7) > 3 || (pr.softMask && (s & CPK_ANCHOR_LOWER))) ok = false;
+                    word = (word << 2) | (unsigned)(s & 3);
+                }
+            }
+            if (ok) key = ((unsigned long long)word << 32) | (unsigned)i;
+        }
+        out[i] = key;
+    }
+}
+
+// Bitonic sort of n (a power of two) elements in global memory by one workgroup.
+template <typename T, typename Less>
+__device__ void anchor_bitonic(T *a, int n, Less less) {
+    __syncthreads();
+    for (int k = 2; k <= n; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), m = i | j;
+                const T x = a[i], y = a[m];
+                const bool sw = (i & k) == 0 ? less(y, x) : less(x, y);
+                if (sw) {
+                    a[i] = y;
+                    a[m] = x;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+struct AnchorKeyLess {
+    __device__ bool operator()(unsigned long long a, unsigned long long b) const { return a < b; }
+};
+
+// Step 1b: the keys of one side of one problem in (word, position) order, fillers last.
+__global__ void __launch_bounds__(1024) cpk_anchor_sort_keys(const CpkAnchorProblem *probs, unsigned long long *keys) {
+    const CpkAnchorProblem pr = probs[blockIdx.x];
+    const int side = blockIdx.y;
+    anchor_bitonic(keys + (side ? pr.keyYOff : pr.keyXOff), side ? pr.capY : pr.capX, AnchorKeyLess());
+}
+
+// first index in the sorted keys a[0..n) whose word is >= w
+__device__ __forceinline__ int anchor_lower_bound(const unsigned long long *a, int n, unsigned long long w) {
+    int lo = 0, hi = n;
+    const unsigned long long key = w << 32;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int anchor_score(const int *sc, int a, int b) { return sc[(a & 7) * 5 + (b & 7)]; }
+
+// Steps 1c and 2.  One lane per Y window: the X windows with its word (none unless the word occurs at most
+// maxSeedOccurrences times on both sides) are its hits.  EXTEND == false counts them; EXTEND == true extends each to an
+// HSP and appends those that reach hspThreshold to the problem's list (slot order is arbitrary: cpk_anchor_chain sorts).
+template <bool EXTEND>
+__global__ void __launch_bounds__(256) cpk_anchor_hits(CpkAnchorProblem *probs, const uint8_t *sym, const unsigned long long *keys,
+                                                       CpkAnchorParams prm, int span, int4 *hsps, int32_t *nHsp) {
+    __shared__ int sc[25];
+    if (threadIdx.x < 25) sc[threadIdx.x] = prm.scores[threadIdx.x];
+    __syncthreads();
+    const int p = blockIdx.x;
+    const CpkAnchorProblem pr = probs[p];
+    const unsigned long long *kx = keys + pr.keyXOff, *ky = keys + pr.keyYOff;
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < pr.capY; i += gridDim.y * blockDim.x) {
+        const unsigned long long key = ky[i];
+        if (key == CPK_ANCHOR_KEY_NONE) continue;
+        const unsigned long long w = key >> 32;
+        const int y0 = anchor_lower_bound(ky, pr.capY, w), y1 = anchor_lower_bound(ky, pr.capY, w + 1);
+        if (y1 - y0 > prm.maxSeedOccurrences) continue;
+        const int x0 = anchor_lower_bound(kx, pr.capX, w), x1 = anchor_lower_bound(kx, pr.capX, w + 1);
+        if (x1 == x0 || x1 - x0 > prm.maxSeedOccurrences) continue;
+        if (!EXTEND) {
+            atomicAdd(&probs[p].hits, x1 - x0);
+            continue;
+        }
+        const int wy = (int)(unsigned)key;
+        for (int h = x0; h < x1; h++) {
+            const int wx = (int)(unsigned)kx[h];
+            int score = 0;
+            for (int k = 0; k < span; k++) score += anchor_score(sc, anchor_sym(sym, pr.xOff + wx + k), anchor_sym(sym, pr.yOff + wy + k));
+            int lenR = 0, lenL = 0;
+            {
+                const int room = min(pr.lX - (wx + span), pr.lY - (wy + span));
+                const int64_t gx = pr.xOff + wx + span, gy = pr.yOff + wy + span;
+                int sum = 0, best = 0;
+                for (int k = 0; k < room; k++) {
+                    sum += anchor_score(sc, anchor_sym(sym, gx + k), anchor_sym(sym, gy + k));
+                    if (sum > best) {
+                        best = sum;
+                        lenR = k + 1;
+                    }
+                    if (sum < best - prm.xDrop) break;
+                }
+                score += best;
+            }
+            {
+                const int room = min(wx, wy);
+                const int64_t gx = pr.xOff + wx - 1, gy = pr.yOff + wy - 1;
+                int sum = 0, best = 0;
+                for (int k = 0; k < room; k++) {
+                    sum += anchor_score(sc, anchor_sym(sym, gx - k), anchor_sym(sym, gy - k));
+                    if (sum > best) {
+                        best = sum;
+                        lenL = k + 1;
+                    }
+                    if (sum < best - prm.xDrop) break;
+                }
+                score += best;
+            }
+            if (score >= prm.hspThreshold) {
+                const int slot = atomicAdd(&nHsp[p], 1);
+                if (slot < pr.hspCap) hsps[pr.hspOff + slot] = make_int4(wx - lenL, wy - lenL, span + lenL + lenR, score);
+            }
+        }
+    }
+}
+
+#define CPK_ANCHOR_HSP_NONE make_int4(0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000)
+struct AnchorHspByPlace {  // (x, y, length); fillers last
+    __device__ bool operator()(const int4 &a, const int4 &b) const {
+        if (a.x != b.x) return a.x < b.x;
+        if (a.y != b.y) return a.y < b.y;
+        return a.z < b.z;
+    }
+};
+struct AnchorHspByScore {  // (score descending, x, y, length); fillers last
+    __device__ bool operator()(const int4 &a, const int4 &b) const {
+        if (a.w != b.w) return a.w > b.w;
+        return AnchorHspByPlace()(a, b);
+    }
+};
+
+// the largest key of the workgroup (every thread gets it); red: 16 slots of LDS
+__device__ __forceinline__ long long anchor_block_max(long long v, long long *red) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long u = __shfl_xor(v, o);
+        v = u > v ? u : v;
+    }
+    __syncthreads();  // red may still be read from the previous call
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long r = red[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); w++) r = red[w] > r ? red[w] : r;
+    return r;
+}
+
+// Steps 2 (duplicates) to 5, one workgroup per problem.  hsps: the problem's hspCap slots, of which the first nHsp[p] were
+// filled by cpk_anchor_hits; best / pred: hspCap ints each; runs: hspCap triples (x, y, length), relative to the problem.
+__global__ void __launch_bounds__(256) cpk_anchor_chain(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp, int32_t *bestAll,
+                                                        int32_t *predAll, int32_t *runsAll, int maxHsps, int trim) {
+    __shared__ long long red[16];
+    __shared__ int shCount;
+    const int p = blockIdx.x, tid = threadIdx.x, nT = blockDim.x;
+    const CpkAnchorProblem pr = probs[p];
+    int4 *hsp = hspsAll + pr.hspOff;
+    int32_t *best = bestAll + pr.hspOff, *pred = predAll + pr.hspOff, *runs = runsAll + 3 * pr.hspOff;
+    const int cap = pr.hspCap;
+    int n = min(nHsp[p], cap);
+    for (int i = n + tid; i < cap; i += nT) hsp[i] = CPK_ANCHOR_HSP_NONE;
+    if (tid == 0) shCount = 0;
+    anchor_bitonic(hsp, cap, AnchorHspByPlace());
+    // exact duplicates of (x, y, length) follow each other; the score is a function of the three
+    for (int i = tid; i < n; i += nT) {
+        bool dup = false;
+        if (i > 0) {
+            const int4 a = hsp[i - 1], b = hsp[i];
+            dup = a.x == b.x && a.y == b.y && a.z == b.z;
+        }
+        pred[i] = dup;
+        if (!dup) atomicAdd(&shCount, 1);
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += nT)
+        if (pred[i]) hsp[i] = CPK_ANCHOR_HSP_NONE;
+    __syncthreads();
+    const int nUnique = shCount;
+    if (nUnique != n) anchor_bitonic(hsp, cap, AnchorHspByPlace());
+    n = nUnique;
+    int capped = 0;
+    if (n > maxHsps) {  // step 3
+        capped = 1;
+        anchor_bitonic(hsp, cap, AnchorHspByScore());
+        for (int i = maxHsps + tid; i < n; i += nT) hsp[i] = CPK_ANCHOR_HSP_NONE;
+        n = maxHsps;
+        anchor_bitonic(hsp, cap, AnchorHspByPlace());
+    }
+    __syncthreads();
+    // step 4: predecessors of i have a smaller x, so they come before i
+    for (int i = 0; i < n; i++) {
+        const int4 me = hsp[i];
+        long long key = CPK_ANCHOR_NO_KEY;
+        for (int j = tid; j < i; j += nT) {
+            const int4 o = hsp[j];
+            if (o.x + o.z <= me.x && o.y + o.z <= me.y) {
+                const long long k = (long long)best[j] * 4294967296LL + (unsigned)~j;  // largest best, then smallest j
+                key = k > key ? k : key;
+            }
+        }
+        key = anchor_block_max(key, red);
+        if (tid == 0) {
+            best[i] = me.w + (key == CPK_ANCHOR_NO_KEY ? 0 : (int)(key >> 32));
+            pred[i] = key == CPK_ANCHOR_NO_KEY ? -1 : (int)~(unsigned)key;
+        }
+        __syncthreads();
+    }
+    long long endKey = CPK_ANCHOR_NO_KEY;
+    for (int i = tid; i < n; i += nT) {
+        const long long k = (long long)best[i] * 4294967296LL + (unsigned)~i;
+        endKey = k > endKey ? k : endKey;
+    }
+    endKey = anchor_block_max(endKey, red);
+    if (tid == 0) {
+        // step 5: walk back from the end, then write the trimmed runs in increasing order (best[] is free: it holds the walk)
+        int m = 0;
+        for (int i = n > 0 ? (int)~(unsigned)endKey : -1; i >= 0; i = pred[i]) best[m++] = i;
+        int nRuns = 0;
+        long long columns = 0;
+        for (int k = m - 1; k >= 0; k--) {
+            const int4 h = hsp[best[k]];
+            const int len = h.z - 2 * trim;
+            if (len > 0) {
+                runs[3 * nRuns] = h.x + trim;
+                runs[3 * nRuns + 1] = h.y + trim;
+                runs[3 * nRuns + 2] = len;
+                nRuns++;
+                columns += len;
+            }
+        }
+        probs[p].hsps = nUnique;
+        probs[p].chained = m;
+        probs[p].nRuns = nRuns;
+        probs[p].columns = columns;
+        probs[p].capped = capped;
+    }
+}

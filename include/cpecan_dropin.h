@@ -14,8 +14,9 @@
  * minimal implementation of exactly the container calls the API needs, exported as WEAK symbols so that a real
  * sonLib linked into the same program takes precedence.
  *
- * Not provided: the lastz path of getAlignedPairs / getExpectations (beyond anchorMatrixBiggerThanThis the reference shells
- * out to lastz, impl/pairwiseAligner.c:1032-1042).  The primitives the reference's unit tests link (inc/pairwiseAligner.h:
+ * lastz: beyond anchorMatrixBiggerThanThis the reference shells out to lastz for anchors (impl/pairwiseAligner.c:1032-1042).
+ * This library has an anchor finder of its own in that place (getBlastPairs below); lastz itself is not provided and its
+ * output is not reproduced.  The primitives the reference's unit tests link (inc/pairwiseAligner.h:
  * 186-237: DpDiagonal, DpMatrix, cell_calculateForward / Backward, cell_dotProduct[2], diagonalCalculationForward /
  * Backward / TotalProbability, the per-diagonal emitters on DpMatrix rows) ARE provided: the containers are host memory
  * with the reference's semantics, their DP arithmetic runs on the GPU (cpecan_ref_cells, one lane, the reference's order
@@ -174,10 +175,17 @@ void getExpectationsUsingAnchors(StateMachine *sM, Hmm *hmmExpectations, const c
                                  bool alignmentHasRaggedRightEnd);
 double computeForwardProbability(char *seqX, char *seqY, stList *anchorPairs, PairwiseAlignmentParameters *p,
                                  StateMachine *sM, bool alignmentHasRaggedLeftEnd, bool alignmentHasRaggedRightEnd);
-/* The entry points that find their own anchors (impl/pairwiseAligner.c:1481-1513).  The reference anchors with lastz only
- * when lX * lY > p->anchorMatrixBiggerThanThis (:1164); up to that size these are the functions above with no anchors,
- * and that is what is provided.  Beyond it they abort: the lastz anchoring (:959-1196) is not part of this library --
- * pass anchors to the *UsingAnchors functions. */
+/* The anchors the reference gets from lastz (impl/pairwiseAligner.c:1005-1080, :1162-1196), found by this library's own
+ * anchor finder on the GPU (cpecan_find_anchor_runs*): lists of (x, y, diagonalExpansion) tuples,
+ * strictly increasing in x and y.  The finder is not lastz and its anchors are not lastz's; trim, expansion, the size
+ * limit, the one level of recursion and the repeat-mask switch are the reference's. */
+stList *getBlastPairs(const char *sX, const char *sY, int64_t lX, int64_t lY, int64_t trim, int64_t diagonalExpansion,
+                      bool repeatMask);
+stList *getBlastPairsForPairwiseAlignmentParameters(const char *sX, const char *sY, const int64_t lX, const int64_t lY,
+                                                    PairwiseAlignmentParameters *p);
+/* The entry points that find their own anchors (impl/pairwiseAligner.c:1481-1513): with lX * lY up to
+ * p->anchorMatrixBiggerThanThis (:1164) the functions above with no anchors, beyond it with the anchors of
+ * getBlastPairsForPairwiseAlignmentParameters. */
 stList *getAlignedPairs(StateMachine *sM, const char *sX, const char *sY, PairwiseAlignmentParameters *p,
                         bool alignmentHasRaggedLeftEnd, bool alignmentHasRaggedRightEnd);
 void getAlignedPairsWithIndels(StateMachine *sM, const char *sX, const char *sY, PairwiseAlignmentParameters *p,

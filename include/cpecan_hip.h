@@ -146,6 +146,65 @@ int64_t cpecan_anchor_runs_from_alignment(const int64_t *ops, int64_t nOps, int6
  * larger in both coordinates.  pairs: n triples sorted by x, then y; out: room for n triples.  Returns the number kept. */
 int64_t cpecan_filter_to_remove_overlap(const int64_t *pairs, int64_t n, int64_t *out);
 
+/* ---- the anchor finder: anchors from the two sequences alone ----
+ * Fills the role lastz has in the reference (getBlastPairsForPairwiseAlignmentParameters, pairwiseAligner.c:1005-1196)
+ * with a finder of this library's own, defined in DESIGN.md section 7; it is NOT lastz and does not reproduce its output.
+ * Per problem: (1) spaced-seed words of X and Y; words that occur more than maxSeedOccurrences times on either side are
+ * dropped; a hit is a pair of windows with equal words; (2) ungapped x-drop extension of every hit to an HSP, kept from
+ * hspThreshold up, exact duplicates dropped; (3) at most maxHsps HSPs, the best by (score descending, x, y, length);
+ * (4) the heaviest chain of HSPs that follow each other without overlap in X or Y, no gap penalty; (5) every chained HSP
+ * minus `trim` columns at either end is an anchor run; (6) one level of recursion into every gap between consecutive
+ * anchors whose matrix is larger than anchorMatrixBiggerThanThis (:1175-1191), soft masking on at the top level and in a
+ * gap larger than repeatMaskMatrixBiggerThanThis.  All of it runs on the GPU; the result is a pure function of the
+ * inputs (tests/anchor_model.py states it in Python and the GPU tests compare integer for integer). */
+typedef struct cpecan_anchor_params {
+    char seed[32];              /* '1' = position compared, '0' = ignored; at most 31 long with at most 15 ones */
+    int32_t maxSeedOccurrences; /* a word that occurs more often in X or in Y seeds nothing */
+    int32_t scores[25];         /* substitution scores [a*5+b], symbols a c g t n */
+    int32_t xDrop;
+    int32_t hspThreshold;
+    int32_t maxHsps;            /* per problem; cpecan_anchor_stats.capped tells when it cut */
+    int32_t reserved;
+} cpecan_anchor_params;
+/* lastz's defaults where it has them: seed 1110100110010101111 (12 of 19, no transitions), HOXD70 with -100 for N,
+ * xDrop 910, hspThreshold 800 (--hspthresh=800, :1034); maxSeedOccurrences 1 and maxHsps 4096 are this library's. */
+int cpecan_anchor_params_default(cpecan_anchor_params *p);
+
+typedef struct cpecan_anchor_problem {
+    const char *sX;
+    int64_t lX;
+    const char *sY;
+    int64_t lY;
+} cpecan_anchor_problem;
+
+/* Counts are sums over the top level and the gaps of the recursion. */
+typedef struct cpecan_anchor_stats {
+    int64_t hits, hsps, chained; /* seed hits; HSPs kept (before the cap); HSPs on the chains */
+    int64_t runs, anchorColumns; /* the result: runs and the anchors they stand for */
+    int64_t subProblems;         /* gaps the recursion searched */
+    int64_t largestGapTop;       /* largest gap matrix between top-level anchors (lX * lY when there are none) */
+    int64_t largestGap;          /* the same after the recursion */
+    int32_t capped;              /* maxHsps cut an HSP list somewhere */
+    int32_t reserved;
+    double kernelMs;             /* HIP-event time of the anchor kernels of the whole CALL (the same in every problem) */
+} cpecan_anchor_stats;
+
+/* Anchors of n problems in one batch on `device`.  runs[i] receives a malloc'd array (cpecan_free) of nRuns[i] quadruples
+ * (x, y, length, expansion), strictly increasing, ready for cpecan_batch_add_many_runs; stats (n entries) may be NULL.
+ * A problem with lX * lY <= anchorMatrixBiggerThanThis gets no anchors (:1164).  params NULL = the defaults. */
+int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                 int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                                 const cpecan_anchor_params *params, int device, int64_t **runs, int64_t *nRuns,
+                                 cpecan_anchor_stats *stats);
+/* One problem on the caller's current device. */
+int cpecan_find_anchor_runs(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
+                            int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                            const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns, cpecan_anchor_stats *stats);
+/* Steps 1-5 alone on the caller's current device, whatever the size and without the recursion: the counterpart of ONE
+ * lastz call (getBlastPairs, :1005, whose repeatMask flag is softMask here). */
+int cpecan_find_anchor_runs_once(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
+                                 int softMask, const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns);
+
 /* The reference's cell-level primitives (inc/pairwiseAligner.h:186-237: cell_calculateForward / Backward,
  * diagonalCalculationForward / Backward, the posterior of :683-685), which its unit tests link, evaluated on the caller's
  * current device: `n` operations applied in order to the cells held in `cells` (nDoubles doubles, changed in place).
