@@ -73,11 +73,10 @@ CPK_HD int cpk_band_init_runs(CpkBandIter *it, const int32_t *runs, int64_t nRun
     return rc;
 }
 
-/* The next anchor's own diagonal has been emitted: the iterator moves on to the interval behind it.  Returns 0, or -1
- * for anchors that do not describe a valid band. */
-CPK_HD int cpk_band_advance(CpkBandIter *it) {
-    it->pX = it->qX;
-    it->pY = it->qY;
+/* The previous anchor stands in (pX, pY): fetches the next one into (qX, qY) -- the virtual last anchor (lX, lY) when
+ * none is left -- and sets the rectangle of the interval between the two.  Returns 0, or -1 for anchors that do not
+ * describe a valid band. */
+CPK_HD int cpk_band_fetch(CpkBandIter *it) {
     it->qX = it->lX;
     it->qY = it->lY;
     if (it->used < it->n) {
@@ -109,6 +108,14 @@ CPK_HD int cpk_band_advance(CpkBandIter *it) {
     return 0;
 }
 
+/* The next anchor's own diagonal has been emitted: the iterator moves on to the interval behind it.  Returns 0, or -1
+ * for anchors that do not describe a valid band. */
+CPK_HD int cpk_band_advance(CpkBandIter *it) {
+    it->pX = it->qX;
+    it->pY = it->qY;
+    return cpk_band_fetch(it);
+}
+
 /* Inside a run of diagonal-neighbour anchors -- the interval (X, Y) -> (X + 1, Y + 1), its rectangle clear of the matrix
  * edges -- the band holds exactly two diagonals: x-y in [X-Y-E-1, X-Y+E+1] (E + 2 cells), then [X-Y-E, X-Y+E] (E + 1
  * cells); cpk_band_next gives the same (planning and the device's table builder skip its arithmetic there).  True when
@@ -129,6 +136,48 @@ CPK_HD int cpk_band_next(CpkBandIter *it, int64_t d, int64_t *xmyL, int64_t *xmy
     *xmyR = 2 * b - d;
     if (it->qSum != d) return 0;
     return cpk_band_advance(it); /* the anchor's own diagonal has been emitted: move on to the next interval */
+}
+
+/* With cpk_band_in_run(it, d) true: the iterator stands in front of the interval between anchors j = used - 2 and j + 1
+ * of a run.  How many consecutive intervals from that one on join diagonal neighbours (anchors j .. j + s) with their
+ * rectangles clear of the matrix edges, at most `limit` (0 for limit <= 0).  Runs form: to the end of anchor j + 1's run
+ * -- a run that happens to continue in the next one starts a stretch of its own there. */
+CPK_HD int64_t cpk_band_run_ahead(const CpkBandIter *it, int64_t limit) {
+    const int64_t h = it->e / 2, roomX = it->lX - h - it->pX, roomY = it->lY - h - it->pY; /* the last interval's rectangle */
+    int64_t s = 0;
+    limit = limit < roomX ? limit : roomX;
+    limit = limit < roomY ? limit : roomY;
+    if (it->runs) {
+        s = (int64_t)it->runs[4 * it->qRi + 2] - it->qRo; /* anchor j + 1 is anchor qRo of run qRi */
+        s = s < limit ? s : limit;
+        return s < 0 ? 0 : s;
+    }
+    const cpk_anchor_t *a = it->anchors + (int64_t)it->stride * (it->used - 2);
+    while (s < limit && it->used - 1 + s < it->n && a[it->stride] == a[0] + 1 && a[it->stride + 1] == a[1] + 1) {
+        s++;
+        a += it->stride;
+    }
+    return s;
+}
+
+/* x - y of the anchors of the run the iterator stands in: the diagonals of its intervals are centred there. */
+CPK_HD int64_t cpk_band_run_xmy(const CpkBandIter *it) { return it->pX - it->pY; }
+
+/* Skips s >= 1 intervals of the run, s <= cpk_band_run_ahead(it, s):
+ * leaves the iterator exactly as the 2 s calls of cpk_band_next for their diagonals would, and returns -1 where they would. */
+CPK_HD int cpk_band_skip_run(CpkBandIter *it, int64_t s) {
+    it->pX = it->qX + (s - 1); /* anchor j + s: anchor j + 1 moved s - 1 steps along the run */
+    it->pY = it->qY + (s - 1);
+    it->used += s - 1;
+    if (it->runs) { /* the cursor goes to the anchor behind it */
+        it->ri = it->qRi;
+        it->ro = it->qRo + (int32_t)s;
+        if (it->ro >= it->runs[4 * it->ri + 2]) {
+            it->ro = 0;
+            it->ri++;
+        }
+    }
+    return cpk_band_fetch(it);
 }
 
 #endif

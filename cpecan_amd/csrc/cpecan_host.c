@@ -1111,6 +1111,535 @@ int cpk_host_threads(void) {
     return n < 1 ? 1 : n;
 }
 
+/* What one upload's planning holds until the batch takes it over (host_plan_commit) or it is dropped (host_plan_free). */
+typedef struct {
+    int64_t *diagStart, *segStart; /* per region: its first diagonal of the device's table and its first segment slot */
+    CostKey *keys;                 /* per region; in device order once sorted */
+    RegionPlan *plan;
+    CpkSegment *segs;
+    int64_t nSegs; /* slots: every region gets room for an upper bound on its segment count */
+    int64_t totalDiags, totalCells;
+    CpkRegion *devRegions;
+    int64_t *devToHost;
+    int64_t outTriples, dbgCells, dbgDiags; /* at least 1 each */
+    int dynamic;    /* per-anchor expansions are in force */
+    int fastWalk;   /* CPECAN_FAST_WALK=0: plan_region walks every diagonal */
+    int packedKnob; /* CPECAN_PACKED: -1 unset; 0 = one wave per region for every region (diagnostic); 2 = pack however few */
+} HostPlan;
+
+static void host_plan_free(HostPlan *hp) {
+    free(hp->diagStart);
+    free(hp->segStart);
+    free(hp->keys);
+    free(hp->plan);
+    cpk_host_free(hp->segs);
+    cpk_host_free(hp->devRegions);
+    cpk_host_free(hp->devToHost);
+    memset(hp, 0, sizeof *hp);
+}
+
+/* The one point at which the batch becomes the owner of the plan's device-order arrays. */
+static void host_plan_commit(cpecan_batch *b, HostPlan *hp, const CpkGeometry *geo) {
+    b->geo = *geo;
+    b->devRegions = hp->devRegions;
+    b->devToHost = hp->devToHost;
+    b->segs = hp->segs;
+    b->nSegs = hp->nSegs;
+    b->nDiags = hp->totalDiags;
+    b->outTriples = hp->outTriples;
+    b->dbgCells = hp->dbgCells;
+    b->dbgDiags = hp->dbgDiags;
+    hp->devRegions = NULL;
+    hp->devToHost = NULL;
+    hp->segs = NULL;
+}
+
+/* The knobs, read once per upload, and the per-region diagonal and segment slots. */
+static int host_plan_init(const cpecan_batch *b, HostPlan *hp) {
+    const cpecan_params *p = &b->params;
+    const char *fwEnv = getenv("CPECAN_FAST_WALK"), *pkEnv = getenv("CPECAN_PACKED");
+    memset(hp, 0, sizeof *hp);
+    hp->dynamic = b->emit == CPECAN_EMIT_FORWARD ? 0 : p->dynamicAnchorExpansion; /* :894: forward uses the static band */
+    hp->fastWalk = !(fwEnv && atoi(fwEnv) == 0);
+    hp->packedKnob = pkEnv ? atoi(pkEnv) : -1;
+    hp->diagStart = malloc(sizeof(int64_t) * (size_t)b->nRegions);
+    hp->segStart = malloc(sizeof(int64_t) * (size_t)b->nRegions);
+    hp->keys = malloc(sizeof(CostKey) * (size_t)b->nRegions);
+    hp->plan = calloc((size_t)b->nRegions, sizeof(RegionPlan));
+    if (!hp->diagStart || !hp->segStart || !hp->keys || !hp->plan) return CPECAN_ENOMEM;
+    for (int64_t i = 0; i < b->nRegions; i++) {
+        const int64_t N = b->regions[i].lX + b->regions[i].lY;
+        hp->diagStart[i] = hp->totalDiags;
+        hp->totalDiags += N + 1;
+        hp->segStart[i] = hp->nSegs;
+        /* consecutive traceback points are at least minDiagsBetweenTraceBack - (traceBackDiagonals + 1) >= 1 apart */
+        hp->nSegs += N / (p->minDiagsBetweenTraceBack - p->traceBackDiagonals - 1) + 2;
+    }
+    hp->segs = host_zalloc((size_t)hp->nSegs, sizeof(CpkSegment));
+    return hp->segs ? CPECAN_OK : CPECAN_ENOMEM;
+}
+
+/* One region's band walk and traceback schedule (pairwiseAligner.c:791-810): fills plan[i], the region's segments and its
+ * cell count.  hist: 4 K cell offsets, widths and first coordinates of the last K = traceBackDiagonals + 3 diagonals --
+ * the schedule looks that far back.  Returns nonzero for anchors that do not define a valid band. */
+static int plan_region(cpecan_batch *b, HostPlan *hp, int64_t i, int64_t *hist) {
+    const cpecan_params *p = &b->params;
+    const int64_t K = p->traceBackDiagonals + 3;
+    int64_t *histOff = hist, *histW = hist + K, *histXlo = hist + 2 * K, *histYlo = hist + 3 * K;
+    HostRegion *r = &b->regions[i];
+    RegionPlan *pl = &hp->plan[i];
+    const int64_t N = r->lX + r->lY;
+    const int dynamic = hp->dynamic;
+    CpkBandIter it;
+    memset(&it, 0, sizeof it);
+    int bad = b->runForm == 1 ? cpk_band_init_runs(&it, b->runs + 4 * r->runOff, r->nRuns, r->nAnchors, r->lX, r->lY, p->diagonalExpansion)
+                              : cpk_band_init(&it, b->anchors + (int64_t)b->anchorStride * r->anchorOff, b->anchorStride, r->nAnchors,
+                                              r->lX, r->lY, p->diagonalExpansion, dynamic);
+    CpkSegment *sg = hp->segs + hp->segStart[i];
+    int64_t cells = 0, tracedBackTo = 0;
+    int64_t offTracedBackTo = 0; /* cells before diagonal tracedBackTo */
+    int64_t offAfter = 0;        /* cells before diagonal tracedBackTo + 1 */
+    int64_t slot = 0; /* d % K without the division: this loop runs once per diagonal of the batch */
+    int64_t maxW = 0;
+    int64_t prevLo = 0, prevHi = 0;
+    int64_t winXlo = 0, winYlo = 0; /* smallest x and y of diagonal tracedBackTo + 1 (symbol windows, RegionPlan::winBytes) */
+    int smooth = !dynamic;
+    const int64_t minBetween = p->minDiagsBetweenTraceBack, narrow = p->diagonalExpansion * 2 + 1;
+    /* Runs of diagonal neighbours among the anchors (realign-style input: one anchor per matching column) are walked
+     * in closed form.  Between two anchors (X, Y) and (X + 1, Y + 1) of a run, away from the matrix edges, the band
+     * holds exactly two diagonals: x-y in [X-Y-E-1, X-Y+E+1] (E + 2 cells) and [X-Y-E, X-Y+E] (E + 1 cells) -- both
+     * "narrow" for E >= 2 (<= 2E + 1) and both edges one x-y step apart from their neighbours'.  So a stretch of s such
+     * intervals adds s (2E + 3) cells and nothing else, unless a traceback point may fall into it or behind it within the
+     * K diagonals whose offsets the schedule looks back at: those diagonals are walked one by one.
+     * (BASELINE config 4: 1.25e8 diagonals at ~14 cycles each were 31 ms of every batch on 16 threads.)  CPECAN_FAST_WALK=0
+     * walks every diagonal (tests compare the two).  The iterator finds the stretch and steps over it (cpk_band_run_ahead,
+     * cpk_band_skip_run); how far a skip may go and what it adds to the plan is decided here. */
+    const int64_t E = p->diagonalExpansion;
+    const int fastOk = hp->fastWalk && !dynamic && E >= 2 && b->anchorStride == 2;  /* (runs are kept for stride 2 only) */
+    for (int64_t d = 0; d <= N && !bad; d++, slot = slot + 1 == K ? 0 : slot + 1) {
+        if (fastOk && cpk_band_in_run(&it, d)) {
+            /* every skipped diagonal stays K + 1 below the next traceback point, and below the region's last two */
+            const int64_t sMax = imin((tracedBackTo + minBetween - (K + 1) - d) / 2, (N - 2 - d) / 2);
+            const int64_t sRun = cpk_band_run_ahead(&it, sMax);
+            if (sRun >= 2) {
+                const int64_t add = sRun * (2 * E + 3);
+                if (cells + add >= (int64_t)1 << 31) {
+                    bad = 1;
+                    break;
+                }
+                const int64_t xmy0 = cpk_band_run_xmy(&it);
+                if (d > 0) { /* the step into the stretch: from the diagonal before to its first one */
+                    const int64_t dl = (xmy0 - E - 1) - prevLo, dh = (xmy0 + E + 1) - prevHi;
+                    smooth &= (dl == 1 || dl == -1) && (dh == 1 || dh == -1);
+                }
+                cells += add;
+                maxW = E + 2 > maxW ? E + 2 : maxW;
+                prevLo = xmy0 - E; /* the stretch's last diagonal: the second one of an interval */
+                prevHi = xmy0 + E;
+                if (cpk_band_skip_run(&it, sRun)) {
+                    bad = 1;
+                    break;
+                }
+                d += 2 * sRun - 1; /* the loop's own step makes it 2 sRun */
+                slot = (slot + 2 * sRun - 1) % K;
+                continue;
+            }
+        }
+        int64_t lo, hi;
+        if (cpk_band_next(&it, d, &lo, &hi)) {
+            bad = 1;
+            break;
+        }
+        const int64_t w = (hi - lo) / 2 + 1;
+        if (cells + w >= (int64_t)1 << 31) {
+            bad = 1;
+            break;
+        }
+        if (d > 0) {
+            const int64_t dl = lo - prevLo, dh = hi - prevHi;
+            smooth &= (dl == 1 || dl == -1) && (dh == 1 || dh == -1);
+        }
+        prevLo = lo;
+        prevHi = hi;
+        histOff[slot] = cells;
+        histW[slot] = w;
+        histXlo[slot] = (d + lo) >> 1;      /* x of the diagonal's first cell */
+        histYlo[slot] = d - ((d + hi) >> 1); /* y of its last cell: the smallest */
+        if (d == 1) {
+            offAfter = cells; /* tracedBackTo == 0 for the first segment */
+            winXlo = histXlo[slot];
+            winYlo = histYlo[slot];
+        }
+        maxW = w > maxW ? w : maxW;
+        cells += w;
+        if (d == 0) continue;
+        const int atEnd = d == N;
+        const int tracebackPoint = d >= tracedBackTo + minBetween && w <= narrow;
+        if (!atEnd && !tracebackPoint) continue;
+        memset(sg, 0, sizeof *sg);
+        sg->tbPrev = (int32_t)tracedBackTo;
+        sg->dTop = (int32_t)d;
+        sg->tbFrom = (int32_t)(d - (atEnd ? 0 : p->traceBackDiagonals + 1));
+        sg->atEnd = atEnd;
+        sg->nRefresh = (int32_t)((sg->tbFrom - (sg->tbPrev + 1)) / CPK_REFRESH_PERIOD + 1);
+        pl->refreshMax = sg->nRefresh > pl->refreshMax ? sg->nRefresh : pl->refreshMax;
+        /* forward diagonals tbPrev..dTop are live during this traceback */
+        pl->liveMax = imax(pl->liveMax, cells - offTracedBackTo);
+        const int64_t tf = sg->tbFrom;
+        const int64_t tfSlot = tf % K; /* once per segment */
+        const int64_t fbCells = histOff[tfSlot] + histW[tfSlot] - offAfter;
+        pl->fbMax = imax(pl->fbMax, fbCells);
+        sg->emitCells = (int32_t)fbCells;
+        {
+            /* the symbols the segment's diagonals tbPrev + 1 .. d touch, the kernel's arithmetic (cpk_sweep.inl,
+             * "Symbol windows"): from the even index at or below the smallest x (y) to one past the largest */
+            const int64_t x0 = winXlo & ~(int64_t)1, y0 = winYlo & ~(int64_t)1;
+            const int64_t x1 = imin(((d + hi) >> 1) + 1, r->lX + 1), y1 = imin(d - ((d + lo) >> 1) + 1, r->lY + 1);
+            pl->winBytes = imax(pl->winBytes, (x1 - x0 + 2) / 2 + (y1 - y0 + 2) / 2);
+        }
+        pl->nSeg++;
+        sg++;
+
+        /* the next segment starts from tbFrom: remember the cell offsets of tbFrom and tbFrom + 1 */
+        tracedBackTo = tf;
+        offTracedBackTo = histOff[tfSlot];
+        offAfter = histOff[tfSlot] + histW[tfSlot];
+        if (tf < d) { /* diagonal tf + 1 has been walked already: within the last K */
+            const int64_t s1 = (tf + 1) % K;
+            winXlo = histXlo[s1];
+            winYlo = histYlo[s1];
+        }
+    }
+    pl->maxW = maxW;
+    pl->smooth = smooth;
+    if (bad) return 1;
+    r->cells = cells;
+    hp->keys[i].cells = N > 0 ? cells : 0;
+    return 0;
+}
+
+/* Planning walks every region's band ONCE as a stream of diagonals (cpecan_band.inl) and keeps per-region sums only:
+ * cell count, widest diagonal, the traceback schedule (pairwiseAligner.c:791-810) and the scratch sizes it implies.
+ * The per-diagonal table the kernels read (16 bytes per diagonal, 640 MB at 10 000 pairs x 2 kb) is built on the
+ * device from the anchors by the same iterator (cpk_device_upload).  Regions are independent: OpenMP.  Of the regions
+ * whose band is bad the lowest index is reported, whichever thread met it first. */
+static int plan_regions(cpecan_batch *b, HostPlan *hp) {
+    const size_t K = (size_t)b->params.traceBackDiagonals + 3;
+    int rc = CPECAN_OK;
+    int64_t badRegion = -1;
+#pragma omp parallel num_threads(cpk_host_threads())
+    {
+        int64_t *hist = malloc(sizeof(int64_t) * K * 4);
+        if (!hist) {
+#pragma omp critical(cpk_plan)
+            rc = CPECAN_ENOMEM;
+        }
+#pragma omp for schedule(dynamic, 16)
+        for (int64_t i = 0; i < b->nRegions; i++) {
+            hp->keys[i].cells = 0;
+            hp->keys[i].index = i;
+            if (!hist || !plan_region(b, hp, i, hist)) continue;
+#pragma omp critical(cpk_plan)
+            {
+                rc = CPECAN_EINVAL;
+                if (badRegion < 0 || i < badRegion) badRegion = i;
+            }
+        }
+        free(hist);
+    }
+    if (badRegion >= 0)
+        cpk_set_error("region %lld of problem %lld: anchors do not define a valid band (or the band exceeds 2^31 cells)",
+                      (long long)badRegion, (long long)b->regions[badRegion].problem);
+    return rc;
+}
+
+/* Narrow regions (no diagonal wider than 32 cells: realign-style bands) are packed several to a wave by their own
+ * kernel; they come first in the device order.  Within each class: longest first (the work queues are LPT). */
+static void classify_regions(const cpecan_batch *b, HostPlan *hp) {
+    const int S = is_five(b->model.type) ? 5 : 3;
+    CostKey *keys = hp->keys;
+    /* (bands with per-anchor expansions run the packed kernel's DYN variant: their edges may move backwards) */
+    const int enabled = (b->emit == CPECAN_EMIT_MATCH || b->emit == CPECAN_EMIT_INDEL || b->emit == CPECAN_EMIT_EXPECT) && !b->debug &&
+                        hp->packedKnob != 0;
+    /* a launch is not worth fewer regions (CPECAN_PACKED=2: always, for tests).  The indel emitter's packed form pays a
+     * pass of its own over every emitted cell: measured on realign-style batches it ties with one wave per region at
+     * 10 000 alignments (32.1 against 30.5 ms) and wins 2.4x at 50 000 (61 against 148 ms) -- from ~12 000 regions of
+     * a class, i.e. once a wave has half a dozen rounds to go (profiles/r04_packed_indel_emitter.txt) */
+    const int64_t minCount = hp->packedKnob >= 2 ? 1 : (b->emit == CPECAN_EMIT_INDEL ? 12000 : 64);
+    int64_t perClass[4] = {0, 0, 0, 0};
+    for (int64_t i = 0; i < b->nRegions; i++) {
+        const int64_t w = hp->plan[i].maxW;
+        const int empty = b->regions[i].lX + b->regions[i].lY == 0;
+        keys[i].cls = (!enabled || empty || w > 32) ? 3 : (w <= 8 ? 0 : (w <= 16 ? 1 : 2));
+        perClass[keys[i].cls]++;
+    }
+    for (int k = 0; k < 3; k++) /* a class too small for its own launch joins the next wider one */
+        if (perClass[k] > 0 && perClass[k] < minCount) {
+            for (int64_t i = 0; i < b->nRegions; i++)
+                if (keys[i].cls == k) keys[i].cls = k + 1;
+            perClass[k + 1] += perClass[k];
+            perClass[k] = 0;
+        }
+    /* the wide regions by the LDS their rolling buffers and symbol strings need (classes 3..9; the last one keeps
+     * both in global memory): a launch per class, each with its own occupancy and per-wave scratch */
+    for (int64_t i = 0; i < b->nRegions; i++) {
+        if (keys[i].cls != 3) continue;
+        const int64_t w = hp->plan[i].maxW;
+        const size_t lds = sizeof(double) * (size_t)(544 + 768 + (2 * S + 1) * (w + 1)) +
+                           (size_t)((b->regions[i].lX + 3) / 2 + (b->regions[i].lY + 3) / 2) + 16;
+        static const int64_t edge[CPK_WIDE_CLASSES - 2] = {64, 128, 192, 256, 384, 512};
+        /* up to 64 cells: a class of its own for the expectation emitter only -- its in-sweep kernel has a build unrolled
+         * for one 64-lane group per diagonal (BASELINE config 5: 99 % of the regions); the other emitters' kernels loop
+         * over groups and gain nothing from another launch */
+        int k = b->emit == CPECAN_EMIT_EXPECT ? 0 : 1;
+        while (k < CPK_WIDE_CLASSES - 2 && w > edge[k]) k++; /* CPK_WIDE_CLASSES - 2: wider, but its LDS still fits */
+        keys[i].cls = 3 + (lds > 64 * 1024 ? CPK_WIDE_CLASSES - 1 : k);
+    }
+}
+
+/* sort value: class in the top 4 of 36 bits, then 2^31 - 1 - cells (cells < 2^31): ascending = by_cost_desc */
+static inline int cost_key_digit(const CostKey *k, int pass) {
+    return (int)(((((uint64_t)k->cls) << 32 | (uint64_t)(0x7fffffffll - k->cells)) >> (12 * pass)) & 0xfff);
+}
+
+/* (class, cells descending, index): the keys stand in index order, so a STABLE sort by (class, -cells) is the order
+ * by_cost_desc defines -- three counting passes of 12 bits instead of qsort's n log n comparator calls (4.3 ms of every
+ * config-4 batch on one thread). */
+static void sort_cost_keys(CostKey *keys, int64_t n) {
+    CostKey *tmp = malloc(sizeof(CostKey) * (size_t)(n ? n : 1));
+    if (!tmp) {
+        qsort(keys, (size_t)n, sizeof(CostKey), by_cost_desc);
+        return;
+    }
+    CostKey *src = keys, *dst = tmp;
+    for (int pass = 0; pass < 3; pass++) {
+        int64_t count[4097];
+        memset(count, 0, sizeof count);
+        for (int64_t i = 0; i < n; i++) count[cost_key_digit(&src[i], pass) + 1]++;
+        for (int q = 0; q < 4096; q++) count[q + 1] += count[q];
+        for (int64_t i = 0; i < n; i++) dst[count[cost_key_digit(&src[i], pass)]++] = src[i];
+        CostKey *t = src;
+        src = dst;
+        dst = t;
+    }
+    if (src != keys) memcpy(keys, src, sizeof(CostKey) * (size_t)n); /* three passes: the result is in tmp */
+    free(tmp);
+}
+
+/* Class counts add up, class maxima are maxima: one thread's geometry into the batch's. */
+static void geometry_merge(CpkGeometry *dst, const CpkGeometry *src) {
+    for (int k = 0; k < 3; k++) {
+        dst->nPacked[k] += src->nPacked[k];
+        dst->pMaxRefresh[k] = (int32_t)imax(dst->pMaxRefresh[k], src->pMaxRefresh[k]);
+        dst->pRingCells[k] = imax(dst->pRingCells[k], src->pRingCells[k]);
+        dst->pFbCells[k] = imax(dst->pFbCells[k], src->pFbCells[k]);
+    }
+    for (int k = 0; k < CPK_WIDE_CLASSES; k++) {
+        dst->nWide[k] += src->nWide[k];
+        dst->wMaxWidth[k] = (int32_t)imax(dst->wMaxWidth[k], src->wMaxWidth[k]);
+        dst->wMaxRefresh[k] = (int32_t)imax(dst->wMaxRefresh[k], src->wMaxRefresh[k]);
+        dst->wRingCells[k] = imax(dst->wRingCells[k], src->wRingCells[k]);
+        dst->wFbCells[k] = imax(dst->wFbCells[k], src->wFbCells[k]);
+        dst->wSeqLdsBytes[k] = (int32_t)imax(dst->wSeqLdsBytes[k], src->wSeqLdsBytes[k]);
+        dst->wWinLdsBytes[k] = (int32_t)imax(dst->wWinLdsBytes[k], src->wWinLdsBytes[k]);
+    }
+}
+
+/* A class that has regions gets scratch of at least one cell and one refresh point. */
+static void geometry_clamp(CpkGeometry *geo) {
+    for (int k = 0; k < 3; k++)
+        if (geo->nPacked[k]) {
+            if (geo->pMaxRefresh[k] < 1) geo->pMaxRefresh[k] = 1;
+            if (geo->pRingCells[k] < 1) geo->pRingCells[k] = 1;
+            if (geo->pFbCells[k] < 1) geo->pFbCells[k] = 1;
+        }
+    for (int k = 0; k < CPK_WIDE_CLASSES; k++)
+        if (geo->nWide[k]) {
+            if (geo->emit == CPECAN_EMIT_FORWARD) { /* no traceback: nothing is kept of the forward matrix */
+                geo->wRingCells[k] = 1;
+                geo->wFbCells[k] = 1;
+            }
+            if (geo->wMaxRefresh[k] < 1) geo->wMaxRefresh[k] = 1;
+            if (geo->wRingCells[k] < 1) geo->wRingCells[k] = 1;
+            if (geo->wFbCells[k] < 1) geo->wFbCells[k] = 1;
+        }
+}
+
+/* Device region di = host region keys[di].index: what its entry holds of its own, and its segments' output slices.
+ * Returns 0, or the size of an output slice that does not fit 32 bits. */
+static int64_t layout_region(cpecan_batch *b, HostPlan *hp, int64_t di) {
+    const int64_t hiRegion = hp->keys[di].index;
+    HostRegion *r = &b->regions[hiRegion];
+    const RegionPlan *pl = &hp->plan[hiRegion];
+    CpkRegion *g = &hp->devRegions[di];
+    r->devIndex = di;
+    hp->devToHost[di] = hiRegion;
+    g->seqXOff = r->seqXOff;
+    g->seqYOff = r->seqYOff;
+    g->diagOff = hp->diagStart[hiRegion];
+    g->segOff = hp->segStart[hiRegion];
+    g->anchorOff = r->anchorOff;
+    g->nAnchors = (int32_t)r->nAnchors;
+    g->nSeg = (int32_t)pl->nSeg;
+    g->lX = (int32_t)r->lX;
+    g->lY = (int32_t)r->lY;
+    g->raggedLeft = r->raggedLeft;
+    g->raggedRight = r->raggedRight;
+    g->maxWidth = (int32_t)pl->maxW;
+    g->absOk = pl->smooth;
+    /* ring: diagonals are laid down one after another and never straddle the end of the ring */
+    g->ringCap = (int32_t)imin(pl->liveMax + pl->maxW, ((int64_t)1 << 31) - 1);
+    g->cells = r->cells;
+    g->outCap = (int32_t)default_out_cap(b, r);
+    /* every traceback segment gets a part of the region's output slice of its own (used when the segments run as
+     * separate queue items, see CpkItem): in proportion to its emitted diagonals, the parts add up to outCap */
+    CpkSegment *sg = hp->segs + hp->segStart[hiRegion];
+    const int64_t N = r->lX + r->lY;
+    int64_t at = 0;
+    for (int64_t si = 0; si < pl->nSeg; si++) {
+        int64_t cap = N > 0 ? (int64_t)g->outCap * (sg[si].tbFrom - sg[si].tbPrev) / N + 16 : 1;
+        /* every cell may be emitted: the cells of the segment's own emitted diagonals (round 3 gave every segment
+         * the whole region's cells, nSeg times what the slice can ever hold) */
+        if (b->params.threshold <= 0.0) cap = sg[si].emitCells;
+        sg[si].outOff = (int32_t)at;
+        sg[si].outCap = (int32_t)cap;
+        at += cap;
+    }
+    if (at > ((int64_t)1 << 31) - 1) return at;
+    if (at > g->outCap) g->outCap = (int32_t)at;
+    return 0;
+}
+
+/* One region into a thread's class counts and maxima: its own class only, this runs once per region of the batch
+ * (geometry_merge, over every class, joins the threads). */
+static void geometry_add_region(CpkGeometry *lg, int cls, const HostRegion *r, const RegionPlan *pl) {
+    if (cls < 3) { /* narrow: scratch of the packed kernel's sub-slots */
+        const int k = cls;
+        lg->nPacked[k]++;
+        lg->pMaxRefresh[k] = (int32_t)imax(lg->pMaxRefresh[k], pl->refreshMax);
+        lg->pRingCells[k] = imax(lg->pRingCells[k], pl->liveMax + pl->maxW);
+        lg->pFbCells[k] = imax(lg->pFbCells[k], pl->fbMax);
+    } else {
+        const int k = cls - 3;
+        lg->nWide[k]++;
+        lg->wMaxWidth[k] = (int32_t)imax(lg->wMaxWidth[k], (int32_t)pl->maxW);
+        lg->wMaxRefresh[k] = (int32_t)imax(lg->wMaxRefresh[k], pl->refreshMax);
+        lg->wRingCells[k] = imax(lg->wRingCells[k], pl->liveMax + pl->maxW);
+        lg->wFbCells[k] = imax(lg->wFbCells[k], pl->fbMax);
+        lg->wSeqLdsBytes[k] = (int32_t)imax(lg->wSeqLdsBytes[k], imin((r->lX + 3) / 2 + (r->lY + 3) / 2, (int64_t)1 << 30));
+        lg->wWinLdsBytes[k] = (int32_t)imax(lg->wWinLdsBytes[k], imin(pl->winBytes, (int64_t)1 << 30));
+    }
+}
+
+/* The regions in device order: CpkRegion entries, every segment's output slice, the running offsets and the class
+ * geometry.  Two passes: what a region's entry holds of its own (the regions are visited in sorted order, i.e. at random
+ * in memory: on one thread this loop was 6-9 ms of every config-4 batch), then the running offsets and the class maxima. */
+static int layout_device_order(cpecan_batch *b, HostPlan *hp, CpkGeometry *geo) {
+    hp->devRegions = host_zalloc((size_t)b->nRegions, sizeof(CpkRegion));
+    hp->devToHost = cpk_host_alloc(sizeof(int64_t) * (size_t)b->nRegions);
+    if (!hp->devRegions || !hp->devToHost) return CPECAN_ENOMEM;
+    memset(geo, 0, sizeof *geo);
+    geo->nRegions = (int32_t)b->nRegions;
+    geo->nStates = is_five(b->model.type) ? 5 : 3;
+    geo->emit = b->emit;
+    geo->debug = b->debug;
+    int64_t tooLarge = -1;
+#pragma omp parallel num_threads(cpk_host_threads()) if (b->nRegions >= 4096)
+    {
+        CpkGeometry lg; /* this thread's class counts and maxima */
+        memset(&lg, 0, sizeof lg);
+#pragma omp for schedule(static)
+        for (int64_t di = 0; di < b->nRegions; di++) {
+            const int64_t at = layout_region(b, hp, di);
+            if (at) {
+#pragma omp critical(cpk_order)
+                if (at > tooLarge) tooLarge = at;
+                continue;
+            }
+            geometry_add_region(&lg, hp->keys[di].cls, &b->regions[hp->keys[di].index], &hp->plan[hp->keys[di].index]);
+        }
+#pragma omp critical(cpk_order)
+        geometry_merge(geo, &lg);
+    }
+    if (tooLarge >= 0) {
+        /* segment offsets and the region's slice are 32-bit: threshold <= 0 on a region of more than 2^31 cells x
+         * segments cannot be laid out (the reference would return a list of that many tuples) */
+        cpk_set_error("a region's output slice exceeds 2^31 triples (%lld): raise the threshold or split the region", (long long)tooLarge);
+        return CPECAN_EINVAL;
+    }
+    int64_t outAt = 0, dbgCells = 0, dbgDiags = 0;
+    for (int64_t di = 0; di < b->nRegions; di++) { /* the running offsets, in device order */
+        CpkRegion *g = &hp->devRegions[di];
+        g->dbgCellOff = dbgCells;
+        g->dbgDiagOff = dbgDiags;
+        if (b->debug) {
+            dbgCells += g->cells;
+            dbgDiags += (int64_t)g->lX + g->lY + 1;
+        }
+        hp->totalCells += g->cells;
+        g->outOff = outAt;
+        outAt += g->outCap;
+    }
+    geometry_clamp(geo);
+    /* the scalar geometry (maxWidth, rollStride, ringCells, ..., useGlobalRoll) is filled per launch from the class
+     * arrays by the device side (cpk_class_geometry) */
+    hp->outTriples = outAt < 1 ? 1 : outAt;
+    hp->dbgCells = dbgCells < 1 ? 1 : dbgCells;
+    hp->dbgDiags = dbgDiags < 1 ? 1 : dbgDiags;
+    return CPECAN_OK;
+}
+
+/* Everything an upload decides before a device is involved; integers only.  On failure the caller frees hp all the same. */
+static int batch_plan(cpecan_batch *b, HostPlan *hp, CpkGeometry *geo, CpkModel *km) {
+    const double t0 = now_ms();
+    int rc = host_plan_init(b, hp);
+    if (rc == CPECAN_OK) rc = plan_regions(b, hp);
+    if (rc != CPECAN_OK) return rc;
+    const double t1 = now_ms();
+    classify_regions(b, hp);
+    const double t2 = now_ms();
+    sort_cost_keys(hp->keys, b->nRegions);
+    const double t3 = now_ms();
+    rc = layout_device_order(b, hp, geo);
+    if (rc != CPECAN_OK) return rc;
+    kernel_model(&b->model, b->params.threshold, km);
+    const double t4 = now_ms();
+    if (trace_host())
+        fprintf(stderr, "cpecan upload: %lld regions, %lld segment slots: band walk %.1f ms, classes %.1f, sort %.1f, device order %.1f\n",
+                (long long)b->nRegions, (long long)hp->nSegs, t1 - t0, t2 - t1, t3 - t2, t4 - t3);
+    return CPECAN_OK;
+}
+
+static uint64_t fnv1a64(const void *data, size_t n, uint64_t h) {
+    const unsigned char *p = data;
+    for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+
+/* For tests, no device needed: plans an unfrozen batch as cpecan_batch_upload would and hashes (FNV-1a, 64 bits) the
+ * whole plan -- the CpkRegion array in device order, devToHost, every segment slot, and the geometry with outTriples,
+ * nDiags, dbgCells and dbgDiags.  The plan is dropped; of the batch only what every plan rewrites (a region's cell
+ * count and device index) is touched. */
+int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]) {
+    if (!b || !out || b->frozen || dl_busy(b)) return CPECAN_ESTATE;
+    const uint64_t seed = 0xcbf29ce484222325ull;
+    out[0] = out[1] = out[2] = out[3] = seed;
+    if (b->nRegions == 0) return CPECAN_OK;
+    HostPlan hp;
+    CpkGeometry geo;
+    CpkModel km;
+    const int rc = batch_plan(b, &hp, &geo, &km);
+    if (rc == CPECAN_OK) {
+        const int64_t totals[4] = {hp.outTriples, hp.totalDiags, hp.dbgCells, hp.dbgDiags};
+        out[0] = fnv1a64(hp.devRegions, sizeof(CpkRegion) * (size_t)b->nRegions, seed);
+        out[1] = fnv1a64(hp.devToHost, sizeof(int64_t) * (size_t)b->nRegions, seed);
+        out[2] = fnv1a64(hp.segs, sizeof(CpkSegment) * (size_t)hp.nSegs, seed);
+        out[3] = fnv1a64(totals, sizeof totals, fnv1a64(&geo, sizeof geo, seed));
+    }
+    host_plan_free(&hp);
+    return rc;
+}
+
 int cpecan_batch_upload(cpecan_batch *b) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || b->frozen) return CPECAN_ESTATE;
@@ -1122,522 +1651,32 @@ int cpecan_batch_upload(cpecan_batch *b) {
         b->frozen = 1;
         return CPECAN_OK;
     }
-    const cpecan_params *p = &b->params;
-    const int S = is_five(b->model.type) ? 5 : 3;
-    int rc = CPECAN_OK;
-
-    /* Planning walks every region's band ONCE as a stream of diagonals (cpecan_band.inl) and keeps per-region sums only:
-     * cell count, widest diagonal, the traceback schedule (pairwiseAligner.c:791-810) and the scratch sizes it implies.
-     * The per-diagonal table the kernels read (16 bytes per diagonal, 640 MB at 10 000 pairs x 2 kb) is built on the
-     * device from the anchors by the same iterator (cpk_device_upload).  Regions are independent: OpenMP. */
-    const double tU0 = now_ms();
-    int64_t totalDiags = 0;
-    int64_t *diagStart = malloc(sizeof(int64_t) * (size_t)b->nRegions);
-    int64_t *segStart = malloc(sizeof(int64_t) * (size_t)b->nRegions);
-    CostKey *keys = malloc(sizeof(CostKey) * (size_t)b->nRegions);
-    RegionPlan *plan = calloc((size_t)b->nRegions, sizeof(RegionPlan));
-    CpkSegment *segs = NULL;
-    int64_t nSegs = 0; /* slots: every region gets room for an upper bound on its segment count */
-    if (!diagStart || !segStart || !keys || !plan) {
-        rc = CPECAN_ENOMEM;
-        goto fail1;
-    }
-    for (int64_t i = 0; i < b->nRegions; i++) {
-        const int64_t N = b->regions[i].lX + b->regions[i].lY;
-        diagStart[i] = totalDiags;
-        totalDiags += N + 1;
-        segStart[i] = nSegs;
-        /* consecutive traceback points are at least minDiagsBetweenTraceBack - (traceBackDiagonals + 1) >= 1 apart */
-        nSegs += N / (p->minDiagsBetweenTraceBack - p->traceBackDiagonals - 1) + 2;
-    }
-    segs = host_zalloc((size_t)nSegs, sizeof(CpkSegment));
-    if (!segs) {
-        rc = CPECAN_ENOMEM;
-        goto fail1;
-    }
-    const int dynamic = b->emit == CPECAN_EMIT_FORWARD ? 0 : p->dynamicAnchorExpansion; /* :894: forward uses the static band */
-    const char *fwEnv = getenv("CPECAN_FAST_WALK");
-    const int fastWalk = !(fwEnv && atoi(fwEnv) == 0);
-    int64_t badRegion = -1;
-#pragma omp parallel num_threads(cpk_host_threads())
-    {
-        /* cell offsets of the last traceBackDiagonals + 3 diagonals: the schedule looks that far back */
-        const int64_t K = p->traceBackDiagonals + 3;
-        int64_t *histOff = malloc(sizeof(int64_t) * (size_t)K * 4), *histW = histOff ? histOff + K : NULL;
-        int64_t *histXlo = histOff ? histOff + 2 * K : NULL, *histYlo = histOff ? histOff + 3 * K : NULL;
-        if (!histOff) {
-#pragma omp critical(cpk_plan)
-            rc = CPECAN_ENOMEM;
-        }
-#pragma omp for schedule(dynamic, 16)
-        for (int64_t i = 0; i < b->nRegions; i++) {
-            HostRegion *r = &b->regions[i];
-            RegionPlan *pl = &plan[i];
-            const int64_t N = r->lX + r->lY;
-            keys[i].cells = 0;
-            keys[i].index = i;
-            if (!histOff) continue;
-            CpkBandIter it;
-            memset(&it, 0, sizeof it);
-            const int keepRuns = b->runForm == 1;
-            int bad = keepRuns ? cpk_band_init_runs(&it, b->runs + 4 * r->runOff, r->nRuns, r->nAnchors, r->lX, r->lY, p->diagonalExpansion)
-                               : cpk_band_init(&it, b->anchors + (int64_t)b->anchorStride * r->anchorOff, b->anchorStride, r->nAnchors,
-                                               r->lX, r->lY, p->diagonalExpansion, dynamic);
-            CpkSegment *sg = segs + segStart[i];
-            int64_t cells = 0, tracedBackTo = 0;
-            int64_t offTracedBackTo = 0; /* cells before diagonal tracedBackTo */
-            int64_t offAfter = 0;        /* cells before diagonal tracedBackTo + 1 */
-            int64_t slot = 0; /* d % K without the division: this loop runs once per diagonal of the batch */
-            int64_t maxW = 0;
-            int64_t prevLo = 0, prevHi = 0;
-            int64_t winXlo = 0, winYlo = 0; /* smallest x and y of diagonal tracedBackTo + 1 (symbol windows, RegionPlan::winBytes) */
-            int smooth = !dynamic;
-            const int64_t minBetween = p->minDiagsBetweenTraceBack, narrow = p->diagonalExpansion * 2 + 1;
-            /* Runs of diagonal neighbours among the anchors (realign-style input: one anchor per matching column) are walked
-             * in closed form.  Between two anchors (X, Y) and (X + 1, Y + 1) of a run, away from the matrix edges, the band
-             * holds exactly two diagonals: x-y in [X-Y-E-1, X-Y+E+1] (E + 2 cells) and [X-Y-E, X-Y+E] (E + 1 cells) -- both
-             * "narrow" for E >= 2 (<= 2E + 1) and both edges one x-y step apart from their neighbours'.  So a stretch of s such
-             * intervals adds s (2E + 3) cells and nothing else, unless a traceback point may fall into it or behind it within the
-             * K diagonals whose offsets the schedule looks back at: those diagonals are walked one by one.
-             * (BASELINE config 4: 1.25e8 diagonals at ~14 cycles each were 31 ms of every batch on 16 threads.)  CPECAN_FAST_WALK=0
-             * walks every diagonal (tests compare the two). */
-            const cpk_anchor_t *ra = keepRuns ? NULL : b->anchors + (int64_t)b->anchorStride * r->anchorOff;
-            const int64_t E = p->diagonalExpansion, hE = E / 2;
-            const int fastOk = fastWalk && !dynamic && E >= 2 && b->anchorStride == 2;  /* (runs are kept for stride 2 only) */
-            for (int64_t d = 0; d <= N && !bad; d++, slot = slot + 1 == K ? 0 : slot + 1) {
-                if (fastOk && cpk_band_in_run(&it, d)) {
-                    /* in the interval (A_j -> A_j+1) of a run, j = used - 2, about to emit its first diagonal */
-                    const int64_t j = it.used - 2;
-                    int64_t sMax = (tracedBackTo + minBetween - (K + 1) - d) / 2; /* every skipped diagonal stays K + 1 below the next traceback point */
-                    sMax = imin(sMax, imin(r->lX - hE - it.pX, r->lY - hE - it.pY)); /* the last interval's rectangle inside the matrix */
-                    if (it.pX - hE < 0 || it.pY - hE < 0) sMax = 0;                  /* ... and the first one's */
-                    sMax = imin(sMax, (N - 2 - d) / 2);
-                    int64_t sRun = 0; /* intervals of the run from here: anchors j .. j + sRun are diagonal neighbours */
-                    if (keepRuns) {
-                        /* anchor j + 1 is the one in (qX, qY): anchor qRo of run qRi, with length - 1 - qRo neighbours behind it
-                         * in its run (a run that happens to continue in the next one starts a stretch of its own there) */
-                        sRun = 1 + (int64_t)b->runs[4 * (r->runOff + it.qRi) + 2] - 1 - it.qRo;
-                        sRun = sRun < sMax ? sRun : sMax;
-                        sRun = sRun < 0 ? 0 : sRun;
-                    } else {
-                        while (sRun < sMax && j + sRun + 1 < r->nAnchors && ra[2 * (j + sRun + 1)] == ra[2 * (j + sRun)] + 1 &&
-                               ra[2 * (j + sRun + 1) + 1] == ra[2 * (j + sRun) + 1] + 1)
-                            sRun++;
-                    }
-                    if (sRun >= 2) {
-                        const int64_t add = sRun * (2 * E + 3);
-                        if (cells + add >= (int64_t)1 << 31) {
-                            bad = 1;
-                            break;
-                        }
-                        const int64_t xmy0 = it.pX - it.pY;
-                        if (d > 0) { /* the step into the stretch: from the diagonal before to its first one */
-                            const int64_t dl = (xmy0 - E - 1) - prevLo, dh = (xmy0 + E + 1) - prevHi;
-                            smooth &= (dl == 1 || dl == -1) && (dh == 1 || dh == -1);
-                        }
-                        cells += add;
-                        maxW = E + 2 > maxW ? E + 2 : maxW;
-                        prevLo = xmy0 - E; /* the stretch's last diagonal: the second one of an interval */
-                        prevHi = xmy0 + E;
-                        /* the iterator as it stands behind anchor j + sRun's own diagonal */
-                        const int64_t jn = j + sRun;
-                        if (keepRuns) {
-                            /* anchor jn = anchor j + 1 moved sRun - 1 steps along its run; the cursor goes to the anchor behind it */
-                            it.pX = it.qX + (sRun - 1);
-                            it.pY = it.qY + (sRun - 1);
-                            it.ri = it.qRi;
-                            it.ro = it.qRo + (int32_t)sRun;
-                            if (it.ro >= b->runs[4 * (r->runOff + it.ri) + 2]) {
-                                it.ro = 0;
-                                it.ri++;
-                            }
-                        } else {
-                            it.pX = (int64_t)ra[2 * jn] + 1;
-                            it.pY = (int64_t)ra[2 * jn + 1] + 1;
-                        }
-                        it.used = jn + 1;
-                        it.qX = r->lX;
-                        it.qY = r->lY;
-                        if (it.used < it.n) {
-                            if (keepRuns) {
-                                const int32_t *q = b->runs + 4 * (r->runOff + it.ri);
-                                it.qX = (int64_t)q[0] + it.ro + 1;
-                                it.qY = (int64_t)q[1] + it.ro + 1;
-                                it.qRi = it.ri;
-                                it.qRo = it.ro;
-                                if (++it.ro >= q[2]) {
-                                    it.ro = 0;
-                                    it.ri++;
-                                }
-                            } else {
-                                it.qX = (int64_t)ra[2 * it.used] + 1;
-                                it.qY = (int64_t)ra[2 * it.used + 1] + 1;
-                            }
-                            it.used++;
-                            if (it.qX <= it.pX || it.qY <= it.pY || it.qX > it.lX || it.qY > it.lY) {
-                                bad = 1;
-                                break;
-                            }
-                        }
-                        it.qSum = it.qX + it.qY;
-                        it.xLo = cpk_clamp(it.pX - hE, it.lX);
-                        it.yHi = cpk_clamp(it.qY + hE, it.lY);
-                        it.xHi = cpk_clamp(it.qX + hE, it.lX);
-                        it.yLo = cpk_clamp(it.pY - hE, it.lY);
-                        d += 2 * sRun - 1; /* the loop's own step makes it 2 sRun */
-                        slot = (slot + 2 * sRun - 1) % K;
-                        continue;
-                    }
-                }
-                int64_t lo, hi;
-                if (cpk_band_next(&it, d, &lo, &hi)) {
-                    bad = 1;
-                    break;
-                }
-                const int64_t w = (hi - lo) / 2 + 1;
-                if (cells + w >= (int64_t)1 << 31) {
-                    bad = 1;
-                    break;
-                }
-                if (d > 0) {
-                    const int64_t dl = lo - prevLo, dh = hi - prevHi;
-                    smooth &= (dl == 1 || dl == -1) && (dh == 1 || dh == -1);
-                }
-                prevLo = lo;
-                prevHi = hi;
-                histOff[slot] = cells;
-                histW[slot] = w;
-                histXlo[slot] = (d + lo) >> 1;      /* x of the diagonal's first cell */
-                histYlo[slot] = d - ((d + hi) >> 1); /* y of its last cell: the smallest */
-                if (d == 1) {
-                    offAfter = cells; /* tracedBackTo == 0 for the first segment */
-                    winXlo = histXlo[slot];
-                    winYlo = histYlo[slot];
-                }
-                maxW = w > maxW ? w : maxW;
-                cells += w;
-                if (d == 0) continue;
-                const int atEnd = d == N;
-                const int tracebackPoint = d >= tracedBackTo + minBetween && w <= narrow;
-                if (!atEnd && !tracebackPoint) continue;
-                memset(sg, 0, sizeof *sg);
-                sg->tbPrev = (int32_t)tracedBackTo;
-                sg->dTop = (int32_t)d;
-                sg->tbFrom = (int32_t)(d - (atEnd ? 0 : p->traceBackDiagonals + 1));
-                sg->atEnd = atEnd;
-                sg->nRefresh = (int32_t)((sg->tbFrom - (sg->tbPrev + 1)) / CPK_REFRESH_PERIOD + 1);
-                pl->refreshMax = sg->nRefresh > pl->refreshMax ? sg->nRefresh : pl->refreshMax;
-                /* forward diagonals tbPrev..dTop are live during this traceback */
-                pl->liveMax = imax(pl->liveMax, cells - offTracedBackTo);
-                const int64_t tf = sg->tbFrom;
-                const int64_t tfSlot = tf % K; /* once per segment */
-                const int64_t fbCells = histOff[tfSlot] + histW[tfSlot] - offAfter;
-                pl->fbMax = imax(pl->fbMax, fbCells);
-                sg->emitCells = (int32_t)fbCells;
-                {
-                    /* the symbols the segment's diagonals tbPrev + 1 .. d touch, the kernel's arithmetic (cpk_sweep.inl,
-                     * "Symbol windows"): from the even index at or below the smallest x (y) to one past the largest */
-                    const int64_t x0 = winXlo & ~(int64_t)1, y0 = winYlo & ~(int64_t)1;
-                    const int64_t x1 = imin(((d + hi) >> 1) + 1, r->lX + 1), y1 = imin(d - ((d + lo) >> 1) + 1, r->lY + 1);
-                    pl->winBytes = imax(pl->winBytes, (x1 - x0 + 2) / 2 + (y1 - y0 + 2) / 2);
-                }
-                pl->nSeg++;
-                sg++;
-
-                /* the next segment starts from tbFrom: remember the cell offsets of tbFrom and tbFrom + 1 */
-                tracedBackTo = tf;
-                offTracedBackTo = histOff[tfSlot];
-                offAfter = histOff[tfSlot] + histW[tfSlot];
-                if (tf < d) { /* diagonal tf + 1 has been walked already: within the last K */
-                    const int64_t s1 = (tf + 1) % K;
-                    winXlo = histXlo[s1];
-                    winYlo = histYlo[s1];
-                }
-            }
-            pl->maxW = maxW;
-            pl->smooth = smooth;
-            if (bad) {
-#pragma omp critical(cpk_plan)
-                {
-                    rc = CPECAN_EINVAL;
-                    if (badRegion < 0 || i < badRegion) badRegion = i;
-                }
-                continue;
-            }
-            r->cells = cells;
-            keys[i].cells = N > 0 ? cells : 0;
-        }
-        free(histOff);
-    }
-    const double tU1 = now_ms();
-    if (rc != CPECAN_OK) {
-        if (badRegion >= 0)
-            cpk_set_error("region %lld of problem %lld: anchors do not define a valid band (or the band exceeds 2^31 cells)",
-                          (long long)badRegion, (long long)b->regions[badRegion].problem);
-        goto fail1;
-    }
-    /* Narrow regions (no diagonal wider than 32 cells: realign-style bands) are packed several to a wave by their own
-     * kernel; they come first in the device order.  Within each class: longest first (the work queues are LPT). */
-    {
-        const char *env = getenv("CPECAN_PACKED"); /* diagnostic: 0 = one wave per region for every region */
-        /* (bands with per-anchor expansions run the packed kernel's DYN variant: their edges may move backwards) */
-        const int enabled = (b->emit == CPECAN_EMIT_MATCH || b->emit == CPECAN_EMIT_INDEL || b->emit == CPECAN_EMIT_EXPECT) && !b->debug &&
-                            !(env && atoi(env) == 0);
-        /* a launch is not worth fewer regions (CPECAN_PACKED=2: always, for tests).  The indel emitter's packed form pays a
-         * pass of its own over every emitted cell: measured on realign-style batches it ties with one wave per region at
-         * 10 000 alignments (32.1 against 30.5 ms) and wins 2.4x at 50 000 (61 against 148 ms) -- from ~12 000 regions of
-         * a class, i.e. once a wave has half a dozen rounds to go (profiles/r04_packed_indel_emitter.txt) */
-        const int64_t minCount = (env && atoi(env) >= 2) ? 1 : (b->emit == CPECAN_EMIT_INDEL ? 12000 : 64);
-        int64_t perClass[4] = {0, 0, 0, 0};
-        for (int64_t i = 0; i < b->nRegions; i++) {
-            const int64_t w = plan[i].maxW;
-            const int empty = b->regions[i].lX + b->regions[i].lY == 0;
-            keys[i].cls = (!enabled || empty || w > 32) ? 3 : (w <= 8 ? 0 : (w <= 16 ? 1 : 2));
-            perClass[keys[i].cls]++;
-        }
-        for (int k = 0; k < 3; k++) /* a class too small for its own launch joins the next wider one */
-            if (perClass[k] > 0 && perClass[k] < minCount) {
-                for (int64_t i = 0; i < b->nRegions; i++)
-                    if (keys[i].cls == k) keys[i].cls = k + 1;
-                perClass[k + 1] += perClass[k];
-                perClass[k] = 0;
-            }
-        /* the wide regions by the LDS their rolling buffers and symbol strings need (classes 3..9; the last one keeps
-         * both in global memory): a launch per class, each with its own occupancy and per-wave scratch */
-        for (int64_t i = 0; i < b->nRegions; i++) {
-            if (keys[i].cls != 3) continue;
-            const int64_t w = plan[i].maxW;
-            const size_t lds = sizeof(double) * (size_t)(544 + 768 + (2 * S + 1) * (w + 1)) +
-                               (size_t)((b->regions[i].lX + 3) / 2 + (b->regions[i].lY + 3) / 2) + 16;
-            static const int64_t edge[CPK_WIDE_CLASSES - 2] = {64, 128, 192, 256, 384, 512};
-            /* up to 64 cells: a class of its own for the expectation emitter only -- its in-sweep kernel has a build unrolled
-             * for one 64-lane group per diagonal (BASELINE config 5: 99 % of the regions); the other emitters' kernels loop
-             * over groups and gain nothing from another launch */
-            int k = b->emit == CPECAN_EMIT_EXPECT ? 0 : 1;
-            while (k < CPK_WIDE_CLASSES - 2 && w > edge[k]) k++; /* CPK_WIDE_CLASSES - 2: wider, but its LDS still fits */
-            keys[i].cls = 3 + (lds > 64 * 1024 ? CPK_WIDE_CLASSES - 1 : k);
-        }
-    }
-    const double tU2 = now_ms();
-    /* (class, cells descending, index): the keys stand in index order, so a STABLE sort by (class, -cells) is the order
-     * by_cost_desc defines -- three counting passes of 12 bits instead of qsort's n log n comparator calls (4.3 ms of every
-     * config-4 batch on one thread). */
-    {
-        const int64_t n = b->nRegions;
-        CostKey *tmp = malloc(sizeof(CostKey) * (size_t)(n ? n : 1));
-        if (!tmp) {
-            qsort(keys, (size_t)n, sizeof(CostKey), by_cost_desc);
-        } else {
-            CostKey *src = keys, *dst = tmp;
-            for (int pass = 0; pass < 3; pass++) {
-                int64_t count[4097];
-                memset(count, 0, sizeof count);
-                /* sort value: class in the top 4 of 36 bits, then 2^31 - 1 - cells (cells < 2^31): ascending = by_cost_desc */
-#define CPK_SORT_DIGIT(k) ((int)(((((uint64_t)(k).cls) << 32 | (uint64_t)(0x7fffffffll - (k).cells)) >> (12 * pass)) & 0xfff))
-                for (int64_t i = 0; i < n; i++) count[CPK_SORT_DIGIT(src[i]) + 1]++;
-                for (int q = 0; q < 4096; q++) count[q + 1] += count[q];
-                for (int64_t i = 0; i < n; i++) dst[count[CPK_SORT_DIGIT(src[i])]++] = src[i];
-#undef CPK_SORT_DIGIT
-                CostKey *t = src;
-                src = dst;
-                dst = t;
-            }
-            if (src != keys) memcpy(keys, src, sizeof(CostKey) * (size_t)n); /* three passes: the result is in tmp */
-            free(tmp);
-        }
-    }
-    const double tU3 = now_ms();
-
-    b->devRegions = host_zalloc((size_t)b->nRegions, sizeof(CpkRegion));
-    b->devToHost = cpk_host_alloc(sizeof(int64_t) * (size_t)b->nRegions);
-    if (!b->devRegions || !b->devToHost) {
-        rc = CPECAN_ENOMEM;
-        goto fail2;
-    }
+    HostPlan hp;
     CpkGeometry geo;
-    memset(&geo, 0, sizeof geo);
-    geo.nRegions = (int32_t)b->nRegions;
-    geo.nStates = S;
-    geo.emit = b->emit;
-    geo.debug = b->debug;
-    int64_t outAt = 0, dbgCells = 0, dbgDiags = 0, totalCells = 0;
-    /* Two passes: what a region's entry holds of its own (the regions are visited in sorted order, i.e. at random in
-     * memory: on one thread this loop was 6-9 ms of every config-4 batch), then the running offsets and the class maxima. */
-    int64_t tooLarge = -1;
-#pragma omp parallel num_threads(cpk_host_threads()) if (b->nRegions >= 4096)
-    {
-    CpkGeometry lg; /* this thread's class counts and maxima */
-    memset(&lg, 0, sizeof lg);
-#pragma omp for schedule(static)
-    for (int64_t di = 0; di < b->nRegions; di++) {
-        const int64_t hiRegion = keys[di].index;
-        HostRegion *r = &b->regions[hiRegion];
-        const RegionPlan *pl = &plan[hiRegion];
-        CpkRegion *g = &b->devRegions[di];
-        r->devIndex = di;
-        b->devToHost[di] = hiRegion;
-        g->seqXOff = r->seqXOff;
-        g->seqYOff = r->seqYOff;
-        g->diagOff = diagStart[hiRegion];
-        g->segOff = segStart[hiRegion];
-        g->anchorOff = r->anchorOff;
-        g->nAnchors = (int32_t)r->nAnchors;
-        g->nSeg = (int32_t)pl->nSeg;
-        g->lX = (int32_t)r->lX;
-        g->lY = (int32_t)r->lY;
-        g->raggedLeft = r->raggedLeft;
-        g->raggedRight = r->raggedRight;
-        g->maxWidth = (int32_t)pl->maxW;
-        g->absOk = pl->smooth;
-        /* ring: diagonals are laid down one after another and never straddle the end of the ring */
-        g->ringCap = (int32_t)imin(pl->liveMax + pl->maxW, ((int64_t)1 << 31) - 1);
-        g->cells = r->cells;
-        g->outCap = (int32_t)default_out_cap(b, r);
-        /* every traceback segment gets a part of the region's output slice of its own (used when the segments run as
-         * separate queue items, see CpkItem): in proportion to its emitted diagonals, the parts add up to outCap */
-        {
-            CpkSegment *sg = segs + segStart[hiRegion];
-            const int64_t N = r->lX + r->lY;
-            int64_t at = 0;
-            for (int64_t si = 0; si < pl->nSeg; si++) {
-                int64_t cap = N > 0 ? (int64_t)g->outCap * (sg[si].tbFrom - sg[si].tbPrev) / N + 16 : 1;
-                /* every cell may be emitted: the cells of the segment's own emitted diagonals (round 3 gave every segment
-                 * the whole region's cells, nSeg times what the slice can ever hold) */
-                if (b->params.threshold <= 0.0) cap = sg[si].emitCells;
-                sg[si].outOff = (int32_t)at;
-                sg[si].outCap = (int32_t)cap;
-                at += cap;
-            }
-            if (at > ((int64_t)1 << 31) - 1) {
-#pragma omp critical(cpk_order)
-                if (at > tooLarge) tooLarge = at;
-                continue;
-            }
-            if (at > g->outCap) g->outCap = (int32_t)at;
-        }
-        if (keys[di].cls < 3) { /* narrow: scratch of the packed kernel's sub-slots */
-            const int k = keys[di].cls;
-            lg.nPacked[k]++;
-            lg.pMaxRefresh[k] = pl->refreshMax > lg.pMaxRefresh[k] ? (int32_t)pl->refreshMax : lg.pMaxRefresh[k];
-            lg.pRingCells[k] = imax(lg.pRingCells[k], pl->liveMax + pl->maxW);
-            lg.pFbCells[k] = imax(lg.pFbCells[k], pl->fbMax);
-        } else {
-            const int k = keys[di].cls - 3;
-            lg.nWide[k]++;
-            lg.wMaxWidth[k] = g->maxWidth > lg.wMaxWidth[k] ? g->maxWidth : lg.wMaxWidth[k];
-            lg.wMaxRefresh[k] = pl->refreshMax > lg.wMaxRefresh[k] ? (int32_t)pl->refreshMax : lg.wMaxRefresh[k];
-            lg.wRingCells[k] = imax(lg.wRingCells[k], pl->liveMax + pl->maxW);
-            lg.wFbCells[k] = imax(lg.wFbCells[k], pl->fbMax);
-            lg.wSeqLdsBytes[k] = (int32_t)imax(lg.wSeqLdsBytes[k], imin((r->lX + 3) / 2 + (r->lY + 3) / 2, (int64_t)1 << 30));
-            lg.wWinLdsBytes[k] = (int32_t)imax(lg.wWinLdsBytes[k], imin(pl->winBytes, (int64_t)1 << 30));
-        }
-    }
-#pragma omp critical(cpk_order)
-    {
-        for (int k = 0; k < 3; k++) {
-            geo.nPacked[k] += lg.nPacked[k];
-            geo.pMaxRefresh[k] = lg.pMaxRefresh[k] > geo.pMaxRefresh[k] ? lg.pMaxRefresh[k] : geo.pMaxRefresh[k];
-            geo.pRingCells[k] = imax(geo.pRingCells[k], lg.pRingCells[k]);
-            geo.pFbCells[k] = imax(geo.pFbCells[k], lg.pFbCells[k]);
-        }
-        for (int k = 0; k < CPK_WIDE_CLASSES; k++) {
-            geo.nWide[k] += lg.nWide[k];
-            geo.wMaxWidth[k] = lg.wMaxWidth[k] > geo.wMaxWidth[k] ? lg.wMaxWidth[k] : geo.wMaxWidth[k];
-            geo.wMaxRefresh[k] = lg.wMaxRefresh[k] > geo.wMaxRefresh[k] ? lg.wMaxRefresh[k] : geo.wMaxRefresh[k];
-            geo.wRingCells[k] = imax(geo.wRingCells[k], lg.wRingCells[k]);
-            geo.wFbCells[k] = imax(geo.wFbCells[k], lg.wFbCells[k]);
-            geo.wSeqLdsBytes[k] = lg.wSeqLdsBytes[k] > geo.wSeqLdsBytes[k] ? lg.wSeqLdsBytes[k] : geo.wSeqLdsBytes[k];
-            geo.wWinLdsBytes[k] = lg.wWinLdsBytes[k] > geo.wWinLdsBytes[k] ? lg.wWinLdsBytes[k] : geo.wWinLdsBytes[k];
-        }
-    }
-    }
-    if (tooLarge >= 0) {
-        /* segment offsets and the region's slice are 32-bit: threshold <= 0 on a region of more than 2^31 cells x
-         * segments cannot be laid out (the reference would return a list of that many tuples) */
-        cpk_set_error("a region's output slice exceeds 2^31 triples (%lld): raise the threshold or split the region", (long long)tooLarge);
-        rc = CPECAN_EINVAL;
-        goto fail2;
-    }
-    for (int64_t di = 0; di < b->nRegions; di++) { /* the running offsets, in device order */
-        CpkRegion *g = &b->devRegions[di];
-        g->dbgCellOff = dbgCells;
-        g->dbgDiagOff = dbgDiags;
-        if (b->debug) {
-            dbgCells += g->cells;
-            dbgDiags += (int64_t)g->lX + g->lY + 1;
-        }
-        totalCells += g->cells;
-        g->outOff = outAt;
-        outAt += g->outCap;
-    }
-    for (int k = 0; k < 3; k++)
-        if (geo.nPacked[k]) {
-            if (geo.pMaxRefresh[k] < 1) geo.pMaxRefresh[k] = 1;
-            if (geo.pRingCells[k] < 1) geo.pRingCells[k] = 1;
-            if (geo.pFbCells[k] < 1) geo.pFbCells[k] = 1;
-        }
-    for (int k = 0; k < CPK_WIDE_CLASSES; k++)
-        if (geo.nWide[k]) {
-            if (b->emit == CPECAN_EMIT_FORWARD) { /* no traceback: nothing is kept of the forward matrix */
-                geo.wRingCells[k] = 1;
-                geo.wFbCells[k] = 1;
-            }
-            if (geo.wMaxRefresh[k] < 1) geo.wMaxRefresh[k] = 1;
-            if (geo.wRingCells[k] < 1) geo.wRingCells[k] = 1;
-            if (geo.wFbCells[k] < 1) geo.wFbCells[k] = 1;
-        }
-    /* the scalar geometry (maxWidth, rollStride, ringCells, ..., useGlobalRoll) is filled per launch from the class
-     * arrays by the device side (cpk_class_geometry) */
-    b->geo = geo;
-    b->segs = segs;
-    b->nSegs = nSegs;
-    b->nDiags = totalDiags;
-    b->outTriples = outAt < 1 ? 1 : outAt;
-    b->dbgCells = dbgCells < 1 ? 1 : dbgCells;
-    b->dbgDiags = dbgDiags < 1 ? 1 : dbgDiags;
-
-    b->stats.problems = b->nProblems;
-    b->stats.regions = b->nRegions;
-    b->stats.cells = totalCells;
-    b->stats.diagonals = totalDiags;
     CpkModel km;
-    kernel_model(&b->model, p->threshold, &km);
-    const double tU4 = now_ms();
-    if (trace_host())
-        fprintf(stderr, "cpecan upload: %lld regions, %lld segment slots: band walk %.1f ms, classes %.1f, sort %.1f, device order %.1f\n",
-                (long long)b->nRegions, (long long)nSegs, tU1 - tU0, tU2 - tU1, tU3 - tU2, tU4 - tU3);
-    if (!b->dev) {
-        rc = cpk_device_create(&b->dev, b->device); /* fails with CPECAN_ENODEVICE when there is no GPU */
-        if (rc != CPECAN_OK) goto fail2;
+    int rc = batch_plan(b, &hp, &geo, &km);
+    if (rc == CPECAN_OK) {
+        b->stats.problems = b->nProblems;
+        b->stats.regions = b->nRegions;
+        b->stats.cells = hp.totalCells;
+        b->stats.diagonals = hp.totalDiags;
+        if (!b->dev) rc = cpk_device_create(&b->dev, b->device); /* fails with CPECAN_ENODEVICE when there is no GPU */
     }
-    rc = cpk_device_upload(b->dev, &geo, &km, b->devRegions, b->runForm == 1 ? NULL : b->anchors, b->anchorStride,
-                           b->nAnchorVals / b->anchorStride, b->runForm == 1 ? b->runs : NULL, b->runForm == 1 ? b->nRunVals / 4 : 0, totalDiags,
-                           p->diagonalExpansion, dynamic, segs, nSegs, b->symbols, b->nSymbols, b->outTriples, b->nLists,
-                           b->dbgCells, b->dbgDiags, &b->stats.h2dMs);
-    if (rc != CPECAN_OK) goto fail2;
-    b->stats.deviceBytes = cpk_device_bytes(b->dev);
-    b->stats.wavesPerLaunch = cpk_device_waves(b->dev);
-    b->stats.launchForm = cpk_device_form(b->dev);
-    b->frozen = 1;
-    free(diagStart);
-    free(segStart);
-    free(keys);
-    free(plan);
-    return CPECAN_OK;
-
-fail2:
-    cpk_host_free(b->devRegions);
-    cpk_host_free(b->devToHost);
-    b->devRegions = NULL;
-    b->devToHost = NULL;
-    b->segs = NULL;
-    b->nSegs = 0;
-fail1:
-    if (!b->segs) cpk_host_free(segs);
-    free(diagStart);
-    free(segStart);
-    free(keys);
-    free(plan);
+    if (rc == CPECAN_OK) {
+        const int runs = b->runForm == 1;
+        rc = cpk_device_upload(b->dev, &geo, &km, hp.devRegions, runs ? NULL : b->anchors, b->anchorStride,
+                               b->nAnchorVals / b->anchorStride, runs ? b->runs : NULL, runs ? b->nRunVals / 4 : 0, hp.totalDiags,
+                               b->params.diagonalExpansion, hp.dynamic, hp.segs, hp.nSegs, b->symbols, b->nSymbols, hp.outTriples,
+                               b->nLists, hp.dbgCells, hp.dbgDiags, &b->stats.h2dMs);
+    }
+    if (rc == CPECAN_OK) {
+        b->stats.deviceBytes = cpk_device_bytes(b->dev);
+        b->stats.wavesPerLaunch = cpk_device_waves(b->dev);
+        b->stats.launchForm = cpk_device_form(b->dev);
+        host_plan_commit(b, &hp, &geo);
+        b->frozen = 1;
+    }
+    host_plan_free(&hp);
     return rc;
 }
 

@@ -223,6 +223,10 @@ int64_t cpk_device_bytes(const CpkDevice *dev);
 int cpk_device_waves(const CpkDevice *dev);
 void cpk_set_error(const char *fmt, ...);
 int cpk_host_threads(void); /* threads of the host's parallel loops (cpecan_host.c) */
+/* Plans an unfrozen batch as cpecan_batch_upload would, without a device, and returns FNV-1a hashes of the plan: the
+ * CpkRegion array in device order, devToHost, the CpkSegment slots, CpkGeometry with the output and debug totals.  For
+ * tests: the plan is dropped again (cpecan_host.c). */
+int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]);
 
 /* ---- the anchor finder (cpk_anchor.inl; host side in cpecan_anchor.c) ---- */
 /* One problem of an anchor pass: two substrings of the context's symbol buffer.  The host fills the first block, the

@@ -2342,7 +2342,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
                     // The edges of a band that may run under absolute positions move one x-y step per diagonal
                     // (CpkRegion::absOk), so the smallest and the largest x and y of a diagonal never decrease with d: the
                     // window runs from the first cell of the lowest diagonal to the last cell of the highest.  The host sized
-                    // the LDS for the largest window of the class (cpecan_host.c, RegionPlan::winBytes).
+                    // the LDS for the largest window of the class (cpecan_host.c, plan_region: RegionPlan::winBytes).
                     const int dLo = traceRole ? sg.tbPrev + 1 : d;
                     const CpkDiag gl = table[dLo], gh = table[sg.dTop];
                     const int xLoL = (dLo + gl.xmyL) >> 1, xHiL = xLoL + gl.width - 1;

@@ -356,20 +356,35 @@ def test_hmm_loadFromFile_reads_the_reference_trained_hmm_text():
         assert abs(m.emissionGapX[x] - om.gapXEm[x]) < 1e-15 and abs(m.emissionGapY[x] - om.gapYEm[x]) < 1e-15
 
 
+def _plan_digest(b):
+    """cpk_batch_plan_digest (cpecan_internal.h): FNV-1a hashes of the device-order CpkRegion array, devToHost, the
+    CpkSegment slots, and CpkGeometry with outTriples / nDiags / dbgCells / dbgDiags -- planned, hashed and dropped."""
+    f = api.lib().cpk_batch_plan_digest
+    f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    assert f(b._h, out) == 0, api.lib().cpecan_last_error()
+    return tuple(out)
+
+
 def test_planning_is_the_same_for_runs_triples_and_both_band_walks(monkeypatch):
     """Host planning needs no GPU (cpecan_batch_upload plans, then fails for want of a device here): the band cells,
     regions and diagonals of a batch are the same whether the anchors come as runs (cpecan_batch_add_many_runs) or as one
     triple per column, and whether planning walks the runs of diagonal-neighbour anchors in closed form or every diagonal
     (CPECAN_FAST_WALK=0) -- expansions 2 to 10, default and short traceback schedules, split rectangles, anchors from the
-    first column on.  (On the GPU box tests/test_gpu_parity.py compares the lists as well; tools/asan_cpu.sh runs this under
-    AddressSanitizer.)"""
+    first column on, per-anchor expansions (stride 3: never the closed form).  So is the WHOLE plan (_plan_digest: device
+    order, schedule, classes, ring and output sizes, geometry; no field differs between the input forms, none is left out
+    of the hashes), which does not depend on the number of planning threads either; CPECAN_PACKED=0 / =2 take the wide
+    and the packed class paths.  (On the GPU box tests/test_gpu_parity.py compares the lists as well; tools/asan_cpu.sh
+    runs this under AddressSanitizer.)"""
     import random
     from cpecan_amd import workload
     if api.device_count() > 0:
         pytest.skip("a GPU is present: the upload succeeds (covered by the GPU tests)")
     rng = random.Random(5)
+    packed_matters = 0
     for E, seed, kw in ((4, 21, {}), (2, 22, dict(minDiagsBetweenTraceBack=150, traceBackDiagonals=21)),
-                        (10, 23, dict(minDiagsBetweenTraceBack=64, traceBackDiagonals=40)), (6, 24, dict(splitMatrixBiggerThanThis=10 ** 12))):
+                        (10, 23, dict(minDiagsBetweenTraceBack=64, traceBackDiagonals=40)), (6, 24, dict(splitMatrixBiggerThanThis=10 ** 12)),
+                        (4, 25, dict(dynamicAnchorExpansion=True))):
         probs = workload.make_realign_batch(seed, 120, 30, 4000, expansion=E)
         same = "".join(rng.choice("ACGT") for _ in range(3000))
         probs.append((same, same, np.array([(i, i, E) for i in range(len(same))], dtype=np.int64)))
@@ -378,13 +393,28 @@ def test_planning_is_the_same_for_runs_triples_and_both_band_walks(monkeypatch):
         pkw.update(kw)
         p = api.pairwiseAlignmentBandingParameters_construct(**pkw)
         seen = set()
+        digests = {None: set(), "0": set(), "2": set()}
         for runs in (False, True):
             for walk in ("0", "1"):
                 monkeypatch.setenv("CPECAN_FAST_WALK", walk)
                 with api.Batch(api.stateMachine5_construct(), p) as b:
                     (b.add_many_runs if runs else b.add_many)(problems)
+                    for packed in digests:
+                        for threads in ("1", "16"):
+                            monkeypatch.setenv("CPECAN_THREADS", threads)
+                            if packed is None:
+                                monkeypatch.delenv("CPECAN_PACKED", raising=False)
+                            else:
+                                monkeypatch.setenv("CPECAN_PACKED", packed)
+                            digests[packed].add(_plan_digest(b))
+                    monkeypatch.delenv("CPECAN_PACKED", raising=False)
+                    monkeypatch.delenv("CPECAN_THREADS")
                     with pytest.raises(api.CpecanError):
                         b.upload()
                     st = b.stats()
                     seen.add((st.problems, st.regions, st.cells, st.diagonals))
         assert len(seen) == 1 and next(iter(seen))[2] > 0, seen
+        for packed, d in digests.items():  # runs / triples, both walks, 1 / 16 threads: one plan
+            assert len(d) == 1, (E, kw, packed, d)
+        packed_matters += digests["0"] != digests["2"]
+    assert packed_matters > 0  # the two class paths are not the same path

@@ -347,8 +347,8 @@ def test_run_form_anchors_and_closed_form_band_walk(monkeypatch):
     """VERDICT r3 item 4.  (a) cpecan_batch_add_many_runs takes the anchors as (x, y, length, expansion) runs of diagonal
     neighbours -- what cPecanRealign.c:525-529 + pairwiseAligner.c:979-1003 make of a cigar's match operations before they
     are expanded to one anchor per column -- and must give, bit for bit, what cpecan_batch_add_many gives on the expanded
-    anchors.  (b) Planning walks such runs in closed form (cpecan_host.c, "Runs of diagonal neighbours"): with
-    CPECAN_FAST_WALK=0 every diagonal is walked one by one; cell counts, regions, device memory and every list must be
+    anchors.  (b) Planning walks such runs in closed form (cpecan_host.c, plan_region; the skip itself is the
+    iterator's, cpk_band_skip_run in cpecan_band.inl): with CPECAN_FAST_WALK=0 every diagonal is walked one by one; cell counts, regions, device memory and every list must be
     the same -- also where traceback points fall inside runs (short schedules), at matrix edges (anchors from column 0), with
     split rectangles and with expansions 2 to 10.  And the oracle agrees on a sample."""
     from cpecan_amd import workload
