@@ -98,6 +98,23 @@ class AnchorStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class StrandResult(C.Structure):
+    """cpecan_strand_result: the strand of one problem and the chain scores that decided it (-1 = not computed)."""
+    _fields_ = [("strand", C.c_int32), ("scorePlus", C.c_int32), ("scoreMinus", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {"strand": STRAND_NAMES[self.strand], "scorePlus": self.scorePlus, "scoreMinus": self.scoreMinus}
+
+
+STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 0, 1, 2
+STRAND_NAMES = ("plus", "minus", "both")
+
+
+def _strand_mode(strand):
+    """"plus" / "minus" / "both" or a CPECAN_STRAND_* value; anything else goes to the library, which refuses it."""
+    return STRAND_NAMES.index(strand) if strand in STRAND_NAMES else int(strand)
+
+
 # pairwiseAlignmentBandingParameters_construct (impl/pairwiseAligner.c:1340-1342): the fields of the reference's
 # PairwiseAlignmentParameters that only the anchoring reads
 CONSTRAINT_DIAGONAL_TRIM = 14
@@ -131,6 +148,8 @@ EXPORTS = [
     "cpecan_batch_add_many_runs", "cpecan_anchor_runs", "cpecan_anchor_runs_from_alignment",
     "cpecan_batch_set_model",
     "cpecan_anchor_params_default", "cpecan_find_anchor_runs_many", "cpecan_find_anchor_runs", "cpecan_find_anchor_runs_once",
+    "cpecan_reverse_complement", "cpecan_find_anchor_runs_many_stranded", "cpecan_batch_add_many_runs_stranded",
+    "cpecan_batch_problem_strand",
 ]
 OP_MATCH, OP_INDEL_X, OP_INDEL_Y = 0, 1, 2
 POST_REWEIGHT, POST_MEA, POST_LEFT_SHIFT, POST_ORDERED = 1, 2, 4, 8
@@ -227,6 +246,13 @@ def lib():
                                           C.POINTER(AnchorParams), C.POINTER(i64p), i64p, C.POINTER(AnchorStats)]
     L.cpecan_find_anchor_runs_once.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                                C.POINTER(AnchorParams), C.POINTER(i64p), i64p]
+    L.cpecan_reverse_complement.argtypes = [C.c_char_p, C.c_int64, C.c_char_p]
+    L.cpecan_find_anchor_runs_many_stranded.argtypes = [
+        C.POINTER(AnchorProblem), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AnchorParams), C.c_int,
+        C.c_int, C.POINTER(i64p), i64p, C.POINTER(AnchorStats), C.POINTER(StrandResult)]
+    L.cpecan_batch_add_many_runs_stranded.argtypes = [vp, C.POINTER(ProblemRuns), i32p, C.c_int64]
+    L.cpecan_batch_add_many_runs_stranded.restype = C.c_int64
+    L.cpecan_batch_problem_strand.argtypes = [vp, C.c_int64]
     _lib = L
     return L
 
@@ -359,10 +385,60 @@ def anchor_params_default(**overrides):
     return q
 
 
+def reverse_complement(s):
+    """cpecan_reverse_complement: the bytes reversed, A<->T, C<->G in either case, every other byte as it is."""
+    s = _bytes(s)
+    out = C.create_string_buffer(len(s))
+    _check(lib().cpecan_reverse_complement(s, len(s), out), "cpecan_reverse_complement")
+    return out.raw
+
+
+def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
+                                   anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
+                                   repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
+                                   strand="both"):
+    """cpecan_find_anchor_runs_many_stranded on (sX, sY, ...) tuples: ([int64[nRuns, 4] per problem], [statistics dict per
+    problem], [{"strand": "plus" | "minus", "scorePlus", "scoreMinus"} per problem]).  Runs of a minus problem are in the
+    coordinates of (sX, reverse_complement(sY))."""
+    problems = list(problems)
+    n = len(problems)
+    arr = (AnchorProblem * max(1, n))()
+    keep = []
+    for i, pr in enumerate(problems):
+        sx, sy = _bytes(pr[0]), _bytes(pr[1])
+        keep.append((sx, sy))
+        arr[i].sX, arr[i].lX, arr[i].sY, arr[i].lY = sx, len(sx), sy, len(sy)
+    i64p = C.POINTER(C.c_int64)
+    runs = (i64p * max(1, n))()
+    counts = (C.c_int64 * max(1, n))()
+    stats = (AnchorStats * max(1, n))()
+    strands = (StrandResult * max(1, n))()
+    _check(lib().cpecan_find_anchor_runs_many_stranded(arr, n, trim, expansion, anchorMatrixBiggerThanThis,
+                                                       repeatMaskMatrixBiggerThanThis,
+                                                       C.byref(params) if params is not None else None, device,
+                                                       _strand_mode(strand), runs, counts, stats, strands),
+           "cpecan_find_anchor_runs_many_stranded")
+    out = []
+    for i in range(n):
+        c = counts[i]
+        if c:
+            out.append(np.ctypeslib.as_array(runs[i], shape=(c * 4,)).copy().reshape(c, 4))
+        else:
+            out.append(np.zeros((0, 4), dtype=np.int64))
+        if runs[i]:
+            lib().cpecan_free(C.cast(runs[i], C.c_void_p))
+    return out, [stats[i].as_dict() for i in range(n)], [strands[i].as_dict() for i in range(n)]
+
+
 def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
                           anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
-                          repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0):
-    """cpecan_find_anchor_runs_many on (sX, sY, ...) tuples: ([int64[nRuns, 4] per problem], [statistics dict per problem])."""
+                          repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
+                          strand="plus"):
+    """cpecan_find_anchor_runs_many on (sX, sY, ...) tuples: ([int64[nRuns, 4] per problem], [statistics dict per problem]).
+    strand: "plus" (that function), "minus" or "both" (find_anchor_runs_many_stranded without the strand results)."""
+    if _strand_mode(strand) != STRAND_PLUS:
+        return find_anchor_runs_many_stranded(problems, trim, expansion, anchorMatrixBiggerThanThis,
+                                              repeatMaskMatrixBiggerThanThis, params, device, strand)[:2]
     problems = list(problems)
     n = len(problems)
     arr = (AnchorProblem * max(1, n))()
@@ -392,8 +468,14 @@ def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
 
 def find_anchor_runs(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
                      anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
-                     repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None):
-    """cpecan_find_anchor_runs: (int64[nRuns, 4] of (x, y, length, expansion), statistics dict), on the current device."""
+                     repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, strand="plus"):
+    """cpecan_find_anchor_runs: (int64[nRuns, 4] of (x, y, length, expansion), statistics dict), on the current device.
+    strand "minus" / "both": one problem of find_anchor_runs_many_stranded on the current device, same return value."""
+    if _strand_mode(strand) != STRAND_PLUS:
+        runs, stats, _ = find_anchor_runs_many_stranded([(sX, sY)], trim, expansion, anchorMatrixBiggerThanThis,
+                                                        repeatMaskMatrixBiggerThanThis, params,
+                                                        lib().cpecan_current_device(), strand)
+        return runs[0], stats[0]
     sx, sy = _bytes(sX), _bytes(sY)
     runs, cnt, st = C.POINTER(C.c_int64)(), C.c_int64(), AnchorStats()
     _check(lib().cpecan_find_anchor_runs(sx, len(sx), sy, len(sy), trim, expansion, anchorMatrixBiggerThanThis,
@@ -519,14 +601,27 @@ class Batch:
 
     def add_many_unanchored(self, problems, trim=CONSTRAINT_DIAGONAL_TRIM,
                             anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
-                            repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0):
+                            repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
+                            strand="plus"):
         """problems: iterable of (sX, sY[, raggedLeft, raggedRight]) without anchors: the anchors of all of them are found
         in one anchor batch on `device` (the batch's device) with the batch's diagonalExpansion, then the problems are added
-        as runs.  Returns (index of the first, anchor statistics per problem)."""
+        as runs.  Returns (index of the first, anchor statistics per problem).  strand "minus" / "both": a problem on the
+        minus strand is added as (sX, reverse complement of sY) -- the batch makes the reverse complement itself -- and its
+        results are in those coordinates; the statistics then carry "strand", "scorePlus" and "scoreMinus" as well, and
+        problem_strand(i) reads the strand back."""
         problems = list(problems)
-        runs, stats = find_anchor_runs_many(problems, trim, self._p.diagonalExpansion, anchorMatrixBiggerThanThis,
-                                            repeatMaskMatrixBiggerThanThis, params, device)
-        arr = (ProblemRuns * max(1, len(problems)))()
+        n = len(problems)
+        stranded = _strand_mode(strand) != STRAND_PLUS
+        if stranded:
+            runs, stats, strands = find_anchor_runs_many_stranded(problems, trim, self._p.diagonalExpansion,
+                                                                  anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis,
+                                                                  params, device, strand)
+            for st, sr in zip(stats, strands):
+                st.update(sr)
+        else:
+            runs, stats = find_anchor_runs_many(problems, trim, self._p.diagonalExpansion, anchorMatrixBiggerThanThis,
+                                                repeatMaskMatrixBiggerThanThis, params, device)
+        arr = (ProblemRuns * max(1, n))()
         keep = []
         for i, pr in enumerate(problems):
             sx, sy = _bytes(pr[0]), _bytes(pr[1])
@@ -535,7 +630,16 @@ class Batch:
             arr[i].runs, arr[i].nRuns = runs[i].ctypes.data_as(C.POINTER(C.c_int64)), runs[i].shape[0]
             arr[i].raggedLeft = int(pr[2]) if len(pr) > 2 else 0
             arr[i].raggedRight = int(pr[3]) if len(pr) > 3 else 0
-        return self.add_prepared(arr, len(problems)), stats
+        if not stranded:
+            return self.add_prepared(arr, n), stats
+        minus = (C.c_int32 * max(1, n))(*[int(sr["strand"] == "minus") for sr in strands])
+        first = _check(lib().cpecan_batch_add_many_runs_stranded(self._h, arr, minus, n), "cpecan_batch_add_many_runs_stranded")
+        self.n += n
+        return first, stats
+
+    def problem_strand(self, problem):
+        """cpecan_batch_problem_strand: "plus" or "minus" as the problem was added."""
+        return STRAND_NAMES[_check(lib().cpecan_batch_problem_strand(self._h, problem), "cpecan_batch_problem_strand")]
 
     def add_many(self, problems):
         """problems: iterable of (sX, sY, anchorPairs[, raggedLeft, raggedRight]); cut, converted and copied in parallel
@@ -650,6 +754,26 @@ def getAlignedPairs(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHas
     anchorParams."""
     anchors = getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, **anchoring)
     return getAlignedPairsUsingAnchors(sM, sX, sY, anchors, p, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd)
+
+
+def getAlignedPairsStranded(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False, strand="both",
+                            constraintDiagonalTrim=CONSTRAINT_DIAGONAL_TRIM,
+                            anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
+                            repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, anchorParams=None):
+    """getAlignedPairs for a query that may lie on the other strand (the step cPecanAlign.c:116-117 leaves open):
+    (pairs, "plus" | "minus", (scorePlus, scoreMinus)).  The pairs of a minus result are those of
+    getAlignedPairs(sM, sX, reverse_complement(sY), ...): y there is position len(sY) - 1 - y of sY."""
+    device = lib().cpecan_current_device()
+    with Batch(sM, p, EMIT_MATCH, device) as b:
+        _, stats = b.add_many_unanchored([(sX, sY, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd)],
+                                         constraintDiagonalTrim, anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis,
+                                         anchorParams, device, strand)
+        chosen = b.problem_strand(0)
+        b.upload()
+        b.run()
+        b.download()
+        pairs = b.result(0).copy()
+    return pairs, chosen, (stats[0].get("scorePlus", -1), stats[0].get("scoreMinus", -1))
 
 
 def getAlignedPairsWithIndels(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False, **anchoring):

@@ -2,8 +2,10 @@
  * cpecan_align -- command line of cPecanAlign (cPecanAlign.c:91-164): every query sequence against every target
  * sequence, five-state default model, getAlignedPairs with both ends ragged, reweightAlignedPairs2 with gapGamma, ordered
  * filter at 0.9, one cigar per pair on stdout.  Unlike the reference's loop, the anchors of all pairs are found in one
- * anchor batch (cpecan_find_anchor_runs_many) and all pairs are aligned in one DP batch.  Output order: queries in file
- * order, for each the targets in file order (the reference iterates hash tables, so it defines no order).
+ * anchor batch (cpecan_find_anchor_runs_many_stranded) and all pairs are aligned in one DP batch.  Output order: queries in
+ * file order, for each the targets in file order (the reference iterates hash tables, so it defines no order).
+ * --strand both does what the reference leaves open at cPecanAlign.c:116-117: every pair is tried against the query and
+ * its reverse complement, and a pair on the minus strand gets a cigar with "<length> 0 -" for the query.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -26,7 +28,7 @@ typedef struct {
 
 static void usage(void) {
     fprintf(stderr, "cpecan_align [options] target.fa query.fa > cigars\n"
-                    "-y --loadHmm FILE  -g --device N  -h --help\n");
+                    "-y --loadHmm FILE  -g --device N  -s --strand plus|minus|both (default plus)  -h --help\n");
 }
 
 static int fail(const char *what) {
@@ -98,15 +100,23 @@ static int by_x(const void *a, const void *b) {
 int main(int argc, char **argv) {
     const char *hmmFile = NULL;
     long long device = 0;
+    int strandMode = CPECAN_STRAND_PLUS;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
+                                       {"strand", required_argument, 0, 's'},
                                        {0, 0, 0, 0}};
-    for (int key; (key = getopt_long(argc, argv, "hy:g:", longOpts, NULL)) != -1;) {
+    for (int key; (key = getopt_long(argc, argv, "hy:g:s:", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
         case 'y': hmmFile = optarg; break;
         case 'g': if (sscanf(optarg, "%lld", &device) != 1) { usage(); return 1; } break;
+        case 's':
+            if (strcmp(optarg, "plus") == 0) strandMode = CPECAN_STRAND_PLUS;
+            else if (strcmp(optarg, "minus") == 0) strandMode = CPECAN_STRAND_MINUS;
+            else if (strcmp(optarg, "both") == 0) strandMode = CPECAN_STRAND_BOTH;
+            else { usage(); return 1; }
+            break;
         default: usage(); return 1;
         }
     }
@@ -139,8 +149,10 @@ int main(int argc, char **argv) {
     cpecan_anchor_problem *ap = calloc((size_t)(n ? n : 1), sizeof *ap);
     cpecan_problem_runs *pr = calloc((size_t)(n ? n : 1), sizeof *pr);
     int64_t **runs = calloc((size_t)(n ? n : 1), sizeof *runs), *nRuns = calloc((size_t)(n ? n : 1), sizeof *nRuns);
+    cpecan_strand_result *strands = calloc((size_t)(n ? n : 1), sizeof *strands);
+    int32_t *yMinus = calloc((size_t)(n ? n : 1), sizeof *yMinus);
     cpecan_batch *b = NULL;
-    if (!ap || !pr || !runs || !nRuns) status = 1;
+    if (!ap || !pr || !runs || !nRuns || !strands || !yMinus) status = 1;
     for (int64_t q = 0, i = 0; status == 0 && q < queries.n; q++) /* :110-114 */
         for (int64_t t = 0; t < targets.n; t++, i++) {
             ap[i].sX = targets.r[t].seq; /* :123: the target is X */
@@ -149,8 +161,8 @@ int main(int argc, char **argv) {
             ap[i].lY = queries.r[q].length;
         }
     if (status == 0 && n > 0) {
-        if (cpecan_find_anchor_runs_many(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix, NULL, (int)device,
-                                         runs, nRuns, NULL) != CPECAN_OK)
+        if (cpecan_find_anchor_runs_many_stranded(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix, NULL,
+                                                  (int)device, strandMode, runs, nRuns, NULL, strands) != CPECAN_OK)
             status = fail("anchors");
     }
     if (status == 0 && n > 0) {
@@ -162,12 +174,13 @@ int main(int argc, char **argv) {
             pr[i].runs = runs[i];
             pr[i].nRuns = nRuns[i];
             pr[i].raggedLeft = pr[i].raggedRight = 1; /* :125 */
+            yMinus[i] = strands[i].strand == CPECAN_STRAND_MINUS;
         }
         if (cpecan_batch_create(&b, &model, &params, CPECAN_EMIT_MATCH, (int)device) != CPECAN_OK) status = fail("batch");
         else if (cpecan_batch_set_post(b, CPECAN_POST_REWEIGHT | CPECAN_POST_ORDERED, gapGamma) != CPECAN_OK ||
                  cpecan_batch_set_match_gamma(b, 0.9f) != CPECAN_OK) /* :129-139 */
             status = fail("consumers");
-        else if (cpecan_batch_add_many_runs(b, pr, n) < 0) status = fail("add");
+        else if (cpecan_batch_add_many_runs_stranded(b, pr, yMinus, n) < 0) status = fail("add");
         else if (cpecan_batch_upload(b) != CPECAN_OK) status = fail("upload");
         else if (cpecan_batch_run(b, NULL) != CPECAN_OK) status = fail("run");
         else if (cpecan_batch_download(b) != CPECAN_OK) status = fail("download");
@@ -193,8 +206,8 @@ int main(int argc, char **argv) {
         qsort(xy, (size_t)cnt, sizeof *xy * 2, by_x);
         cpecan_cigar c;
         memset(&c, 0, sizeof c);
-        if (cpecan_cigar_from_aligned_pairs(targets.r[i % targets.n].name, queries.r[i / targets.n].name, 0.0, ap[i].lX, ap[i].lY, xy,
-                                            cnt, &c) != CPECAN_OK) {
+        if (cpecan_cigar_from_aligned_pairs_stranded(targets.r[i % targets.n].name, queries.r[i / targets.n].name, 0.0, ap[i].lX,
+                                                     ap[i].lY, !yMinus[i], xy, cnt, &c) != CPECAN_OK) {
             status = fail("cigar");
         } else {
             const int64_t need = cpecan_cigar_format(&c, NULL, 0) + 1;
@@ -222,6 +235,8 @@ int main(int argc, char **argv) {
     free(nRuns);
     free(ap);
     free(pr);
+    free(strands);
+    free(yMinus);
     free_records(&targets);
     free_records(&queries);
     return status;

@@ -1,8 +1,11 @@
 /*
- * cpecan_anchor.c -- host side of the anchor finder (include/cpecan_hip.h: cpecan_find_anchor_runs_many).
+ * cpecan_anchor.c -- host side of the anchor finder (include/cpecan_hip.h: cpecan_find_anchor_runs_many_stranded).
  * The kernels (cpk_anchor.inl) do steps 1-5 on a list of problems; this file lays the sequences of a call out in one
  * buffer, runs the top-level pass, makes the second pass's problems out of the gaps between the top-level anchors
  * (getBlastPairsForPairwiseAlignmentParameters, impl/pairwiseAligner.c:1175-1191) and splices the runs together.
+ * Strand: a problem that may lie on the minus strand gets a twin in the top-level pass whose
+ * Y is the reverse complement, written on the device behind the forward symbols; the chain scores of the two decide, and
+ * only the chosen orientation goes on to the gaps and the splice.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -31,12 +34,30 @@ typedef struct {
 
 static int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
 
-int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
-                                 int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
-                                 const cpecan_anchor_params *params, int device, int64_t **runs, int64_t *nRuns,
-                                 cpecan_anchor_stats *stats) {
-    if (n < 0 || (n > 0 && (!problems || !runs || !nRuns)) || trim < 0 || trim > (1 << 24)) {
-        cpk_set_error("cpecan_find_anchor_runs_many: bad arguments");
+int cpecan_reverse_complement(const char *s, int64_t l, char *out) {
+    if (l < 0 || (l > 0 && (!s || !out))) return CPECAN_EINVAL;
+    static const char from[] = "ACGTacgt", to[] = "TGCAtgca";
+    for (int64_t i = 0, j = l - 1; i <= j; i++, j--) { /* from both ends inwards: out may be s */
+        unsigned char a = (unsigned char)s[i], b = (unsigned char)s[j];
+        const char *fa = a ? strchr(from, a) : NULL, *fb = b ? strchr(from, b) : NULL;
+        if (fa) a = (unsigned char)to[fa - from];
+        if (fb) b = (unsigned char)to[fb - from];
+        out[i] = (char)b;
+        out[j] = (char)a;
+    }
+    return CPECAN_OK;
+}
+
+/* The finder behind every entry point.  once: steps 1-5 alone on every problem whatever its size, soft masking as
+ * softMaskTop says, no recursion (cpecan_find_anchor_runs_once); otherwise the top level masks (:1168).  who: the entry
+ * point, for the error texts. */
+static int find_runs(const char *who, const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                     int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis, const cpecan_anchor_params *params,
+                     int device, int strandMode, int once, int softMaskTop, int64_t **runs, int64_t *nRuns, cpecan_anchor_stats *stats,
+                     cpecan_strand_result *strands) {
+    if (n < 0 || (n > 0 && (!problems || !runs || !nRuns)) || trim < 0 || trim > (1 << 24) || strandMode < CPECAN_STRAND_PLUS ||
+        strandMode > CPECAN_STRAND_BOTH) {
+        cpk_set_error("%s: bad arguments", who);
         return CPECAN_EINVAL;
     }
     cpecan_anchor_params def;
@@ -45,7 +66,7 @@ int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t 
         params = &def;
     }
     if (memchr(params->seed, 0, sizeof params->seed) == NULL) {
-        cpk_set_error("cpecan_find_anchor_runs_many: the seed is not terminated");
+        cpk_set_error("%s: the seed is not terminated", who);
         return CPECAN_EINVAL;
     }
     for (int64_t i = 0; i < n; i++) {
@@ -55,10 +76,14 @@ int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t 
     for (int64_t i = 0; i < n; i++)
         if (problems[i].lX < 0 || problems[i].lY < 0 || (problems[i].lX > 0 && !problems[i].sX) ||
             (problems[i].lY > 0 && !problems[i].sY) || problems[i].lX > (1 << 24) || problems[i].lY > (1 << 24)) {
-            cpk_set_error("cpecan_find_anchor_runs_many: problem %lld has no sequence or one longer than 2^24", (long long)i);
+            cpk_set_error("%s: problem %lld has no sequence or one longer than 2^24", who, (long long)i);
             return CPECAN_EINVAL;
         }
     if (stats) memset(stats, 0, sizeof *stats * (size_t)n);
+    for (int64_t i = 0; strands && i < n; i++) { /* what holds without a pass: forced, or plus; nothing scored */
+        strands[i].strand = strandMode == CPECAN_STRAND_MINUS ? CPECAN_STRAND_MINUS : CPECAN_STRAND_PLUS;
+        strands[i].scorePlus = strands[i].scoreMinus = -1;
+    }
     const int nDev = cpk_device_count();
     if (nDev <= 0 || device < 0 || device >= nDev) {
         cpk_set_error("no usable HIP device (count=%d, requested=%d): the HIP path has no CPU fallback", nDev, device);
@@ -71,13 +96,16 @@ int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t 
     prm.hspThreshold = params->hspThreshold;
     prm.maxHsps = params->maxHsps;
 
-    /* the problems beyond the size limit, their sequences end to end in one buffer */
+    /* The top-level problems, their sequences end to end in one buffer: those beyond the size limit and, with BOTH, the
+     * others too, for their strand score.  A problem scored on both strands is a pair of twins, plus then minus; the
+     * reverse complements get even offsets in an area behind the sequences. */
+    const int both = strandMode == CPECAN_STRAND_BOTH, twins = both ? 2 : 1;
     int rc = CPECAN_ENOMEM;
-    int64_t nTop = 0, nBytes = 0, nGaps = 0, capGaps = 0, g = 0;
+    int64_t nTop = 0, nBytes = 0, nExtra = 0, nGaps = 0, capGaps = 0, g = 0;
     double ms = 0.0;
     CpkAnchorCtx *ctx = NULL;
-    CpkAnchorProblem *top = malloc(sizeof *top * (size_t)(n ? n : 1)), *sub = NULL;
-    int64_t *owner = malloc(sizeof *owner * (size_t)(n ? n : 1));
+    CpkAnchorProblem *top = malloc(sizeof *top * (size_t)(n ? twins * n : 1)), *sub = NULL;
+    int64_t *owner = malloc(sizeof *owner * (size_t)(n ? twins * n : 1));
     uint8_t *bytes = NULL;
     int32_t *topRuns = NULL, *subRuns = NULL;
     Gap *gaps = NULL;
@@ -85,34 +113,75 @@ int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t 
     for (int64_t i = 0; i < n; i++) {
         const cpecan_anchor_problem *q = &problems[i];
         if (stats) stats[i].largestGapTop = stats[i].largestGap = q->lX * q->lY;
-        if (q->lX * q->lY <= anchorMatrixBiggerThanThis || q->lX == 0 || q->lY == 0) continue;
-        CpkAnchorProblem *t = &top[nTop];
-        memset(t, 0, sizeof *t);
-        t->xOff = nBytes;
-        t->yOff = nBytes + q->lX;
-        t->lX = (int32_t)q->lX;
-        t->lY = (int32_t)q->lY;
-        t->softMask = 1; /* :1168 */
-        owner[nTop++] = i;
+        if (q->lX == 0 || q->lY == 0) { /* :1012; no HSP on either strand */
+            if (strands && both) strands[i].scorePlus = strands[i].scoreMinus = 0;
+            continue;
+        }
+        if (!once && !both && q->lX * q->lY <= anchorMatrixBiggerThanThis) continue;
+        for (int t = 0; t < twins; t++) {
+            const int minus = both ? t : strandMode == CPECAN_STRAND_MINUS;
+            CpkAnchorProblem *p = &top[nTop];
+            memset(p, 0, sizeof *p);
+            p->xOff = nBytes;
+            p->yOff = nBytes + q->lX;
+            p->lX = (int32_t)q->lX;
+            p->lY = (int32_t)q->lY;
+            p->softMask = once ? softMaskTop != 0 : 1; /* :1168 */
+            if (minus) {
+                p->flags = CPK_ANCHOR_RC_Y | (t ? CPK_ANCHOR_SHARE_X : 0);
+                p->yFwd = p->yOff;
+                p->yOff = -1 - nExtra; /* its place in the area, known once nBytes is */
+                nExtra += (q->lY + 1) & ~(int64_t)1;
+            }
+            owner[nTop++] = i;
+        }
         nBytes += q->lX + q->lY;
     }
     if (nTop == 0) {
         rc = CPECAN_OK;
         goto done;
     }
+    for (int64_t k = 0; k < nTop; k++)
+        if (top[k].flags & CPK_ANCHOR_RC_Y) top[k].yOff = ((nBytes + 1) & ~(int64_t)1) + (-1 - top[k].yOff);
     bytes = malloc((size_t)nBytes);
     if (!bytes) goto done;
     for (int64_t k = 0; k < nTop; k++) {
+        if (top[k].flags & CPK_ANCHOR_SHARE_X) continue;
         const cpecan_anchor_problem *q = &problems[owner[k]];
         memcpy(bytes + top[k].xOff, q->sX, (size_t)q->lX);
-        memcpy(bytes + top[k].yOff, q->sY, (size_t)q->lY);
+        memcpy(bytes + top[k].xOff + q->lX, q->sY, (size_t)q->lY);
     }
-    if ((rc = cpk_anchor_open(&ctx, device, bytes, nBytes)) != CPECAN_OK) goto done;
+    if ((rc = cpk_anchor_open(&ctx, device, bytes, nBytes, nExtra)) != CPECAN_OK) goto done;
     if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, top, nTop, (int32_t)trim, &topRuns, &ms)) != CPECAN_OK) goto done;
+
+    /* The strand of every problem; what does not go on is dropped from the list: the twin that lost and, with BOTH, the
+     * problems at or under the size limit, which were there to be scored. */
+    {
+        int64_t kept = 0;
+        for (int64_t k = 0; k < nTop; k += twins) {
+            const int64_t i = owner[k];
+            int64_t pick = k;
+            if (both) {
+                const int minus = top[k + 1].score > top[k].score; /* a tie, 0 = 0 included, is plus */
+                pick = k + minus;
+                if (strands) {
+                    strands[i].strand = minus ? CPECAN_STRAND_MINUS : CPECAN_STRAND_PLUS;
+                    strands[i].scorePlus = top[k].score;
+                    strands[i].scoreMinus = top[k + 1].score;
+                }
+            } else if (strands) {
+                *(strandMode == CPECAN_STRAND_MINUS ? &strands[i].scoreMinus : &strands[i].scorePlus) = top[k].score;
+            }
+            if (!once && problems[i].lX * problems[i].lY <= anchorMatrixBiggerThanThis) continue;
+            top[kept] = top[pick];
+            owner[kept++] = i;
+        }
+        nTop = kept;
+    }
 
     /* the gaps between consecutive top-level anchors that are still too large: the second pass (:1175-1191) */
     rc = CPECAN_ENOMEM;
-    for (int64_t k = 0; k < nTop; k++) {
+    for (int64_t k = 0; k < nTop && !once; k++) {
         const int32_t *r = topRuns + 3 * top[k].hspOff;
         int64_t pX = 0, pY = 0, largest = 0;
         for (int64_t j = 0; j <= top[k].nRuns; j++) {
@@ -215,7 +284,7 @@ int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t 
         for (int64_t i = 0; i < n; i++) stats[i].kernelMs = ms;
     rc = CPECAN_OK;
 done:
-    if (rc == CPECAN_ENOMEM) cpk_set_error("cpecan_find_anchor_runs_many: out of memory");
+    if (rc == CPECAN_ENOMEM) cpk_set_error("%s: out of memory", who);
     if (rc != CPECAN_OK)
         for (int64_t i = 0; i < n; i++) {
             free(runs[i]);
@@ -233,6 +302,22 @@ done:
     return rc;
 }
 
+int cpecan_find_anchor_runs_many_stranded(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                          int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                                          const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
+                                          int64_t *nRuns, cpecan_anchor_stats *stats, cpecan_strand_result *strands) {
+    return find_runs("cpecan_find_anchor_runs_many_stranded", problems, n, trim, expansion, anchorMatrixBiggerThanThis,
+                     repeatMaskMatrixBiggerThanThis, params, device, strandMode, 0, 1, runs, nRuns, stats, strands);
+}
+
+int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                 int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                                 const cpecan_anchor_params *params, int device, int64_t **runs, int64_t *nRuns,
+                                 cpecan_anchor_stats *stats) {
+    return find_runs("cpecan_find_anchor_runs_many", problems, n, trim, expansion, anchorMatrixBiggerThanThis,
+                     repeatMaskMatrixBiggerThanThis, params, device, CPECAN_STRAND_PLUS, 0, 1, runs, nRuns, stats, NULL);
+}
+
 int cpecan_find_anchor_runs(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
                             int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
                             const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns, cpecan_anchor_stats *stats) {
@@ -244,67 +329,11 @@ int cpecan_find_anchor_runs(const char *sX, int64_t lX, const char *sY, int64_t 
 
 int cpecan_find_anchor_runs_once(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
                                  int softMask, const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns) {
-    if (!runs || !nRuns || lX < 0 || lY < 0 || (lX > 0 && !sX) || (lY > 0 && !sY) || lX > (1 << 24) || lY > (1 << 24) || trim < 0 ||
-        trim > (1 << 24)) {
+    if (!runs || !nRuns) {
         cpk_set_error("cpecan_find_anchor_runs_once: bad arguments");
         return CPECAN_EINVAL;
     }
-    *runs = NULL;
-    *nRuns = 0;
-    cpecan_anchor_params def;
-    if (!params) {
-        cpecan_anchor_params_default(&def);
-        params = &def;
-    }
-    if (memchr(params->seed, 0, sizeof params->seed) == NULL) {
-        cpk_set_error("cpecan_find_anchor_runs_once: the seed is not terminated");
-        return CPECAN_EINVAL;
-    }
-    if (cpk_device_count() <= 0) {
-        cpk_set_error("no usable HIP device: the HIP path has no CPU fallback");
-        return CPECAN_ENODEVICE;
-    }
-    if (lX == 0 || lY == 0) return CPECAN_OK; /* :1012 */
-    CpkAnchorParams prm;
-    memcpy(prm.scores, params->scores, sizeof prm.scores);
-    prm.maxSeedOccurrences = params->maxSeedOccurrences;
-    prm.xDrop = params->xDrop;
-    prm.hspThreshold = params->hspThreshold;
-    prm.maxHsps = params->maxHsps;
-    uint8_t *bytes = malloc((size_t)(lX + lY));
-    if (!bytes) {
-        cpk_set_error("cpecan_find_anchor_runs_once: out of memory");
-        return CPECAN_ENOMEM;
-    }
-    memcpy(bytes, sX, (size_t)lX);
-    memcpy(bytes + lX, sY, (size_t)lY);
-    CpkAnchorProblem t;
-    memset(&t, 0, sizeof t);
-    t.yOff = lX;
-    t.lX = (int32_t)lX;
-    t.lY = (int32_t)lY;
-    t.softMask = softMask != 0;
-    CpkAnchorCtx *ctx = NULL;
-    int32_t *found = NULL;
-    double ms = 0.0;
-    int rc = cpk_anchor_open(&ctx, cpk_current_device(), bytes, lX + lY);
-    if (rc == CPECAN_OK) rc = cpk_anchor_pass(ctx, &prm, params->seed, &t, 1, (int32_t)trim, &found, &ms);
-    if (rc == CPECAN_OK) {
-        int64_t *out = malloc(sizeof *out * 4 * (size_t)(t.nRuns ? t.nRuns : 1));
-        if (!out) {
-            cpk_set_error("cpecan_find_anchor_runs_once: out of memory");
-            rc = CPECAN_ENOMEM;
-        } else {
-            for (int64_t j = 0; j < t.nRuns; j++) {
-                for (int f = 0; f < 3; f++) out[4 * j + f] = found[3 * (t.hspOff + j) + f];
-                out[4 * j + 3] = expansion;
-            }
-            *runs = out;
-            *nRuns = t.nRuns;
-        }
-    }
-    cpk_anchor_close(ctx);
-    free(found);
-    free(bytes);
-    return rc;
+    const cpecan_anchor_problem q = {sX, lX, sY, lY};
+    return find_runs("cpecan_find_anchor_runs_once", &q, 1, trim, expansion, 0, 0, params, cpk_current_device(), CPECAN_STRAND_PLUS,
+                     1, softMask, runs, nRuns, NULL, NULL);
 }

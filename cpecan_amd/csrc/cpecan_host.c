@@ -402,6 +402,7 @@ typedef struct {
     int64_t nTriples[4];
     int64_t lX, lY;          /* of the whole problem */
     int64_t charX, charY;    /* raw upper-case sequences in cpecan_batch.chars */
+    int32_t minus;           /* Y was added reverse-complemented (cpecan_batch_add_many_runs_stranded) */
     double scores[CPK_POST_SCORES]; /* byPosterior, byPosteriorIgnoringGaps, MEA alignment score, byIdentity, ...IgnoringGaps */
 } HostProblem;
 
@@ -730,6 +731,18 @@ static int64_t put_symbols(uint8_t *dst, int64_t at, const char *s, int64_t l) {
     return at + l + 2;
 }
 
+/* The reversed twin of put_symbols: the l symbols that END at s[end - 1], complemented, last first -- bases a .. a + l - 1
+ * of the reverse complement of a sequence of length lY when end = lY - a. */
+static int64_t put_symbols_rc(uint8_t *dst, int64_t at, const char *s, int64_t end, int64_t l) {
+    dst[at] = CPK_SYM_N;
+    for (int64_t i = 0; i < l; i++) {
+        const uint8_t c = g_symbolOf[(unsigned char)s[end - 1 - i]];
+        dst[at + 1 + i] = c < 4 ? (uint8_t)(3 - c) : c;
+    }
+    dst[at + l + 1] = CPK_SYM_N;
+    return at + l + 2;
+}
+
 /* What one problem adds to the batch's arrays; filled by the counting pass of cpecan_batch_add_many. */
 typedef struct {
     int64_t nRects, symbolBytes, nAnchorsKept, nRunsKept;
@@ -746,6 +759,7 @@ typedef struct {
     int64_t nAnchors; /* entries: anchors or runs */
     int32_t raggedLeft, raggedRight;
     int runs;
+    int minus; /* anchors and results are in the coordinates of (X, rc(sY)) */
 } ProblemView;
 
 /* getSplitPoints over runs: between two anchors of a run the gap is empty (0 x 0 cells), so only the gaps in front of a
@@ -823,19 +837,19 @@ static int problem_valid(const ProblemView *it) {
 }
 
 /* problem i of an add call in either form (the two public structs differ in what their anchor arrays hold) */
-static ProblemView view_of(const void *items, int runs, int64_t i) {
+static ProblemView view_of(const void *items, int runs, const int32_t *yMinus, int64_t i) {
     ProblemView v;
     if (runs) {
         const cpecan_problem_runs *p = (const cpecan_problem_runs *)items + i;
-        v = (ProblemView){p->sX, p->lX, p->sY, p->lY, p->runs, p->nRuns, p->raggedLeft, p->raggedRight, 1};
+        v = (ProblemView){p->sX, p->lX, p->sY, p->lY, p->runs, p->nRuns, p->raggedLeft, p->raggedRight, 1, yMinus && yMinus[i]};
     } else {
         const cpecan_problem *p = (const cpecan_problem *)items + i;
-        v = (ProblemView){p->sX, p->lX, p->sY, p->lY, p->anchors, p->nAnchors, p->raggedLeft, p->raggedRight, 0};
+        v = (ProblemView){p->sX, p->lX, p->sY, p->lY, p->anchors, p->nAnchors, p->raggedLeft, p->raggedRight, 0, 0};
     }
     return v;
 }
 
-static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n) {
+static int64_t add_many(cpecan_batch *b, const void *items, int runs, const int32_t *yMinus, int64_t n) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || b->frozen) return CPECAN_ESTATE;
     if (n < 0 || (n > 0 && !items)) return CPECAN_EINVAL;
@@ -860,7 +874,7 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n)
         int64_t *rects = NULL, cap = 0;
 #pragma omp for schedule(dynamic, 32)
         for (int64_t i = 0; i < n; i++) {
-            const ProblemView view = view_of(items, runs, i), *it = &view;
+            const ProblemView view = view_of(items, runs, yMinus, i), *it = &view;
             int64_t nRects = problem_valid(it) ? problem_rects(b, it, &rects, &cap) : CPECAN_EINVAL;
             if (nRects < 0) {
 #pragma omp critical(cpk_add)
@@ -915,7 +929,7 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n)
         nRegions += cnt[i].nRects;
         nSymbols += cnt[i].symbolBytes;
         nAnchorVals += b->anchorStride * cnt[i].nAnchorsKept;
-        const ProblemView view = view_of(items, runs, i);
+        const ProblemView view = view_of(items, runs, yMinus, i);
         nChars += view.lX + view.lY;
     }
     if (grow((void **)&b->problems, &b->capProblems, b->nProblems + n, sizeof(HostProblem)) ||
@@ -937,7 +951,7 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n)
         int64_t *rects = NULL, cap = 0;
 #pragma omp for schedule(dynamic, 32)
         for (int64_t i = 0; i < n; i++) {
-            const ProblemView view = view_of(items, runs, i), *it = &view;
+            const ProblemView view = view_of(items, runs, yMinus, i), *it = &view;
             const int64_t nRects = problem_rects(b, it, &rects, &cap);
             if (nRects != cnt[i].nRects) { /* only an allocation failure can change the answer */
 #pragma omp atomic write
@@ -954,7 +968,17 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n)
             pr->charX = offs[4 * i + 3];
             for (int64_t k = 0; k < it->lX; k++) ch[k] = g_upperOf[(unsigned char)it->sX[k]];
             pr->charY = pr->charX + it->lX;
-            for (int64_t k = 0; k < it->lY; k++) ch[it->lX + k] = g_upperOf[(unsigned char)it->sY[k]];
+            pr->minus = it->minus;
+            if (it->minus) {
+                static const char from[] = "ACGT", to[] = "TGCA";
+                for (int64_t k = 0; k < it->lY; k++) {
+                    const uint8_t c = g_upperOf[(unsigned char)it->sY[it->lY - 1 - k]];
+                    const char *f = c ? strchr(from, c) : NULL;
+                    ch[it->lX + k] = f ? (uint8_t)to[f - from] : c;
+                }
+            } else {
+                for (int64_t k = 0; k < it->lY; k++) ch[it->lX + k] = g_upperOf[(unsigned char)it->sY[k]];
+            }
             int64_t next = 0, symAt = offs[4 * i + 1], anchorAt = offs[4 * i + 2]; /* anchors go to regions in order, :1296-1308 */
             int64_t runValAt = keepRuns ? runAt[i] : 0;
             for (int64_t k = 0; k < nRects; k++) {
@@ -971,7 +995,8 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n)
                 r->seqXOff = symAt;
                 symAt = put_symbols(b->symbols, symAt, it->sX + x1, r->lX);
                 r->seqYOff = symAt;
-                symAt = put_symbols(b->symbols, symAt, it->sY + y1, r->lY);
+                symAt = it->minus ? put_symbols_rc(b->symbols, symAt, it->sY, it->lY - y1, r->lY)
+                                  : put_symbols(b->symbols, symAt, it->sY + y1, r->lY);
                 r->anchorOff = anchorAt / b->anchorStride;
                 if (keepRuns) { /* the runs stay runs: 16 bytes each, whatever their length */
                     r->runOff = runValAt / 4;
@@ -1041,8 +1066,16 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, int64_t n)
     return firstProblem;
 }
 
-int64_t cpecan_batch_add_many(cpecan_batch *b, const cpecan_problem *items, int64_t n) { return add_many(b, items, 0, n); }
-int64_t cpecan_batch_add_many_runs(cpecan_batch *b, const cpecan_problem_runs *items, int64_t n) { return add_many(b, items, 1, n); }
+int64_t cpecan_batch_add_many(cpecan_batch *b, const cpecan_problem *items, int64_t n) { return add_many(b, items, 0, NULL, n); }
+int64_t cpecan_batch_add_many_runs(cpecan_batch *b, const cpecan_problem_runs *items, int64_t n) { return add_many(b, items, 1, NULL, n); }
+int64_t cpecan_batch_add_many_runs_stranded(cpecan_batch *b, const cpecan_problem_runs *items, const int32_t *yMinus, int64_t n) {
+    return add_many(b, items, 1, yMinus, n);
+}
+
+int cpecan_batch_problem_strand(const cpecan_batch *b, int64_t problem) {
+    if (!b || problem < 0 || problem >= b->nProblems) return CPECAN_EINVAL;
+    return b->problems[problem].minus ? CPECAN_STRAND_MINUS : CPECAN_STRAND_PLUS;
+}
 
 int64_t cpecan_anchor_runs(const int64_t *anchors, int64_t nAnchors, int64_t *out, int64_t cap) {
     if (nAnchors < 0 || cap < 0 || (nAnchors > 0 && !anchors) || (cap > 0 && !out)) return CPECAN_EINVAL;

@@ -230,7 +230,13 @@ int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]);
 
 /* ---- the anchor finder (cpk_anchor.inl; host side in cpecan_anchor.c) ---- */
 /* One problem of an anchor pass: two substrings of the context's symbol buffer.  The host fills the first block, the
- * device layer sizes the lists (second block) and the kernels leave the counts (third block). */
+ * device layer sizes the lists (second block) and the kernels leave the counts (third block).
+ * flags: CPK_ANCHOR_RC_Y -- the pass first writes the reverse complement of the lY symbols at yFwd (forward symbols of the
+ * buffer) to yOff, which is even and lies in the area cpk_anchor_open reserved behind them; CPK_ANCHOR_SHARE_X -- the
+ * minus twin of the problem in front of it in the list: same xOff and lX, and it reads that problem's sorted X keys
+ * instead of making its own. */
+#define CPK_ANCHOR_RC_Y 1
+#define CPK_ANCHOR_SHARE_X 2
 typedef struct {
     int64_t xOff, yOff; /* first symbol of X / Y in the context's buffer */
     int32_t lX, lY;
@@ -238,8 +244,11 @@ typedef struct {
     int32_t capX, capY; /* key slots: the window counts rounded up to a power of two */
     int32_t hspCap;     /* HSP slots: the hit count rounded up to a power of two */
     int64_t keyXOff, keyYOff, hspOff;
-    int32_t hits, hsps, chained, nRuns, capped, pad;
+    int32_t hits, hsps, chained, nRuns, capped, flags;
     int64_t columns;
+    int64_t yFwd;  /* CPK_ANCHOR_RC_Y: first symbol of the forward Y */
+    int32_t score; /* the chain score of step 4 (sum of the chained HSPs' scores; 0 without an HSP) */
+    int32_t pad;
 } CpkAnchorProblem;
 
 typedef struct {
@@ -248,8 +257,9 @@ typedef struct {
 } CpkAnchorParams;
 
 typedef struct CpkAnchorCtx CpkAnchorCtx;
-/* Copies the nBytes raw sequence bytes to `device` and packs them into symbols there. */
-int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes);
+/* Copies the nBytes raw sequence bytes to `device` and packs them into symbols there; behind them (from the next even
+ * symbol index on) the buffer has room for nExtra symbols more, for the reverse complements of a pass. */
+int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes, int64_t nExtra);
 /* Steps 1-5 of the anchor finder on n problems.  seed: '0' / '1' string.  *runs receives a malloc'd array of triples
  * (x, y, length) relative to each problem; problem i owns triples hspOff .. hspOff + nRuns - 1.  *ms: kernel time added. */
 int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, CpkAnchorProblem *probs, int64_t n,

@@ -1611,7 +1611,8 @@ struct CpkAnchorCtx {
     int device = 0;
     PostScratch *sc = nullptr;
     uint8_t *dSym = nullptr;
-    int64_t nSym = 0;
+    int64_t nSym = 0;     // symbols the buffer holds: the packed bytes, then the area of the reverse complements
+    int64_t nForward = 0; // the packed bytes
     hipEvent_t evA = nullptr, evB = nullptr;
 };
 
@@ -1630,7 +1631,7 @@ extern "C" void cpk_anchor_close(CpkAnchorCtx *c) {
     delete c;
 }
 
-extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes) {
+extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes, int64_t nExtra) {
     const int nDev = cpk_device_count();
     if (nDev <= 0 || device < 0 || device >= nDev) {
         cpk_set_error("no usable HIP device (count=%d, requested=%d): the HIP path has no CPU fallback", nDev, device);
@@ -1647,10 +1648,11 @@ extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *by
     }
     HIP_TRY(hipEventCreate(&c->evA));
     HIP_TRY(hipEventCreate(&c->evB));
-    c->nSym = nBytes;
+    c->nForward = nBytes;
+    c->nSym = nExtra > 0 ? ((nBytes + 1) & ~(int64_t)1) + nExtra : nBytes;
     uint8_t *dRaw = nullptr;
     if (int rc = c->sc->alloc(&dRaw, (size_t)nBytes)) return rc;
-    if (int rc = c->sc->alloc(&c->dSym, (size_t)((nBytes + 1) / 2))) return rc;
+    if (int rc = c->sc->alloc(&c->dSym, (size_t)((c->nSym + 1) / 2))) return rc;
     if (nBytes > 0) {
         HIP_TRY(hipMemcpyAsync(dRaw, bytes, (size_t)nBytes, hipMemcpyHostToDevice, c->sc->stream));
         const unsigned blocks = (unsigned)std::min<int64_t>(((nBytes + 1) / 2 + 255) / 256, 65535);
@@ -1686,9 +1688,22 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
     PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
     hipStream_t st = sc.stream;
     int64_t nKeys = 0;
-    int maxCap = 1;
+    int maxCap = 1, maxRc = 0;
     for (int64_t i = 0; i < n; i++) {
         CpkAnchorProblem &p = probs[i];
+        // a reverse complement is written from the forward symbols into the area behind them, at an even index
+        if ((p.flags & CPK_ANCHOR_RC_Y) && (p.yFwd < 0 || p.lY < 0 || p.yFwd + p.lY > c->nForward || (p.yOff & 1) ||
+                                            p.yOff < ((c->nForward + 1) & ~(int64_t)1))) {
+            cpk_set_error("anchor problem %lld: the reverse complement does not go from the forward symbols to the area behind them",
+                          (long long)i);
+            return CPECAN_EINVAL;
+        }
+        if ((p.flags & CPK_ANCHOR_SHARE_X) && (i == 0 || probs[i - 1].xOff != p.xOff || probs[i - 1].lX != p.lX ||
+                                               probs[i - 1].softMask != p.softMask || (probs[i - 1].flags & CPK_ANCHOR_SHARE_X))) {
+            cpk_set_error("anchor problem %lld: a twin follows the problem whose X it shares", (long long)i);
+            return CPECAN_EINVAL;
+        }
+        if (p.flags & CPK_ANCHOR_RC_Y) maxRc = std::max(maxRc, p.lY);
         if (p.lX < 0 || p.lY < 0 || p.xOff < 0 || p.yOff < 0 || p.xOff + p.lX > c->nSym || p.yOff + p.lY > c->nSym ||
             p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * prm->maxSeedOccurrences > (1 << 30)) {
             cpk_set_error("anchor problem %lld: sequences outside the buffer, longer than 2^24, or too many seed occurrences allowed",
@@ -1697,11 +1712,17 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
         }
         p.capX = anchor_pow2(std::max(p.lX - seed.span + 1, 1));
         p.capY = anchor_pow2(std::max(p.lY - seed.span + 1, 1));
-        p.keyXOff = nKeys;
-        p.keyYOff = nKeys + p.capX;
-        nKeys += (int64_t)p.capX + p.capY;
+        if (p.flags & CPK_ANCHOR_SHARE_X) {  // X's words are made and sorted once per pair
+            p.keyXOff = probs[i - 1].keyXOff;
+            p.keyYOff = nKeys;
+            nKeys += p.capY;
+        } else {
+            p.keyXOff = nKeys;
+            p.keyYOff = nKeys + p.capX;
+            nKeys += (int64_t)p.capX + p.capY;
+        }
         maxCap = std::max(maxCap, std::max(p.capX, p.capY));
-        p.hits = p.hsps = p.chained = p.nRuns = p.capped = p.pad = 0;
+        p.hits = p.hsps = p.chained = p.nRuns = p.capped = p.score = p.pad = 0;
         p.columns = 0;
         p.hspCap = 0;
         p.hspOff = 0;
@@ -1714,6 +1735,11 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
     float part = 0.f;
     HIP_TRY(hipMemcpyAsync(dProbs, probs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(c->evA, st));
+    if (maxRc > 0) {  // step 0, only in a pass that has a minus strand
+        const unsigned rcChunks = (unsigned)std::min(1024, (maxRc / 2 + 256) / 256);
+        hipLaunchKernelGGL(cpk_anchor_revcomp, dim3((unsigned)n, rcChunks), dim3(256), 0, st, dProbs, c->dSym);
+        HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(cpk_anchor_words, dim3((unsigned)n, chunks, 2), dim3(256), 0, st, dProbs, c->dSym, seed, dKeys);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpk_anchor_sort_keys, dim3((unsigned)n, 2), dim3(maxCap >= 4096 ? 1024 : 256), 0, st, dProbs, dKeys);

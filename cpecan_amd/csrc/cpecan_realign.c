@@ -362,6 +362,13 @@ int cpecan_cigar_from_aligned_pairs(const char *contig1, const char *contig2, do
     return rc;
 }
 
+int cpecan_cigar_from_aligned_pairs_stranded(const char *contig1, const char *contig2, double score, int64_t length1,
+                                             int64_t length2, int strand2, const int64_t *xy, int64_t n, cpecan_cigar *out) {
+    const int rc = cpecan_cigar_from_aligned_pairs(contig1, contig2, score, length1, length2, xy, n, out);
+    if (rc == CPECAN_OK && !strand2) rebase(&out->start2, &out->end2, &out->strand2, 0, 1);
+    return rc;
+}
+
 int cpecan_cigar_split(const cpecan_cigar *c, int64_t maxIndelLength, cpecan_cigar **out, int64_t *nOut) {
     if (!c || !c->contig1 || !c->contig2 || maxIndelLength < 0 || !out || !nOut || !cigar_consistent(c)) return CPECAN_EINVAL;
     *out = NULL;

@@ -7,7 +7,8 @@
 // Symbols are held as in stage_symbols (cpk_device_common.inl): two to a byte, low nibble = even index; the code is
 // 0..3 = a c g t, CPK_SYM_N = anything else, and bit 3 marks a lower-case (soft-masked) base.  X and Y strings of all
 // problems share one buffer and are addressed by global symbol index, so a sub-problem of the recursion is an offset
-// and a length, not a copy.
+// and a length, not a copy.  That holds for the minus strand too: cpk_anchor_revcomp writes the reverse complement of a
+// problem's Y behind the forward symbols of the same buffer.
 
 #define CPK_ANCHOR_LOWER 8
 #define CPK_ANCHOR_MAX_WEIGHT 15 /* word < 2^30: a key (word << 32 | position) never equals the all-ones filler */
@@ -38,12 +39,39 @@ __global__ void __launch_bounds__(256) cpk_anchor_pack(const uint8_t *raw, int64
     }
 }
 
+// Step 0: the reverse complement of the Y range of every problem that asks for it (CPK_ANCHOR_RC_Y): symbol i of the
+// range at yOff is the complement of symbol lY - 1 - i of the forward range at yFwd.  One output byte per thread; yOff is
+// even, so a byte belongs to one range, and the partner of a last odd symbol is N.  The source nibbles straddle bytes when
+// yFwd + lY is odd.  Complementing a code 0..3 is 3 - code; N and the lower-case bit pass through.
+__global__ void __launch_bounds__(256) cpk_anchor_revcomp(const CpkAnchorProblem *probs, uint8_t *sym) {
+    const CpkAnchorProblem pr = probs[blockIdx.x];
+    if (!(pr.flags & CPK_ANCHOR_RC_Y)) return;
+    const int nOut = (pr.lY + 1) >> 1;
+    uint8_t *out = sym + (pr.yOff >> 1);
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < nOut; i += gridDim.y * blockDim.x) {
+        int nib[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int d = 2 * i + h;
+            int s = CPK_SYM_N;
+            if (d < pr.lY) {
+                s = anchor_sym(sym, pr.yFwd + (pr.lY - 1 - d));
+                if ((s & 7) < 4) s = (3 - (s & 3)) | (s & CPK_ANCHOR_LOWER);
+            }
+            nib[h] = s;
+        }
+        out[i] = (uint8_t)(nib[0] | (nib[1] << 4));
+    }
+}
+
 // Step 1a: one key per window slot of X (blockIdx.z == 0) or Y (1): word << 32 | position, or the filler for a window
 // that is skipped (N or, with softMask, a lower-case base at a 1 position) and for the slots that pad to a power of two.
+// A problem that shares the X keys of its twin (CPK_ANCHOR_SHARE_X) has no side 0 of its own.
 __global__ void __launch_bounds__(256) cpk_anchor_words(const CpkAnchorProblem *probs, const uint8_t *sym, CpkAnchorSeed seed,
                                                         unsigned long long *keys) {
     const CpkAnchorProblem pr = probs[blockIdx.x];
     const int side = blockIdx.z;
+    if (side == 0 && (pr.flags & CPK_ANCHOR_SHARE_X)) return;
     const int cap = side ? pr.capY : pr.capX, l = side ? pr.lY : pr.lX;
     const int64_t off = side ? pr.yOff : pr.xOff;
     unsigned long long *out = keys + (side ? pr.keyYOff : pr.keyXOff);
@@ -93,6 +121,7 @@ struct AnchorKeyLess {
 __global__ void __launch_bounds__(1024) cpk_anchor_sort_keys(const CpkAnchorProblem *probs, unsigned long long *keys) {
     const CpkAnchorProblem pr = probs[blockIdx.x];
     const int side = blockIdx.y;
+    if (side == 0 && (pr.flags & CPK_ANCHOR_SHARE_X)) return;  // uniform over the workgroup: no barrier is left behind
     anchor_bitonic(keys + (side ? pr.keyYOff : pr.keyXOff), side ? pr.capY : pr.capX, AnchorKeyLess());
 }
 
@@ -292,5 +321,6 @@ __global__ void __launch_bounds__(256) cpk_anchor_chain(CpkAnchorProblem *probs,
         probs[p].nRuns = nRuns;
         probs[p].columns = columns;
         probs[p].capped = capped;
+        probs[p].score = n > 0 ? (int32_t)(endKey >> 32) : 0;  // the chain score: the strand score of a top-level pass
     }
 }

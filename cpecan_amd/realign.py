@@ -9,7 +9,7 @@ from . import api
 # Every symbol include/cpecan_realign.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "cpecan_cigar_parse", "cpecan_cigar_format", "cpecan_cigar_clear", "cpecan_cigars_free",
-    "cpecan_cigar_from_aligned_pairs", "cpecan_cigar_split",
+    "cpecan_cigar_from_aligned_pairs", "cpecan_cigar_from_aligned_pairs_stranded", "cpecan_cigar_split",
     "cpecan_realign_options_default", "cpecan_realigner_create", "cpecan_realigner_destroy",
     "cpecan_realigner_add_sequence", "cpecan_realigner_read_fasta", "cpecan_realigner_set_posterior_files",
     "cpecan_realigner_realign", "cpecan_realigner_expectations",
@@ -52,6 +52,8 @@ def _lib():
         L.cpecan_cigars_free.restype = None
         L.cpecan_cigar_from_aligned_pairs.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_int64, C.c_int64,
                                                       C.POINTER(C.c_int64), C.c_int64, C.POINTER(_Cigar)]
+        L.cpecan_cigar_from_aligned_pairs_stranded.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_int64, C.c_int64, C.c_int,
+                                                               C.POINTER(C.c_int64), C.c_int64, C.POINTER(_Cigar)]
         L.cpecan_cigar_split.argtypes = [C.POINTER(_Cigar), C.c_int64, C.POINTER(C.POINTER(_Cigar)), C.POINTER(C.c_int64)]
         L.cpecan_realign_options_default.argtypes = [C.POINTER(RealignOptions)]
         L.cpecan_realign_options_default.restype = None
@@ -117,13 +119,15 @@ class Cigar:
         return buf.value.decode()
 
     @staticmethod
-    def from_aligned_pairs(contig1, contig2, score, length1, length2, xy):  # cPecanRealign.c:49
-        """convertAlignedPairsToPairwiseAlignment: xy = increasing (x, y) pairs."""
+    def from_aligned_pairs(contig1, contig2, score, length1, length2, xy, strand2=True):  # cPecanRealign.c:49
+        """convertAlignedPairsToPairwiseAlignment: xy = increasing (x, y) pairs.  strand2 False: the pairs are in the
+        coordinates of (X, reverse complement of Y) and the cigar reads "<length2> 0 -" for contig2."""
         flat = [int(v) for p in xy for v in p]
         arr = (C.c_int64 * max(1, len(flat)))(*flat)
         c = _Cigar()
-        api._check(_lib().cpecan_cigar_from_aligned_pairs(contig1.encode(), contig2.encode(), score, length1, length2, arr,
-                                                          len(flat) // 2, C.byref(c)), "cpecan_cigar_from_aligned_pairs")
+        api._check(_lib().cpecan_cigar_from_aligned_pairs_stranded(contig1.encode(), contig2.encode(), score, length1, length2,
+                                                                   int(bool(strand2)), arr, len(flat) // 2, C.byref(c)),
+                   "cpecan_cigar_from_aligned_pairs_stranded")
         try:
             return Cigar._from_c(c)
         finally:

@@ -205,6 +205,31 @@ int cpecan_find_anchor_runs(const char *sX, int64_t lX, const char *sY, int64_t 
 int cpecan_find_anchor_runs_once(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
                                  int softMask, const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns);
 
+/* ---- strand: a query that may lie on the other strand ----
+ * rc(s): the bytes reversed with A<->T, C<->G, a<->t, c<->g; every other byte stays (to the kernels it is N anyway) and
+ * case survives, so soft masking means the same on both strands.  out holds l bytes and may be s itself. */
+int cpecan_reverse_complement(const char *s, int64_t l, char *out);
+
+/* PLUS and MINUS force the orientation: the problem is searched as (X, Y) or as (X, rc(Y)).  BOTH: one top-level pass
+ * (steps 1-4, soft masking on) scores the WHOLE pair in either orientation, whatever anchorMatrixBiggerThanThis says; the
+ * strand score is the chain score of step 4, the sum of the chained HSPs' scores, 0 without an HSP.  The pair is on the
+ * minus strand iff scoreMinus > scorePlus: a tie, 0 = 0 included, is plus.  The chosen orientation then goes on exactly
+ * as a forced call goes on.  A score that was not computed reads -1. */
+enum { CPECAN_STRAND_PLUS = 0, CPECAN_STRAND_MINUS = 1, CPECAN_STRAND_BOTH = 2 };
+typedef struct cpecan_strand_result {
+    int32_t strand; /* CPECAN_STRAND_PLUS or CPECAN_STRAND_MINUS */
+    int32_t scorePlus, scoreMinus;
+    int32_t reserved;
+} cpecan_strand_result;
+/* cpecan_find_anchor_runs_many with a strand mode (CPECAN_EINVAL outside 0..2); PLUS is that function, integer for
+ * integer.  Runs and statistics of a minus problem are in the coordinates of (X, rc(Y)): position y' there is position
+ * lY - 1 - y' of Y.  The reverse complements are made on the device, and the twins of a BOTH problem share X's sorted
+ * words.  strands (n entries) may be NULL. */
+int cpecan_find_anchor_runs_many_stranded(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                          int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                                          const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
+                                          int64_t *nRuns, cpecan_anchor_stats *stats, cpecan_strand_result *strands);
+
 /* The reference's cell-level primitives (inc/pairwiseAligner.h:186-237: cell_calculateForward / Backward,
  * diagonalCalculationForward / Backward, the posterior of :683-685), which its unit tests link, evaluated on the caller's
  * current device: `n` operations applied in order to the cells held in `cells` (nDoubles doubles, changed in place).
@@ -277,6 +302,13 @@ typedef struct cpecan_problem_runs {
     int32_t raggedLeft, raggedRight;
 } cpecan_problem_runs;
 int64_t cpecan_batch_add_many_runs(cpecan_batch *b, const cpecan_problem_runs *problems, int64_t n);
+/* The same for problems of either strand: yMinus (n entries, or NULL = all plus) marks the problems whose runs are in the
+ * coordinates of (X, rc(Y)), as cpecan_find_anchor_runs_many_stranded returns them.  sY stays the forward sequence: the
+ * batch writes its reverse complement straight into its own arrays, and planning, upload and the kernels see a forward
+ * problem on those bytes.  Results of a minus problem are in the coordinates of (X, rc(Y)). */
+int64_t cpecan_batch_add_many_runs_stranded(cpecan_batch *b, const cpecan_problem_runs *problems, const int32_t *yMinus, int64_t n);
+/* CPECAN_STRAND_PLUS or CPECAN_STRAND_MINUS as problem i was added, or < 0. */
+int cpecan_batch_problem_strand(const cpecan_batch *b, int64_t problem);
 /* Run-length form of an anchor list: out receives at most cap quadruples; returns the number of runs the list has (which
  * may exceed cap: nothing beyond cap is written), or < 0.  Consecutive anchors join a run when both coordinates step by
  * one and the expansion is the same. */

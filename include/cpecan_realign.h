@@ -44,6 +44,11 @@ void cpecan_cigars_free(cpecan_cigar *cigars, int64_t n);
  * spans [0, length1) x [0, length2) on the forward strands, unaligned ends included as leading / trailing indels. */
 int cpecan_cigar_from_aligned_pairs(const char *contig1, const char *contig2, double score, int64_t length1, int64_t length2,
                                     const int64_t *xy, int64_t n, cpecan_cigar *out);
+/* The same for a query on either strand: strand2 1 is the function above; strand2 0 takes the pairs (x, y') in the
+ * coordinates of (X, rc(Y)) and gives start2 = length2, end2 = 0, strand2 = 0 with the operations in the order of the
+ * pairs -- what the realigner reads back as rc(Y) (getSubSequence, cPecanRealign.c:252-258). */
+int cpecan_cigar_from_aligned_pairs_stranded(const char *contig1, const char *contig2, double score, int64_t length1,
+                                             int64_t length2, int strand2, const int64_t *xy, int64_t n, cpecan_cigar *out);
 /* splitPairwiseAlignment (cPecanRealign.c:117-230): cuts c at every run of indels longer than maxIndelLength; the runs
  * that are cut and any indels at either end are dropped.  *out: malloc'd array of *nOut cigars (cpecan_cigars_free). */
 int cpecan_cigar_split(const cpecan_cigar *c, int64_t maxIndelLength, cpecan_cigar **out, int64_t *nOut);
