@@ -150,7 +150,10 @@ EXPORTS = [
     "cpecan_anchor_params_default", "cpecan_find_anchor_runs_many", "cpecan_find_anchor_runs", "cpecan_find_anchor_runs_once",
     "cpecan_reverse_complement", "cpecan_find_anchor_runs_many_stranded", "cpecan_batch_add_many_runs_stranded",
     "cpecan_batch_problem_strand",
+    "cpecan_batch_reserve_models", "cpecan_batch_set_models", "cpecan_batch_expectations_slot",
+    "cpecan_batch_forward_prob_slot",
 ]
+MAX_MODEL_SLOTS = 8  # CPECAN_MAX_MODEL_SLOTS
 OP_MATCH, OP_INDEL_X, OP_INDEL_Y = 0, 1, 2
 POST_REWEIGHT, POST_MEA, POST_LEFT_SHIFT, POST_ORDERED = 1, 2, 4, 8
 
@@ -253,6 +256,10 @@ def lib():
     L.cpecan_batch_add_many_runs_stranded.argtypes = [vp, C.POINTER(ProblemRuns), i32p, C.c_int64]
     L.cpecan_batch_add_many_runs_stranded.restype = C.c_int64
     L.cpecan_batch_problem_strand.argtypes = [vp, C.c_int64]
+    L.cpecan_batch_reserve_models.argtypes = [vp, C.c_int]
+    L.cpecan_batch_set_models.argtypes = [vp, C.POINTER(StateMachine), C.c_int]
+    L.cpecan_batch_expectations_slot.argtypes = [vp, C.c_int, C.POINTER(Hmm)]
+    L.cpecan_batch_forward_prob_slot.argtypes = [vp, C.c_int, C.c_int64, dp]
     _lib = L
     return L
 
@@ -658,6 +665,17 @@ class Batch:
         _check(lib().cpecan_batch_set_model(self._h, C.byref(sM)), "cpecan_batch_set_model")
         self._sM = sM
 
+    def reserve_models(self, n_slots):
+        """Before upload(): the batch (EMIT_EXPECT or EMIT_FORWARD) will evaluate up to n_slots models per run()."""
+        _check(lib().cpecan_batch_reserve_models(self._h, int(n_slots)), "cpecan_batch_reserve_models")
+
+    def set_models(self, models):
+        """The models of the next run() of a reserved batch, one launch for all; slot k of the getters is models[k]."""
+        models = list(models)
+        arr = (StateMachine * max(len(models), 1))(*models)
+        _check(lib().cpecan_batch_set_models(self._h, arr, len(models)), "cpecan_batch_set_models")
+        self._sM = models[0]
+
     def download(self):
         _check(lib().cpecan_batch_download(self._h), "cpecan_batch_download")
 
@@ -697,14 +715,15 @@ class Batch:
         _check(lib().cpecan_batch_scores(self._h, problem, C.byref(a), C.byref(b), C.byref(c)), "cpecan_batch_scores")
         return a.value, b.value, c.value
 
-    def expectations(self, hmm):
-        """Adds the batch's expectation counts into hmm (EMIT_EXPECT), like getExpectationsUsingAnchors on each problem."""
-        _check(lib().cpecan_batch_expectations(self._h, C.byref(hmm)), "cpecan_batch_expectations")
+    def expectations(self, hmm, slot=0):
+        """Adds the batch's expectation counts into hmm (EMIT_EXPECT), like getExpectationsUsingAnchors on each problem;
+        slot: the model of a reserved batch's run (set_models)."""
+        _check(lib().cpecan_batch_expectations_slot(self._h, int(slot), C.byref(hmm)), "cpecan_batch_expectations_slot")
         return hmm
 
-    def forward_prob(self, problem):
+    def forward_prob(self, problem, slot=0):
         v = C.c_double()
-        _check(lib().cpecan_batch_forward_prob(self._h, problem, C.byref(v)), "cpecan_batch_forward_prob")
+        _check(lib().cpecan_batch_forward_prob_slot(self._h, int(slot), problem, C.byref(v)), "cpecan_batch_forward_prob_slot")
         return v.value
 
     def stats(self):

@@ -251,6 +251,7 @@ struct cpecan_em_trainer {
     char **fastas;
     int nFastas;
     cpecan_em_timing timing;
+    int concurrentTrials; /* cpecan_em_trainer_set_concurrent_trials: trials per launch (1: one after another) */
 };
 
 static char *dup_str(const char *s) {
@@ -277,6 +278,7 @@ int cpecan_em_trainer_create(cpecan_em_trainer **out, const cpecan_em_options *o
     t->opt.inputModel = t->inputModel;
     t->opt.blastScoringMatrixFile = t->blastFile;
     t->type = o->modelType;
+    t->concurrentTrials = 1;
     int rc = CPECAN_OK;
     if (t->inputModel) {
         if (cpecan_hmm_load(&t->input, t->inputModel) != CPECAN_OK) {
@@ -333,6 +335,16 @@ int cpecan_em_trainer_set_devices(cpecan_em_trainer *t, const int *devices, int 
     return cpecan_realigner_set_devices(t->r, devices, nDevices);
 }
 
+int cpecan_em_trainer_set_concurrent_trials(cpecan_em_trainer *t, int n) {
+    if (!t) return CPECAN_EINVAL;
+    if (n < 1 || n > CPECAN_MAX_MODEL_SLOTS) {
+        cpk_set_error("concurrent trials: %d, 1 to %d are possible", n, CPECAN_MAX_MODEL_SLOTS);
+        return CPECAN_EINVAL;
+    }
+    t->concurrentTrials = n;
+    return CPECAN_OK;
+}
+
 int cpecan_em_trainer_timing(const cpecan_em_trainer *t, cpecan_em_timing *out) {
     if (!t || !out) return CPECAN_EINVAL;
     *out = t->timing;
@@ -383,6 +395,44 @@ static int run_trial(cpecan_em_trainer *t, cpecan_expect_set *set, int64_t nJobs
     return rc;
 }
 
+/* The M-step of one trial from its E-step's counts (calculateMaximisation). */
+static void m_step(const cpecan_em_trainer *t, cpecan_hmm *acc, cpecan_hmm *h, double *running) {
+    cpecan_hmm_normalise(acc);
+    *running = acc->likelihood;
+    if (!t->opt.trainEmissions)
+        memcpy(acc->emissions, h->emissions, sizeof acc->emissions);
+    else if (t->opt.tieEmissions)
+        cpecan_hmm_tie_emissions(acc);
+    *h = *acc;
+}
+
+/* A round of n trials side by side: every iteration is ONE cpecan_expect_set_run_models over the round's models plus the
+ * M-step of each -- what run_trial does for one trial, file for file. */
+static int run_round(cpecan_em_trainer *t, cpecan_expect_set *set, int64_t nJobs, cpecan_hmm *hmms, int n, double *runs,
+                     int iters, char **paths) {
+    cpecan_model ms[CPECAN_MAX_MODEL_SLOTS];
+    cpecan_hmm accs[CPECAN_MAX_MODEL_SLOTS];
+    int rc = CPECAN_OK;
+    for (int j = 0; rc == CPECAN_OK && j < n; j++) {
+        rc = cpecan_em_write_model(&hmms[j], NULL, 0, paths[j]);
+        if (rc == CPECAN_OK)
+            rc = t->opt.useDefaultModelAsStart ? cpecan_model_default(&ms[j], t->type) : cpecan_model_from_hmm(&ms[j], &hmms[j]);
+    }
+    for (int it = 0; rc == CPECAN_OK && it < iters; it++) {
+        for (int j = 0; rc == CPECAN_OK && j < n; j++)
+            rc = cpecan_hmm_init(&accs[j], t->type, EM_PSEUDO * (double)(nJobs > 0 ? nJobs : 1));
+        if (rc == CPECAN_OK) rc = cpecan_expect_set_run_models(set, ms, n, accs);
+        for (int j = 0; rc == CPECAN_OK && j < n; j++) {
+            m_step(t, &accs[j], &hmms[j], &runs[(size_t)j * (size_t)iters + it]);
+            rc = cpecan_em_write_model(&hmms[j], NULL, 0, paths[j]);
+            if (rc == CPECAN_OK) rc = cpecan_model_from_hmm(&ms[j], &hmms[j]);
+        }
+    }
+    for (int j = 0; rc == CPECAN_OK && j < n; j++)
+        rc = cpecan_em_write_model(&hmms[j], runs + (size_t)j * (size_t)iters, iters, paths[j]);
+    return rc;
+}
+
 int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, const char *outputModel, cpecan_hmm *best,
                     double *running) {
     if (!t || (!in && n > 0) || n < 0 || !outputModel) return CPECAN_EINVAL;
@@ -390,6 +440,7 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
     memset(&t->timing, 0, sizeof t->timing);
     const int iters = t->opt.iterations;
     const int trials = (!t->inputModel && t->opt.randomStart) ? t->opt.trials : 1;
+    const int conc = t->concurrentTrials < trials ? t->concurrentTrials : trials; /* trials per launch */
     int64_t *order = malloc(sizeof(int64_t) * (size_t)(n ? n : 1));
     cpecan_cigar *sample = malloc(sizeof(cpecan_cigar) * (size_t)(n ? n : 1));
     double *runs = calloc((size_t)trials * (size_t)(iters ? iters : 1), sizeof(double));
@@ -403,12 +454,31 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
     cpecan_expect_set *set = NULL;
     if (rc == CPECAN_OK) {
         for (int64_t i = 0; i < nSample; i++) sample[i] = in[order[i]]; /* shallow copies: nothing is freed through them */
-        rc = cpecan_expect_set_create(&set, t->r, sample, nSample);
+        rc = cpecan_expect_set_reserve_models(t->r, conc > 1 ? conc : 0);
+        if (rc == CPECAN_OK) rc = cpecan_expect_set_create(&set, t->r, sample, nSample);
     }
     uint64_t rng = t->opt.seed ^ 0x5DEECE66Dull; /* the random starts: a stream of their own, from the same seed */
     const double t1 = now_ms();
     int bestTrial = 0;
-    for (int k = 0; rc == CPECAN_OK && k < trials; k++) {
+    if (conc > 1) {
+        /* every start model first, in trial order, from the same generator state (the trials' iterations draw nothing):
+         * trial k starts where it starts in a sequential run.  Then rounds of up to `conc` trials. */
+        char *paths[CPECAN_MAX_MODEL_SLOTS] = {0};
+        for (int k = 0; rc == CPECAN_OK && k < trials; k++) rc = start_model(t, &rng, &hmms[k]);
+        for (int j = 0; rc == CPECAN_OK && j < conc; j++)
+            if (!(paths[j] = malloc(strlen(outputModel) + 32))) rc = CPECAN_ENOMEM;
+        for (int k0 = 0; rc == CPECAN_OK && k0 < trials; k0 += conc) {
+            const int nr = trials - k0 < conc ? trials - k0 : conc;
+            for (int j = 0; j < nr; j++) sprintf(paths[j], t->opt.outputTrialHmms ? "%s_%d" : "%s.trial_%d", outputModel, k0 + j);
+            rc = run_round(t, set, nJobs, hmms + k0, nr, runs + (size_t)k0 * (size_t)iters, iters, paths);
+            for (int j = 0; j < nr; j++) {
+                if (!t->opt.outputTrialHmms) remove(paths[j]);
+                if (rc == CPECAN_OK && hmms[k0 + j].likelihood > hmms[bestTrial].likelihood) bestTrial = k0 + j;
+            }
+        }
+        for (int j = 0; j < conc; j++) free(paths[j]);
+    }
+    for (int k = 0; conc <= 1 && rc == CPECAN_OK && k < trials; k++) {
         rc = start_model(t, &rng, &hmms[k]);
         if (rc != CPECAN_OK) break;
         if (trials == 1) strcpy(path, outputModel);

@@ -17,6 +17,7 @@ static void usage(void) {
             "cpecan_em --sequences \"a.fa b.fa\" --alignments FILE --outputModel FILE [options]\n"
             "--modelType fiveState|fiveStateAsymmetric|threeState|threeStateAsymmetric  --inputModel FILE\n"
             "--iterations N (10)  --trials N (3, with --randomStart and no --inputModel)  --randomStart  --outputTrialHmms\n"
+            "--concurrentTrials N (1; up to 8 trials per kernel launch, more trials run in rounds)\n"
             "--useDefaultModelAsStart  --setJukesCantorStartingEmissions F  --trainEmissions  --tieEmissions\n"
             "--maxAlignmentLengthPerJob N (1000000)  --maxAlignmentLengthToSample N (50000000)  --seed N (0)\n"
             "--blastScoringMatrixFile FILE  --optionsToRealign \"...\" (default \"--diagonalExpansion=10\n"
@@ -142,13 +143,14 @@ int main(int argc, char **argv) {
     enum {
         kModelType = 256, kInputModel, kOutputModel, kIterations, kTrials, kRandomStart, kTrialHmms, kDefaultStart,
         kJukesCantor, kTrainEmissions, kTieEmissions, kPerJob, kToSample, kSeed, kBlast, kToRealign, kSequences,
-        kAlignments, kDevice, kDevices, kLogLevel, kXml, kUpdateBand
+        kAlignments, kDevice, kDevices, kLogLevel, kXml, kUpdateBand, kConcurrent
     };
     static struct option longOpts[] = {{"modelType", required_argument, 0, kModelType},
                                        {"inputModel", required_argument, 0, kInputModel},
                                        {"outputModel", required_argument, 0, kOutputModel},
                                        {"iterations", required_argument, 0, kIterations},
                                        {"trials", required_argument, 0, kTrials},
+                                       {"concurrentTrials", required_argument, 0, kConcurrent},
                                        {"randomStart", no_argument, 0, kRandomStart},
                                        {"outputTrialHmms", no_argument, 0, kTrialHmms},
                                        {"useDefaultModelAsStart", no_argument, 0, kDefaultStart},
@@ -169,7 +171,7 @@ int main(int argc, char **argv) {
                                        {"updateTheBand", no_argument, 0, kUpdateBand},
                                        {"help", no_argument, 0, 'h'},
                                        {0, 0, 0, 0}};
-    long long v;
+    long long v, concurrent = 1;
     for (int key; (key = getopt_long(argc, argv, "h", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
@@ -183,6 +185,13 @@ int main(int argc, char **argv) {
         case kOutputModel: outputModel = optarg; break;
         case kIterations: if (sscanf(optarg, "%lld", &v) != 1 || v < 0) return fail("--iterations"); o.iterations = (int)v; break;
         case kTrials: if (sscanf(optarg, "%lld", &v) != 1 || v < 1) return fail("--trials"); o.trials = (int)v; break;
+        case kConcurrent:
+            if (sscanf(optarg, "%lld", &v) != 1 || v < 1 || v > CPECAN_MAX_MODEL_SLOTS) {
+                fprintf(stderr, "cpecan_em: --concurrentTrials %s: 1 to %d trials per launch\n", optarg, CPECAN_MAX_MODEL_SLOTS);
+                return 1;
+            }
+            concurrent = v;
+            break;
         case kRandomStart: o.randomStart = 1; break;
         case kTrialHmms: o.outputTrialHmms = 1; break;
         case kDefaultStart: o.useDefaultModelAsStart = 1; break;
@@ -221,6 +230,7 @@ int main(int argc, char **argv) {
     cpecan_em_trainer *t = NULL;
     if (cpecan_em_trainer_create(&t, &o, &ro, (int)device) != CPECAN_OK) return fail("options");
     if (nDevices > 1 && cpecan_em_trainer_set_devices(t, devices, nDevices) != CPECAN_OK) return fail("--devices");
+    if (cpecan_em_trainer_set_concurrent_trials(t, (int)concurrent) != CPECAN_OK) return fail("--concurrentTrials");
     int status = 0;
     char *seqs = strdup(sequences), *save = NULL;
     for (char *path = strtok_r(seqs, " \t", &save); status == 0 && path; path = strtok_r(NULL, " \t", &save))

@@ -439,7 +439,9 @@ struct cpecan_batch {
     int nLists;
     int64_t dbgCells, dbgDiags;
     CpkDevice *dev;
-    double *forward; /* [nRegions] in device order, FORWARD emitter */
+    double *forward; /* [slot][nRegions] in device order, FORWARD emitter; [slot][106] sums, EXPECT emitter */
+    int modelSlots;  /* cpecan_batch_reserve_models: models reserved per run; 0: a plain batch */
+    int activeModels, downloadedModels; /* models of the next run / of the downloaded one */
     int32_t *results; /* every emitted triple of the batch, list-ordered: [list][problem][triple] */
     uint8_t *chars;   /* raw upper-case sequences (leftShiftAlignment compares letters, not symbols) */
     int64_t nChars, capChars;
@@ -653,6 +655,7 @@ int cpecan_batch_create(cpecan_batch **out, const cpecan_model *model, const cpe
     b->anchorStride = params->dynamicAnchorExpansion ? 3 : 2;
     b->runForm = -1;
     b->postMatchGamma = 0.85f; /* cPecanRealign.c:355 */
+    b->activeModels = b->downloadedModels = 1;
     *out = b;
     return CPECAN_OK;
 }
@@ -1694,6 +1697,7 @@ int cpecan_batch_upload(cpecan_batch *b) {
         b->stats.cells = hp.totalCells;
         b->stats.diagonals = hp.totalDiags;
         if (!b->dev) rc = cpk_device_create(&b->dev, b->device); /* fails with CPECAN_ENODEVICE when there is no GPU */
+        if (rc == CPECAN_OK) rc = cpk_device_reserve_models(b->dev, b->modelSlots);
     }
     if (rc == CPECAN_OK) {
         const int runs = b->runForm == 1;
@@ -1729,27 +1733,64 @@ int cpecan_batch_run(cpecan_batch *b, void *stream) {
     return rc;
 }
 
-int cpecan_batch_set_model(cpecan_batch *b, const cpecan_model *m) {
+int cpecan_batch_reserve_models(cpecan_batch *b, int nSlots) {
     if (dl_busy(b)) return CPECAN_ESTATE;
-    if (!b || !m) return CPECAN_EINVAL;
-    if (!(is_five(m->type) || is_three(m->type)) || is_five(m->type) != is_five(b->model.type)) {
-        cpk_set_error("set_model: a model of %d states for a batch planned for %d", is_five(m->type) ? 5 : 3,
-                      is_five(b->model.type) ? 5 : 3);
-        return CPECAN_EINVAL;
-    }
-    if (!b->frozen) {
-        cpk_set_error("set_model before upload");
+    if (!b) return CPECAN_EINVAL;
+    if (b->frozen) {
+        cpk_set_error("reserve_models after upload");
         return CPECAN_ESTATE;
     }
-    if (b->nRegions > 0) {
-        CpkModel km;
-        kernel_model(m, b->params.threshold, &km);
-        const int rc = cpk_device_set_model(b->dev, &km);
-        if (rc != CPECAN_OK) return rc;
+    if (b->emit != CPECAN_EMIT_EXPECT && b->emit != CPECAN_EMIT_FORWARD) {
+        cpk_set_error("reserve_models: only CPECAN_EMIT_EXPECT and CPECAN_EMIT_FORWARD batches take model slots (emitter %d returns lists)", b->emit);
+        return CPECAN_EINVAL;
     }
-    b->model = *m;
-    b->ran = 0; /* a run not downloaded yet belongs to the old model: the next download needs a new run */
+    if (nSlots < 1 || nSlots > CPECAN_MAX_MODEL_SLOTS) {
+        cpk_set_error("reserve_models: %d slots, 1 to %d are possible", nSlots, CPECAN_MAX_MODEL_SLOTS);
+        return CPECAN_EINVAL;
+    }
+    b->modelSlots = nSlots;
     return CPECAN_OK;
+}
+
+int cpecan_batch_set_models(cpecan_batch *b, const cpecan_model *models, int n) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !models) return CPECAN_EINVAL;
+    if (n < 1 || n > CPECAN_MAX_MODEL_SLOTS) { /* before models[] is read */
+        cpk_set_error("set_models: %d models, 1 to %d are possible", n, CPECAN_MAX_MODEL_SLOTS);
+        return CPECAN_EINVAL;
+    }
+    for (int k = 0; k < n; k++) {
+        const cpecan_model *m = &models[k];
+        if (!(is_five(m->type) || is_three(m->type)) || is_five(m->type) != is_five(b->model.type)) {
+            cpk_set_error("set_models: a model of %d states for a batch planned for %d", is_five(m->type) ? 5 : 3,
+                          is_five(b->model.type) ? 5 : 3);
+            return CPECAN_EINVAL;
+        }
+    }
+    if (!b->frozen) {
+        cpk_set_error("set_models before upload");
+        return CPECAN_ESTATE;
+    }
+    if (n > (b->modelSlots > 0 ? b->modelSlots : 1)) {
+        cpk_set_error("set_models: %d models for a batch that reserved %d", n, b->modelSlots);
+        return CPECAN_EINVAL;
+    }
+    if (b->nRegions > 0) {
+        CpkModel km[CPECAN_MAX_MODEL_SLOTS];
+        for (int k = 0; k < n; k++) kernel_model(&models[k], b->params.threshold, &km[k]);
+        const int rc = cpk_device_set_models(b->dev, km, n);
+        if (rc != CPECAN_OK) return rc;
+        b->stats.wavesPerLaunch = cpk_device_waves(b->dev); /* a reserved batch: the waves of a run grow with its models */
+    }
+    b->model = models[0];
+    b->activeModels = n;
+    b->ran = 0; /* a run not downloaded yet belongs to the old models: the next download needs a new run */
+    return CPECAN_OK;
+}
+
+int cpecan_batch_set_model(cpecan_batch *b, const cpecan_model *m) {
+    if (!b || !m) return dl_busy(b) ? CPECAN_ESTATE : CPECAN_EINVAL;
+    return cpecan_batch_set_models(b, m, 1);
 }
 
 /* The copy plan of cpk_device_gather for the whole batch: per list, problems in order, regions in order, traceback
@@ -1957,7 +1998,7 @@ int cpecan_batch_download(cpecan_batch *b) {
             break;
         }
         if ((b->emit == CPECAN_EMIT_FORWARD || b->emit == CPECAN_EMIT_EXPECT) && !b->forward) {
-            b->forward = malloc(sizeof(double) * (size_t)(b->nRegions > 106 ? b->nRegions : 106));
+            b->forward = malloc(sizeof(double) * (size_t)(b->modelSlots > 0 ? b->modelSlots : 1) * (size_t)(b->nRegions > 106 ? b->nRegions : 106));
             if (!b->forward) {
                 rc = CPECAN_ENOMEM;
                 break;
@@ -2037,7 +2078,10 @@ int cpecan_batch_download(cpecan_batch *b) {
             fprintf(stderr, "cpecan download: wait + counts %.1f ms, overflow scan %.1f, list plan %.1f (%lld chunks), gather %.1f, consumers %.1f, fetch %.1f (%lld triples)\n",
                     tD1 - tD0, tD2 - tD1, tD3 - tD2, (long long)nChunks, tD4 - tD3, tD5 - tD4, now_ms() - tD5, (long long)total);
     }
-    if (rc == CPECAN_OK) b->downloaded = 1;
+    if (rc == CPECAN_OK) {
+        b->downloaded = 1;
+        b->downloadedModels = b->activeModels;
+    }
     cpk_host_free(counts);
     cpk_host_free(segStarts);
     cpk_host_free(segCounts);
@@ -2086,26 +2130,39 @@ int cpecan_batch_result(const cpecan_batch *b, int64_t problem, int which, const
     return CPECAN_OK;
 }
 
-int cpecan_batch_forward_prob(const cpecan_batch *b, int64_t problem, double *logProb) {
+int cpecan_batch_forward_prob_slot(const cpecan_batch *b, int slot, int64_t problem, double *logProb) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || !b->downloaded || b->emit != CPECAN_EMIT_FORWARD) return CPECAN_ESTATE;
     if (problem < 0 || problem >= b->nProblems || !logProb) return CPECAN_EINVAL;
-    *logProb = b->forward[b->regions[b->problems[problem].firstRegion].devIndex];
+    if (slot < 0 || slot >= b->downloadedModels) {
+        cpk_set_error("slot %d of a run with %d models", slot, b->downloadedModels);
+        return CPECAN_EINVAL;
+    }
+    *logProb = b->forward[(size_t)slot * b->nRegions + b->regions[b->problems[problem].firstRegion].devIndex];
     return CPECAN_OK;
 }
+int cpecan_batch_forward_prob(const cpecan_batch *b, int64_t problem, double *logProb) {
+    return cpecan_batch_forward_prob_slot(b, 0, problem, logProb);
+}
 
-int cpecan_batch_expectations(const cpecan_batch *b, cpecan_hmm *acc) {
+int cpecan_batch_expectations_slot(const cpecan_batch *b, int slot, cpecan_hmm *acc) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || !b->downloaded || b->emit != CPECAN_EMIT_EXPECT) return CPECAN_ESTATE;
     const int S = is_five(b->model.type) ? 5 : 3;
     if (!acc || acc->stateNumber != S) return CPECAN_EINVAL;
+    if (slot < 0 || slot >= b->downloadedModels) {
+        cpk_set_error("slot %d of a run with %d models", slot, b->downloadedModels);
+        return CPECAN_EINVAL;
+    }
     if (b->nRegions == 0) return CPECAN_OK;
-    /* b->forward holds the batch sums: [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood */
-    for (int i = 0; i < S * S; i++) acc->transitions[i] += b->forward[i];
-    for (int i = 0; i < S * 16; i++) acc->emissions[i] += b->forward[25 + i];
-    acc->likelihood += b->forward[105];
+    /* b->forward holds the sums per slot: [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood */
+    const double *sum = b->forward + (size_t)slot * 106;
+    for (int i = 0; i < S * S; i++) acc->transitions[i] += sum[i];
+    for (int i = 0; i < S * 16; i++) acc->emissions[i] += sum[25 + i];
+    acc->likelihood += sum[105];
     return CPECAN_OK;
 }
+int cpecan_batch_expectations(const cpecan_batch *b, cpecan_hmm *acc) { return cpecan_batch_expectations_slot(b, 0, acc); }
 
 int cpecan_batch_stats(const cpecan_batch *b, cpecan_stats *s) {
     if (dl_busy(b)) return CPECAN_ESTATE;

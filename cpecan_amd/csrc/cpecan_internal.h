@@ -169,6 +169,12 @@ int cpk_device_update_regions(CpkDevice *dev, const CpkRegion *regions, const Cp
 /* Replaces the model the next cpk_device_run uses (kernel-argument transitions and the device CpkModel); the copy is
  * ordered behind the last run on the batch's own stream and in front of the next sweep. */
 int cpk_device_set_model(CpkDevice *dev, const CpkModel *model);
+/* Model slots.  Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch; expectation
+ * and forward emitters only) -- wave counts and everything per wave are planned for nSlots times the regions.  After it:
+ * the n models of the next run, 1 <= n <= nSlots, ordered on the stream as cpk_device_set_model orders its one.
+ * cpk_device_download then fills `expect` per slot: [n][106] sums, or [n][nRegions] forward probabilities. */
+int cpk_device_reserve_models(CpkDevice *dev, int nSlots);
+int cpk_device_set_models(CpkDevice *dev, const CpkModel *models, int n);
 int cpk_device_run(CpkDevice *dev, void *stream);
 int cpk_device_form(const CpkDevice *dev); /* CPECAN_FORM_* of the batch's last (widest) size class */
 /* Once more on the stream of the last run (after an output overflow); kernel times of a batch's launches add up. */

@@ -636,6 +636,11 @@ struct CpkDevice {
     // cpk_device_set_model: the pinned source of the last model copy and the event that says it has been read
     CpkModel *hModel = nullptr;
     hipEvent_t evModel = nullptr;
+    // Model slots (cpk_device_reserve_models): the reserved count (0: a plain batch), the models of the next run, the
+    // device table the SLOTS kernels read and its pinned source, and the doubles of dExpect ([slot][wave][128] per class)
+    int modelSlots = 0, activeModels = 1;
+    CpkSlotModel *dSlots = nullptr, *hSlots = nullptr;
+    int64_t expectDoubles = 0;
     bool uploadTimed = true;
     double h2dMs = 0.0;
     hipStream_t lastStream = nullptr;
@@ -679,6 +684,7 @@ static void shell_delete(CpkDevice *d) {  // the shell's device is current
     if (d->evUp1) (void)hipEventDestroy(d->evUp1);
     if (d->evModel) (void)hipEventDestroy(d->evModel);
     if (d->hModel) (void)hipHostFree(d->hModel);
+    if (d->hSlots) (void)hipHostFree(d->hSlots);
     if (d->io) (void)hipStreamDestroy(d->io);
     for (int k = 0; k < kMaxClasses; k++) {
         if (d->sideStream[k]) (void)hipStreamDestroy(d->sideStream[k]);
@@ -785,6 +791,7 @@ static void free_all(CpkDevice *d) {
     d->dCand = nullptr;
     d->dForward = nullptr;
     d->dExpect = nullptr;
+    d->dSlots = nullptr;
     d->dCounts = d->dSegStarts = d->dSegCounts = d->dTriples = nullptr;
     cpk_host_free(d->hostCounts);
     d->hostCounts = nullptr;
@@ -816,6 +823,8 @@ extern "C" void cpk_device_destroy(CpkDevice *d) {
         d->classes.clear();
         ran_set(d, false);
         d->lastStream = nullptr;
+        d->modelSlots = 0;
+        d->activeModels = 1;
         std::lock_guard<std::mutex> lock(g_cacheMutex);
         if (g_shells[d->device].size() < 16) {
             g_shells[d->device].push_back(d);
@@ -907,6 +916,27 @@ static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regio
     }
 }
 
+static KConsts kconsts_of(const CpkModel *model) {
+    return KConsts{model->matchContinue, model->matchFromShortX, model->matchFromShortY, model->matchFromLongX,
+                   model->matchFromLongY, model->shortOpenX, model->shortOpenY, model->shortExtendX,
+                   model->shortExtendY, model->shortSwitchToX, model->shortSwitchToY, model->longOpenX,
+                   model->longOpenY, model->longExtendX, model->longExtendY, model->threshold};
+}
+// the waves of a run with the batch's active models, over all classes (cpecan_stats::wavesPerLaunch)
+static void count_waves(CpkDevice *d) {
+    d->totalWaves = 0;
+    for (const LaunchClass &c : d->classes)
+        d->totalWaves += (c.split && c.wavesTrace > c.waves ? c.wavesTrace : c.wavesWith(d->activeModels)) * (c.threads / CPK_WAVE);
+}
+
+// Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch).
+extern "C" int cpk_device_reserve_models(CpkDevice *d, int nSlots) {
+    if (nSlots < 0 || nSlots > CPECAN_MAX_MODEL_SLOTS) return CPECAN_EINVAL;
+    d->modelSlots = nSlots;
+    d->activeModels = 1;
+    return CPECAN_OK;
+}
+
 extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const CpkModel *model, CpkRegion *regions,
                                  const cpk_anchor_t *anchors, int anchorStride, int64_t nAnchors, const int32_t *runs, int64_t nRuns,
                                  int64_t nDiags, int64_t expansion, int dynamic,
@@ -918,10 +948,8 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     d->kernelMsAccum = 0.0;
     d->fusedRetried = false;
     d->geo = *geo;
-    d->kc = KConsts{model->matchContinue, model->matchFromShortX, model->matchFromShortY, model->matchFromLongX,
-                    model->matchFromLongY, model->shortOpenX, model->shortOpenY, model->shortExtendX,
-                    model->shortExtendY, model->shortSwitchToX, model->shortSwitchToY, model->longOpenX,
-                    model->longOpenY, model->longExtendX, model->longExtendY, model->threshold};
+    d->kc = kconsts_of(model);
+    d->activeModels = 1;
     d->nLists = nLists;
     d->nSegs = nSegs;
     d->nDiags = nDiags;
@@ -939,8 +967,8 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     dev.idleCachedBytes = cache_bytes(d->device);
     dev.othersAlive = d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0;  // (this batch no longer counts: ran_set above)
     const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
-    if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, &d->classes)) return rc;
-    d->totalWaves = 0;
+    if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, d->modelSlots, &d->classes)) return rc;
+    const int slotCount = d->modelSlots > 0 ? d->modelSlots : 1;
     {
         // (the rings start 64 doubles into their block and the block ends 256 doubles behind them: the streamed traceback's
         // prefetch reads up to 63 words in front of a diagonal's row and up to 191 behind it, Sweep::tracebackAbs)
@@ -960,8 +988,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
             oTot += c.subSlots * c.totEl;
             oBring += c.subSlots * c.bringEl;
             oGroll += c.subSlots * c.grollEl;
-            oExpect += (int64_t)c.waves * (c.threads / CPK_WAVE) * 128;  // a partial result per wave
-            d->totalWaves += (c.split && c.wavesTrace > c.waves ? c.wavesTrace : c.waves) * (c.threads / CPK_WAVE);
+            oExpect += (int64_t)slotCount * c.waves * (c.threads / CPK_WAVE) * 128;  // a partial result per wave (and slot)
             if (c.ldsBytes > kLdsPathMaxBytes) {
                 HIP_TRY(hipFuncSetAttribute((const void *)c.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
                 if (c.fnTrace)
@@ -977,7 +1004,9 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
             if (int rc = dev_alloc(d, &d->dGroll, (size_t)oGroll)) return rc;
         if (oBring > 0)
             if (int rc = dev_alloc(d, &d->dBring, (size_t)oBring)) return rc;
-        if (int rc = dev_alloc(d, &d->dExpect, (size_t)(oExpect > 0 ? oExpect : 128))) return rc;
+        d->expectDoubles = oExpect > 0 ? oExpect : 128;
+        if (int rc = dev_alloc(d, &d->dExpect, (size_t)d->expectDoubles)) return rc;
+        count_waves(d);
     }
 
     if (int rc = dev_alloc(d, &d->dRegions, (size_t)geo->nRegions)) return rc;
@@ -991,7 +1020,9 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     if (int rc = dev_alloc(d, &d->dSegs, (size_t)nSegs)) return rc;
     if (int rc = dev_alloc(d, &d->dSymbols, (size_t)nSymbolBytes)) return rc;
     if (int rc = dev_alloc(d, &d->dModel, 1)) return rc;
-    if (int rc = dev_alloc(d, &d->dForward, (size_t)geo->nRegions)) return rc;
+    if (int rc = dev_alloc(d, &d->dForward, (size_t)slotCount * geo->nRegions)) return rc;
+    if (d->modelSlots > 0)
+        if (int rc = dev_alloc(d, &d->dSlots, (size_t)d->modelSlots)) return rc;
     {
         const size_t nC = (size_t)nLists * geo->nRegions, nS = (size_t)nLists * (nSegs ? nSegs : 1);
         const size_t words = (nC + 63) / 64 * 64 + 2 * ((nS + 63) / 64 * 64);
@@ -1038,7 +1069,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         auto staged = [](const void *p, size_t bytes) { return (bytes > kStageMaxCopy || host_is_pinned(p, bytes)) ? (size_t)0 : bytes + 256; };
         if (int rc = stage_reserve(d, staged(regions, sizeof(CpkRegion) * (size_t)geo->nRegions) + staged(runs ? (const void *)runs : (const void *)anchors, anchorBytes) +
                                       staged(segs, sizeof(CpkSegment) * (size_t)nSegs) + staged(symbols, (size_t)nSymbolBytes) +
-                                      sizeof(CpkModel) + sizeof(CpkItem) * items.size() + 8 * 256))
+                                      sizeof(CpkModel) + sizeof(CpkSlotModel) + sizeof(CpkItem) * items.size() + 9 * 256))
             return rc;
     }
     if (!items.empty())
@@ -1063,6 +1094,10 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         // (the symbols and the model go first: nothing but the table build is then between the last copy and the sweep)
         if (int rc = staged_h2d(d, d->dSymbols, symbols, (size_t)nSymbolBytes, &stageAt)) return rc;
         if (int rc = staged_h2d(d, d->dModel, model, sizeof(CpkModel), &stageAt)) return rc;
+        if (d->dSlots) {  // a reserved batch starts with its own model in slot 0
+            const CpkSlotModel s0{d->kc, *model};
+            if (int rc = staged_h2d(d, d->dSlots, &s0, sizeof s0, &stageAt)) return rc;
+        }
         // the regions of split classes: one wave per region (cpk_table_gather.inl); every other region: one thread
         // (CPECAN_TABLE_WAVE=0: one thread for all, as rounds 1-3 -- tests compare the two)
         const char *twEnv = getenv("CPECAN_TABLE_WAVE");
@@ -1093,27 +1128,37 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
 // next launch); the priors and padded emissions are copied into dModel on the batch's own stream, behind the stop event
 // of the last run -- a sweep still in flight reads the old table to its end -- and the next sweep waits for the copy
 // through evUp1, as it waits for the upload's copies.
-extern "C" int cpk_device_set_model(CpkDevice *d, const CpkModel *model) {
+// n models (cpk_device_set_models) go the same way into the slot table of a reserved batch; slot 0 is *dModel as well.
+extern "C" int cpk_device_set_models(CpkDevice *d, const CpkModel *models, int n) {
     CPK_ON_DEVICE(d->device);
     if (!d->dModel) {
         cpk_set_error("set_model before upload");
         return CPECAN_ESTATE;
     }
+    if (n < 1 || n > (d->modelSlots > 0 ? d->modelSlots : 1)) {
+        cpk_set_error("set_models: %d models for a batch that reserved %d", n, d->modelSlots);
+        return CPECAN_EINVAL;
+    }
     if (!d->hModel) HIP_TRY(hipHostMalloc(&d->hModel, sizeof(CpkModel), hipHostMallocDefault));
+    if (d->dSlots && !d->hSlots) HIP_TRY(hipHostMalloc(&d->hSlots, sizeof(CpkSlotModel) * CPECAN_MAX_MODEL_SLOTS, hipHostMallocDefault));
     if (!d->evModel) HIP_TRY(hipEventCreateWithFlags(&d->evModel, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(d->evModel));  // the previous model copy has left the pinned block
-    *d->hModel = *model;
+    *d->hModel = models[0];
     hipStream_t io = d->io;
     if (d->ran) HIP_TRY(hipStreamWaitEvent(io, d->evStop, 0));
     HIP_TRY(hipMemcpyAsync(d->dModel, d->hModel, sizeof(CpkModel), hipMemcpyHostToDevice, io));
+    if (d->dSlots) {
+        for (int k = 0; k < n; k++) d->hSlots[k] = CpkSlotModel{kconsts_of(&models[k]), models[k]};
+        HIP_TRY(hipMemcpyAsync(d->dSlots, d->hSlots, sizeof(CpkSlotModel) * (size_t)n, hipMemcpyHostToDevice, io));
+    }
     HIP_TRY(hipEventRecord(d->evModel, io));
     HIP_TRY(hipEventRecord(d->evUp1, io));
-    d->kc = KConsts{model->matchContinue, model->matchFromShortX, model->matchFromShortY, model->matchFromLongX,
-                    model->matchFromLongY, model->shortOpenX, model->shortOpenY, model->shortExtendX,
-                    model->shortExtendY, model->shortSwitchToX, model->shortSwitchToY, model->longOpenX,
-                    model->longOpenY, model->longExtendX, model->longExtendY, model->threshold};
+    d->kc = kconsts_of(&models[0]);
+    d->activeModels = n;
+    count_waves(d);
     return CPECAN_OK;
 }
+extern "C" int cpk_device_set_model(CpkDevice *d, const CpkModel *model) { return cpk_device_set_models(d, model, 1); }
 
 // duration of the upload's copies (valid once the batch has run: the sweep waited for them)
 extern "C" double cpk_device_h2d_ms(CpkDevice *d) {
@@ -1192,11 +1237,13 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
     a.expectOut = d->dExpect;
     a.dbgFb = d->dDbgFb;
     a.dbgTotals = d->dDbgTotals;
+    a.slotModels = d->dSlots;
+    a.nModels = d->dSlots ? d->activeModels : 0;
     HIP_TRY(hipStreamWaitEvent(st, d->evUp1, 0));  // the upload's copies and the table build (the batch's own stream)
     HIP_TRY(hipMemsetAsync(d->dQueue, 0, 2 * kMaxClasses * sizeof(unsigned int), st));
     if (d->dProgress) HIP_TRY(hipMemsetAsync(d->dProgress, 0, sizeof(int) * ((size_t)d->geo.nRegions + 1), st));
     if (d->geo.emit == CPECAN_EMIT_EXPECT)
-        HIP_TRY(hipMemsetAsync(d->dExpect, 0, sizeof(double) * 128 * (size_t)(d->totalWaves > 0 ? d->totalWaves : 1), st));
+        HIP_TRY(hipMemsetAsync(d->dExpect, 0, sizeof(double) * (size_t)(d->dSlots ? d->expectDoubles : 128 * (int64_t)(d->totalWaves > 0 ? d->totalWaves : 1)), st));
     HIP_TRY(hipEventRecord(d->evStart, st));
     // one launch per size class, side by side: the last class (the widest regions, usually the bulk of the work) on the
     // caller's stream, the others on streams of their own, joined below
@@ -1239,7 +1286,7 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
         }
         hipStream_t cs = onCaller ? st : d->sideStream[i];
         if (!onCaller) HIP_TRY(hipStreamWaitEvent(cs, d->evStart, 0));
-        hipLaunchKernelGGL(c.fn, dim3((unsigned)c.waves), dim3((unsigned)c.threads), c.firstLdsBytes(), cs, p);
+        hipLaunchKernelGGL(c.fn, dim3((unsigned)c.wavesWith(d->activeModels)), dim3((unsigned)c.threads), c.firstLdsBytes(), cs, p);
         HIP_TRY(hipGetLastError());
         if (c.split && !c.fused) {  // the tracebacks of the class's regions, one queue item each, behind the forward launch
             KArgs t = p;
@@ -1306,10 +1353,26 @@ extern "C" int cpk_device_download(CpkDevice *d, int32_t *counts, int32_t *segSt
     HIP_TRY(hipStreamSynchronize(io));
     HIP_TRY(hipEventElapsedTime(&ms, d->evA, d->evB));
     if (d2hMs) *d2hMs = ms;
-    if (expect && d->geo.emit == kEmitForward) {
-        HIP_TRY(hipMemcpyAsync(expect, d->dForward, sizeof(double) * (size_t)d->geo.nRegions, hipMemcpyDeviceToHost, io));
+    if (expect && d->geo.emit == kEmitForward) {  // [slot][nRegions]
+        HIP_TRY(hipMemcpyAsync(expect, d->dForward, sizeof(double) * (size_t)d->activeModels * d->geo.nRegions, hipMemcpyDeviceToHost, io));
         HIP_TRY(hipStreamSynchronize(io));
     }
+    if (expect && d->geo.emit == CPECAN_EMIT_EXPECT && d->dSlots) {
+        // [slot][106]: per slot, the partials of every class's waves in class and wave order, as below for a plain batch
+        std::vector<double> part((size_t)d->expectDoubles);
+        HIP_TRY(hipMemcpyAsync(part.data(), d->dExpect, sizeof(double) * part.size(), hipMemcpyDeviceToHost, io));
+        HIP_TRY(hipStreamSynchronize(io));
+        for (int s = 0; s < d->activeModels; s++) {
+            double *sum = expect + (size_t)s * 106;
+            for (int i = 0; i < 106; i++) sum[i] = 0.0;
+            for (const LaunchClass &c : d->classes) {
+                const int64_t nW = (int64_t)c.wavesWith(d->activeModels) * (c.threads / CPK_WAVE);
+                const double *base = part.data() + c.oExpect + (size_t)s * nW * 128;
+                for (int64_t w = 0; w < nW; w++)
+                    for (int i = 0; i < 106; i++) sum[i] += base[(size_t)w * 128 + i];
+            }
+        }
+    } else
     if (expect && d->geo.emit == CPECAN_EMIT_EXPECT) {
         // sum the per-wave partials (every launched wave wrote its 106 values, zeros included)
         const int nWaves = d->totalWaves;

@@ -398,6 +398,7 @@ struct cpecan_realigner {
     int device;
     int devices[CPK_REALIGN_MAX_DEVICES]; /* cpecan_realigner_set_devices: the shards of a call, one per entry */
     int nDevices;                         /* 0 or 1: everything on `device` */
+    int expectModelSlots;                 /* cpecan_expect_set_reserve_models: slots of the sets created from here on (0: none) */
     SeqEntry *seqs; /* open addressing, capacity a power of two */
     int64_t nSeqs, capSeqs;
     char *finalPairsPath, *allPairsPath;
@@ -1132,7 +1133,18 @@ struct cpecan_expect_set {
     int32_t type;                                /* the model type the batches were planned for */
     cpecan_batch *batches[CPK_REALIGN_MAX_DEVICES]; /* NULL: an empty shard */
     int devices[CPK_REALIGN_MAX_DEVICES];
+    int modelSlots;                              /* models the batches reserved (0: plain batches) */
 };
+
+int cpecan_expect_set_reserve_models(cpecan_realigner *r, int nSlots) {
+    if (!r) return CPECAN_EINVAL;
+    if (nSlots < 0 || nSlots > CPECAN_MAX_MODEL_SLOTS) { /* 0: plain batches again */
+        cpk_set_error("reserve_models: %d slots, 1 to %d are possible", nSlots, CPECAN_MAX_MODEL_SLOTS);
+        return CPECAN_EINVAL;
+    }
+    r->expectModelSlots = nSlots;
+    return CPECAN_OK;
+}
 
 void cpecan_expect_set_destroy(cpecan_expect_set *s) {
     if (!s) return;
@@ -1148,6 +1160,7 @@ static int expect_shard_create(const cpecan_realigner *r, const cpecan_cigar *in
     if (rc == CPECAN_OK) rc = prepare_and_add(r, in, n, items, b);
     for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
     free(items);
+    if (rc == CPECAN_OK && r->expectModelSlots > 0) rc = cpecan_batch_reserve_models(b, r->expectModelSlots);
     if (rc == CPECAN_OK) {
         rc = cpecan_batch_upload(b);
         if (rc == CPECAN_ENOMEM) {
@@ -1172,6 +1185,7 @@ int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const
     cpecan_expect_set *s = calloc(1, sizeof *s);
     if (!s) return CPECAN_ENOMEM;
     s->type = r->model.type;
+    s->modelSlots = r->expectModelSlots;
     s->nShards = r->nDevices > 1 ? r->nDevices : 1;
     int64_t bounds[CPK_REALIGN_MAX_DEVICES + 1];
     int rc = cpecan_realign_shard_bounds(in, n, r->opt.params.diagonalExpansion, s->nShards, bounds);
@@ -1201,6 +1215,28 @@ int cpecan_expect_set_run(cpecan_expect_set *s, const cpecan_model *m, cpecan_hm
         if (!s->batches[k]) continue;
         int rc = cpecan_batch_download(s->batches[k]);
         if (rc == CPECAN_OK) rc = cpecan_batch_expectations(s->batches[k], acc);
+        if (rc != CPECAN_OK) return rc;
+    }
+    return CPECAN_OK;
+}
+
+int cpecan_expect_set_run_models(cpecan_expect_set *s, const cpecan_model *models, int n, cpecan_hmm *accs) {
+    if (!s || !models || !accs) return CPECAN_EINVAL;
+    if (n < 1 || n > (s->modelSlots > 0 ? s->modelSlots : 1)) {
+        cpk_set_error("run_models: %d models for a set that reserved %d", n, s->modelSlots);
+        return CPECAN_EINVAL;
+    }
+    /* every shard queues its one launch before the first download waits */
+    for (int k = 0; k < s->nShards; k++) {
+        if (!s->batches[k]) continue;
+        int rc = cpecan_batch_set_models(s->batches[k], models, n);
+        if (rc == CPECAN_OK) rc = cpecan_batch_run(s->batches[k], NULL);
+        if (rc != CPECAN_OK) return rc;
+    }
+    for (int k = 0; k < s->nShards; k++) { /* per slot, summed in shard order, as cpecan_expect_set_run does */
+        if (!s->batches[k]) continue;
+        int rc = cpecan_batch_download(s->batches[k]);
+        for (int j = 0; rc == CPECAN_OK && j < n; j++) rc = cpecan_batch_expectations_slot(s->batches[k], j, &accs[j]);
         if (rc != CPECAN_OK) return rc;
     }
     return CPECAN_OK;

@@ -19,6 +19,16 @@ struct KConsts {
     double threshold;
 };
 
+// A reserved batch (cpecan_batch_reserve_models) runs several models over the same regions in one launch: the queue of a
+// size class holds nModels x regionCount VIRTUAL regions, slot-major, and the model of slot k -- the transitions a plain
+// launch carries in its kernel arguments and the priors and emissions it reads from *KArgs::model -- is entry k of this
+// device table.  A wave reads it outside the diagonal loops only: when the slot of the region it drew differs from the
+// one whose weights it holds.
+struct CpkSlotModel {
+    KConsts kc;
+    CpkModel m;
+};
+
 struct KArgs {
     KConsts kc;
     const CpkRegion *regions;
@@ -50,6 +60,11 @@ struct KArgs {
     double *expectOut;   // [slots][128] per-wave expectation partial sums (expectation mode)
     double *dbgFb;
     double *dbgTotals;
+    // Reserved batches only (the SLOTS builds of the kernels; null / 0 otherwise and never read): the slot table and the
+    // models of this run.  forwardOut is [slot][nRegions] then and expectOut [slot][wave][128].
+    const CpkSlotModel *slotModels;
+    int32_t nModels;
+    int32_t reserved1;
 };
 
 // logAdd, impl/pairwiseAligner.c:287-307: with hi = max(x, y), lo = min(x, y), d = hi - lo the reference returns hi when

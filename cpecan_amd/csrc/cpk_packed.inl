@@ -45,9 +45,12 @@ __host__ __device__ constexpr int pack_group_bytes(int S, int gw) {  // a multip
 // backward steps is 20 ms whatever else the chip does -- BASELINE config 4 took 20.2 ms with 6 000 pairs and 29.3 with
 // 50 000 (profiles/r04_config4_chain_bound.txt).  Split, the chain is the forward steps alone and the tracebacks of a
 // long region run side by side.
-template <int S, int GW, int EMIT, bool DYN = false, int MODE = kModeWhole>  // EMIT: CPECAN_EMIT_MATCH, _INDEL or _EXPECT
+// SLOTS: the build for reserved batches (cf. cpecan_pairhmm_sweep).  A wave steps its G regions under ONE weight table, so
+// a packed group never mixes slots: the queue counts GROUPS of G regions, ceil(regionCount / G) per slot, slot-major.
+template <int S, int GW, int EMIT, bool DYN = false, int MODE = kModeWhole, bool SLOTS = false>  // EMIT: CPECAN_EMIT_MATCH, _INDEL or _EXPECT
 __global__ void __launch_bounds__(CPK_WAVE) __attribute__((amdgpu_waves_per_eu(CPK_PACKED_WAVES, CPK_PACKED_WAVES)))
 cpecan_pairhmm_packed(const KArgs a) {
+    static_assert(!SLOTS || (MODE == kModeWhole && EMIT == CPECAN_EMIT_EXPECT), "model slots: expectation emitter, whole regions");
     static_assert(MODE == kModeWhole || MODE == kModeForward || MODE == kModeTrace, "packed kernel: whole regions, or the two launches of a split class");
     static_assert(MODE == kModeWhole || (EMIT == CPECAN_EMIT_MATCH && !DYN), "split classes: match emitter, fixed expansion");
     constexpr bool kSplit = MODE != kModeWhole;
@@ -59,12 +62,14 @@ cpecan_pairhmm_packed(const KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
     const int g = lane / GW, c = lane % GW;
-    const CpkModel &m = *a.model;
+    const CpkModel *mp = SLOTS ? &a.slotModels[0].m : a.model;  // (SLOTS: the model of the slot this wave holds)
+    int curSlot = 0;
 
     fill_cubics(lds);
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
     double *wt = lds + kLdsCubics + kLdsEm;
-    fill_weights<S>(wt, m, a.kc, lane);
+    if constexpr (SLOTS) fill_weights<S>(wt, *mp, a.slotModels[0].kc, lane);
+    else fill_weights<S>(wt, *mp, a.kc, lane);
     constexpr bool kExpect = EMIT == CPECAN_EMIT_EXPECT;
     // Indel emitter (round 4; diagonalCalculationPosteriorProbs, pairwiseAligner.c:691-733): three lists -- match, gapX,
     // gapY -- of one segment.  Round 3 built it with three candidate lists live in the traceback: 55 spilled registers,
@@ -101,10 +106,59 @@ cpecan_pairhmm_packed(const KArgs a) {
     const float logThr = (float)log(a.kc.threshold);
     const double thr = a.kc.threshold;
 
+    // one partial result per wave (SLOTS: per slot and wave), as in the sweep kernel: [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood
+    auto flushExpect = [&](int vs) __attribute__((always_inline)) {
+        __syncthreads();
+        double *dst = a.expectOut + (SLOTS ? (size_t)vs * gridDim.x + blockIdx.x : (size_t)blockIdx.x) * 128;
+        constexpr int kFrom5[13] = {0, 1, 0, 3, 0, 1, 2, 3, 4, 0, 2, 0, 4}, kTo5[13] = {1, 1, 3, 3, 0, 0, 0, 0, 0, 2, 2, 4, 4};
+        constexpr int kFrom3[9] = {0, 1, 2, 0, 1, 2, 0, 2, 1}, kTo3[9] = {1, 1, 1, 0, 0, 0, 2, 2, 2};
+        for (int i = lane; i < 25; i += CPK_WAVE) dst[i] = 0.0;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kNT; i++) {
+            double v = tAcc[i];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            const int idx = S == 5 ? kFrom5[i] * 5 + kTo5[i] : kFrom3[i] * 3 + kTo3[i];
+            if (lane == 0) dst[idx] = v;
+        }
+        for (int i = lane; i < 80; i += CPK_WAVE) {
+            double e = 0.0;
+            for (int k = 0; k < kExpectCopies; k++) e += eLds[k * 80 + i];
+            dst[25 + i] = e;
+        }
+        double lk = likelihood;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) lk += __shfl_xor(lk, off);
+        if (lane == 0) dst[105] = lk;
+    };
+
     for (;;) {
-        const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? (unsigned)G : 0u);
-        const int tk = __builtin_amdgcn_readfirstlane((int)ticket);
-        if (tk >= a.regionCount) break;
+        int tk;
+        if constexpr (SLOTS) {
+            const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? 1u : 0u);  // one GROUP of G regions of one slot
+            const int gt = __builtin_amdgcn_readfirstlane((int)ticket);
+            const int groupsPerSlot = (a.regionCount + G - 1) / G;
+            if (gt >= groupsPerSlot * a.nModels) break;
+            const int vs = gt / groupsPerSlot;
+            tk = (gt - vs * groupsPerSlot) * G;
+            if (vs != curSlot) {  // what this wave has summed belongs to the slot it leaves
+                flushExpect(curSlot);
+#pragma unroll
+                for (int i = 0; i < kNT; i++) tAcc[i] = 0.0;
+                likelihood = 0.0;
+                __syncthreads();
+                for (int i = lane; i < kExpectCopies * 80; i += CPK_WAVE) eLds[i] = 0.0;
+                curSlot = vs;
+                mp = &a.slotModels[vs].m;
+                fill_weights<S>(wt, *mp, a.slotModels[vs].kc, lane);
+                __syncthreads();
+            }
+        } else {
+            const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? (unsigned)G : 0u);
+            tk = __builtin_amdgcn_readfirstlane((int)ticket);
+            if (tk >= a.regionCount) break;
+        }
         const bool have = tk + g < a.regionCount;
         // kModeTrace: the queue holds (region, segment) items, longest first (a.regionCount of them); else regions
         const int itemSeg = MODE == kModeTrace ? a.items[have ? tk + g : tk].seg : 0;
@@ -211,7 +265,7 @@ cpecan_pairhmm_packed(const KArgs a) {
         if (nSeg > 0 && MODE != kModeTrace) {
             const int4 t0 = *reinterpret_cast<const int4 *>(table);
             e1 = e2 = unpack(t0);
-            const double *startPrior = rg.raggedLeft ? m.raggedStart : m.start;
+            const double *startPrior = rg.raggedLeft ? mp->raggedStart : mp->start;
             if (c < S) {  // diagonal 0: the single cell (0,0) holds the start prior (pairwiseAligner.c:776-777)
                 fbuf1(0)[c] = startPrior[c];
                 ringAt(e1)[SW::ringIdx(1, c, 0)] = startPrior[c];
@@ -278,7 +332,7 @@ cpecan_pairhmm_packed(const KArgs a) {
             }
             if (MODE == kModeForward) continue;  // the tracebacks of a split class are the items of the next launch
             // ---------------- traceback of the segment (pairwiseAligner.c:796-862) ----------------
-            const double *endPrior = (segOn && sg.atEnd && rg.raggedRight) ? m.raggedEnd : m.end;
+            const double *endPrior = (segOn && sg.atEnd && rg.raggedRight) ? mp->raggedEnd : mp->end;
             double ep[S];
 #pragma unroll
             for (int s = 0; s < S; s++) ep[s] = endPrior[s];
@@ -696,30 +750,5 @@ cpecan_pairhmm_packed(const KArgs a) {
             }
         }
     }
-    if (kExpect) {
-        // one partial result per wave, as in the sweep kernel: [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood
-        __syncthreads();
-        double *dst = a.expectOut + (size_t)blockIdx.x * 128;
-        constexpr int kFrom5[13] = {0, 1, 0, 3, 0, 1, 2, 3, 4, 0, 2, 0, 4}, kTo5[13] = {1, 1, 3, 3, 0, 0, 0, 0, 0, 2, 2, 4, 4};
-        constexpr int kFrom3[9] = {0, 1, 2, 0, 1, 2, 0, 2, 1}, kTo3[9] = {1, 1, 1, 0, 0, 0, 2, 2, 2};
-        for (int i = lane; i < 25; i += CPK_WAVE) dst[i] = 0.0;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < kNT; i++) {
-            double v = tAcc[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            const int idx = S == 5 ? kFrom5[i] * 5 + kTo5[i] : kFrom3[i] * 3 + kTo3[i];
-            if (lane == 0) dst[idx] = v;
-        }
-        for (int i = lane; i < 80; i += CPK_WAVE) {
-            double e = 0.0;
-            for (int k = 0; k < kExpectCopies; k++) e += eLds[k * 80 + i];
-            dst[25 + i] = e;
-        }
-        double lk = likelihood;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) lk += __shfl_xor(lk, off);
-        if (lane == 0) dst[105] = lk;
-    }
+    if (kExpect) flushExpect(curSlot);
 }

@@ -13,6 +13,11 @@ struct LaunchClass {
     KernelFn fn = nullptr;
     CpkGeometry geo{};   // what the kernel reads: the scalar fields describe this class
     int waves = 0;       // workgroups of the launch
+    // A reserved batch (model slots, KArgs::slotModels): the SLOTS build of the kernel, and the workgroups of a run with
+    // t models, 1 <= t <= the reserved count -- `waves` is the most of them, which the per-wave scratch is sized for
+    bool slots = false;
+    int wavesFor[CPECAN_MAX_MODEL_SLOTS + 1] = {};
+    int wavesWith(int nModels) const { return slots && wavesFor[nModels] < waves ? wavesFor[nModels] : waves; }
     int threads = CPK_WAVE;  // threads per workgroup: one wave, or the waves of a team
     int64_t subSlots = 0;  // scratch slots: one per wave (sweep) or one per region group of a wave (packed)
     size_t ldsBytes = 0;
@@ -37,8 +42,20 @@ struct LaunchClass {
     }
 };
 
-static KernelFn pick_packed_kernel(const CpkGeometry &g, int cls, bool dynamic) {  // class k: groups of 8 << k lanes
+static KernelFn pick_packed_kernel(const CpkGeometry &g, int cls, bool dynamic, bool slots = false) {  // class k: groups of 8 << k lanes
     const bool five = g.nStates == 5;
+    if (slots) {  // reserved batches: the expectation emitter alone reaches the packed kernel (a FORWARD batch has no narrow class)
+#define CPK_PICK_PACKED_SLOTS(D)                                                                                                          \
+    if (g.emit == CPECAN_EMIT_EXPECT && dynamic == (D)) switch (cls) {                                                                  \
+            case 0: return five ? cpecan_pairhmm_packed<5, 8, CPECAN_EMIT_EXPECT, (D), kModeWhole, true> : cpecan_pairhmm_packed<3, 8, CPECAN_EMIT_EXPECT, (D), kModeWhole, true>;    \
+            case 1: return five ? cpecan_pairhmm_packed<5, 16, CPECAN_EMIT_EXPECT, (D), kModeWhole, true> : cpecan_pairhmm_packed<3, 16, CPECAN_EMIT_EXPECT, (D), kModeWhole, true>;  \
+            case 2: return five ? cpecan_pairhmm_packed<5, 32, CPECAN_EMIT_EXPECT, (D), kModeWhole, true> : cpecan_pairhmm_packed<3, 32, CPECAN_EMIT_EXPECT, (D), kModeWhole, true>;  \
+        }
+        CPK_PICK_PACKED_SLOTS(false)
+        CPK_PICK_PACKED_SLOTS(true)
+#undef CPK_PICK_PACKED_SLOTS
+        return nullptr;
+    }
 #define CPK_PICK_PACKED(E, D)                                                                                               \
     if (g.emit == (E) && dynamic == (D)) switch (cls) {                                                                     \
             case 0: return five ? cpecan_pairhmm_packed<5, 8, (E), (D)> : cpecan_pairhmm_packed<3, 8, (E), (D)>;            \
@@ -136,8 +153,28 @@ static KernelFn pick_dense_kernel(const CpkGeometry &g) {  // one wave per regio
     return !g.useGlobalRoll ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeWhole, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeWhole, 3>;
 }
 
-static KernelFn pick_kernel(const CpkGeometry &g) {
+static KernelFn pick_kernel(const CpkGeometry &g, bool slots = false) {
     const bool fast = !g.useGlobalRoll;  // second template argument = FAST (LDS rolling buffers + LDS symbol strings)
+    if (slots) {  // reserved batches (expectation and forward emitters): the same forms, the SLOTS builds
+        if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep == 1)
+            return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1, true>
+                                  : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1, true>;
+        if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep)
+            return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2, true>
+                                  : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2, true>;
+#define CPK_PICK_SLOTS(E)                                                                                                             \
+    if (g.emit == (E)) {                                                                                                              \
+        if (g.nStates == 5)                                                                                                           \
+            return fast ? cpecan_pairhmm_sweep<5, true, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>                           \
+                        : cpecan_pairhmm_sweep<5, false, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>;                          \
+        return fast ? cpecan_pairhmm_sweep<3, true, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>                               \
+                    : cpecan_pairhmm_sweep<3, false, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>;                              \
+    }
+        CPK_PICK_SLOTS(CPECAN_EMIT_EXPECT)
+        CPK_PICK_SLOTS(kEmitForward)
+#undef CPK_PICK_SLOTS
+        return nullptr;
+    }
     if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep == 1)  // no diagonal wider than one 64-lane group
         return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1>
                               : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1>;
@@ -223,6 +260,7 @@ struct PlanInputs {
     int dynamic;
     const PlanDevice &dev;
     const PlanKnobs &knobs;
+    int modelSlots = 0;  // models reserved with cpecan_batch_reserve_models; 0: a plain batch
 };
 
 // Resident workgroups of `wavesPerWorkgroup` waves per CU.  hipOccupancyMaxActiveBlocksPerMultiprocessor answers 3 for
@@ -266,7 +304,8 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
     LaunchClass c;
     c.packed = true;
     c.k = k;
-    c.fn = pick_packed_kernel(geo, k, in.dynamic != 0);
+    c.slots = in.modelSlots > 0;
+    c.fn = pick_packed_kernel(geo, k, in.dynamic != 0, c.slots);
     if (!c.fn) {
         cpk_set_error("no packed kernel for emitter %d", geo.emit);
         return CPECAN_EINVAL;
@@ -333,6 +372,13 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
         cc.regionBase = (int)pBase;
         cc.regionCount = (int)pCount;
         int64_t waves = (pCount + G - 1) / G;
+        if (cc.slots) {  // t models: t times the groups, up to the wave slots of the chip
+            const int64_t groups = waves;
+            for (int t = 1; t <= in.modelSlots; t++) {
+                cc.wavesFor[t] = (int)(groups * t < slots ? groups * t : slots);
+                if (cc.wavesFor[t] > waves) waves = cc.wavesFor[t];
+            }
+        }
         if (waves > slots) waves = slots;
         cc.waves = (int)waves;
         cc.subSlots = waves * G;
@@ -450,7 +496,10 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
     const bool big = 2 * teamLds > kCuLdsBytes;
     if (wanted && (geo.emit == CPECAN_EMIT_MATCH || geo.emit == CPECAN_EMIT_INDEL || expect) && !geo.debug &&
         c.geo.maxWidth <= CPK_WAVE * kTeamWaves * (big ? 2 : 1) * kTeamGroups && teamLds <= kCuLdsBytes) {
-        if (expect)  // (round 4: the expectation emitter -- its second pass shared by the team's waves)
+        if (expect && c.slots)  // (reserved batches: the SLOTS build)
+            c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_EXPECT, true> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_EXPECT, true>)
+                          : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_EXPECT, true> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_EXPECT, true>);
+        else if (expect)  // (round 4: the expectation emitter -- its second pass shared by the team's waves)
             c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_EXPECT> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_EXPECT>)
                           : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_EXPECT> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_EXPECT>);
         else if (geo.emit == CPECAN_EMIT_INDEL)  // (round 4: the three lists of the indel emitter from the team as well)
@@ -639,7 +688,8 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     c.geo.useGlobalRoll = c.ldsBytes + 16 > kLdsPathMaxBytes;
     set_row_form(c, absWanted && !c.geo.useGlobalRoll, in.knobs);  // absolute positions are a form of the LDS rows
     plan_expect_in_sweep(c, in.knobs);
-    c.fn = pick_kernel(c.geo);
+    c.slots = in.modelSlots > 0;
+    c.fn = pick_kernel(c.geo, c.slots);
     if (!c.fn) {
         cpk_set_error("no kernel for emitter %d", geo.emit);
         return CPECAN_EINVAL;
@@ -654,6 +704,16 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     int64_t waves = (int64_t)perCU * in.dev.numCUs;
     if (waves > n) waves = n;
     waves = even_rounds(n, waves);
+    if (c.slots) {
+        // t models: t x n virtual regions -- an under-subscribed class gets more waves, a saturated one none.  (Rounds are
+        // evened out per t, so the count is not monotone in t: the scratch is sized for the most.)
+        const int64_t cap = (int64_t)perCU * in.dev.numCUs;
+        for (int t = 1; t <= in.modelSlots; t++) {
+            const int64_t v = n * t;
+            c.wavesFor[t] = (int)even_rounds(v, cap < v ? cap : v);
+            if (c.wavesFor[t] > waves) waves = c.wavesFor[t];
+        }
+    }
     c.waves = (int)waves;
     c.subSlots = waves;
     c.regionBase = base;
@@ -763,8 +823,12 @@ static int fit_to_memory(const PlanInputs &in, const PlanFixedSizes &sz, std::ve
 // The launches of a run: one per size class that has regions -- the split parts of the narrow classes, their whole
 // parts, then the wide classes -- fitted to the device's memory.
 static int plan_batch(const CpkGeometry &geo, const CpkRegion *regions, int dynamic, const PlanFixedSizes &sizes, const PlanDevice &dev,
-                      const PlanKnobs &knobs, std::vector<LaunchClass> *out) {
-    const PlanInputs in{geo, regions, dynamic, dev, knobs};
+                      const PlanKnobs &knobs, int modelSlots, std::vector<LaunchClass> *out) {
+    const PlanInputs in{geo, regions, dynamic, dev, knobs, modelSlots};
+    if (modelSlots > 0 && geo.emit != CPECAN_EMIT_EXPECT && geo.emit != kEmitForward) {
+        cpk_set_error("model slots: expectation and forward emitters only");
+        return CPECAN_EINVAL;
+    }
     out->clear();
     int regionAt = 0;
     std::vector<LaunchClass> packedSplit, packedWhole;

@@ -2153,14 +2153,21 @@ constexpr int kModeWhole = 0, kModeForward = 1, kModeTrace = 2, kModeFused = 3;
 // INSWEEP: expectation emitter, every diagonal of the class within one 64-lane group: the events are formed inside the
 // traceback (Sweep::tracebackExpect / scaleWindows) instead of in a second pass (Sweep::expectations)
 // (INSWEEP = 1: a class without a diagonal wider than 64 cells -- one group per diagonal, nothing kept for a second)
-template <int S, bool FAST, int EMIT, int MODE = kModeWhole, int WPS = CPK_SWEEP_WAVES, bool ABS = false, int INSWEEP = 0>
+// SLOTS: the build for reserved batches (KArgs::slotModels): nModels x regionCount virtual regions in the queue, slot-major.
+// Tickets ascend, so a wave sees the slots in non-decreasing order: at a slot change it writes the expectation sums it
+// holds to the old slot's partial result, starts them again from zero and refills its weight table -- at most nModels
+// times, outside the diagonal loops.  A template parameter, not a test at ticket time: the builds of plain batches are
+// the code they were (the five-state expectation kernels have no register to give away).
+template <int S, bool FAST, int EMIT, int MODE = kModeWhole, int WPS = CPK_SWEEP_WAVES, bool ABS = false, int INSWEEP = 0, bool SLOTS = false>
 __global__ void __launch_bounds__(CPK_WAVE) __attribute__((amdgpu_waves_per_eu(WPS, WPS)))
 cpecan_pairhmm_sweep(const KArgs a) {
+    static_assert(!SLOTS || (MODE == kModeWhole && (EMIT == CPECAN_EMIT_EXPECT || EMIT == kEmitForward)), "model slots: expectation and forward emitters, whole regions");
     static_assert(!ABS || (FAST && MODE != kModeWhole && EMIT == CPECAN_EMIT_MATCH), "absolute positions: split classes of the match emitter");
     static_assert(!INSWEEP || (FAST && MODE == kModeWhole && EMIT == CPECAN_EMIT_EXPECT), "in-sweep events: expectation emitter, LDS rows");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
-    const CpkModel &m = *a.model;
+    const CpkModel *mp = SLOTS ? &a.slotModels[0].m : a.model;  // (SLOTS: the model of the slot this wave holds)
+    int curSlot = 0;
     const int stride = a.geo.rollStride;
     constexpr int R = ABS ? S : 2 * S + 1;  // rows of the rolling buffers (Sweep::R; absolute positions: two arrays of S rows)
     const int rollDoubles = (ABS ? 2 * S : 2 * S + 1) * stride;
@@ -2170,7 +2177,8 @@ cpecan_pairhmm_sweep(const KArgs a) {
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
     double *em = lds + kLdsCubics;  // (no plain emission table any more: kLdsEm == 0, every term reads `wt`)
     double *wt = lds + kLdsCubics + kLdsEm;
-    fill_weights<S>(wt, m, a.kc, lane);
+    if constexpr (SLOTS) fill_weights<S>(wt, *mp, a.slotModels[0].kc, lane);
+    else fill_weights<S>(wt, *mp, a.kc, lane);
     double *eLds = lds + kLdsCubics + kLdsEm + kLdsWeights;  // emission-expectation sums of this wave (expectation emitter)
     constexpr int kECopies = lds_expect_copies(INSWEEP != 0);
     if (EMIT == CPECAN_EMIT_EXPECT)
@@ -2197,6 +2205,34 @@ cpecan_pairhmm_sweep(const KArgs a) {
     }
     __syncthreads();
 
+    // one partial result per resident wave (SLOTS: per slot and wave): [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood
+    auto flushExpect = [&](int vs) __attribute__((always_inline)) {
+        __syncthreads();
+        double *dst = a.expectOut + (SLOTS ? (size_t)vs * gridDim.x + blockIdx.x : (size_t)blockIdx.x) * 128;
+        constexpr int kFrom5[13] = {0, 1, 0, 3, 0, 1, 2, 3, 4, 0, 2, 0, 4}, kTo5[13] = {1, 1, 3, 3, 0, 0, 0, 0, 0, 2, 2, 4, 4};
+        constexpr int kFrom3[9] = {0, 1, 2, 0, 1, 2, 0, 2, 1}, kTo3[9] = {1, 1, 1, 0, 0, 0, 2, 2, 2};
+        for (int i = lane; i < 25; i += CPK_WAVE) dst[i] = 0.0;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kNT; i++) {
+            double v = tAcc[i];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            const int idx = S == 5 ? kFrom5[i] * 5 + kTo5[i] : kFrom3[i] * 3 + kTo3[i];
+            if (lane == 0) dst[idx] = v;
+        }
+        for (int i = lane; i < 80; i += CPK_WAVE) {
+            double e = 0.0;
+            for (int k = 0; k < kECopies; k++) e += eLds[k * 80 + i];
+            dst[25 + i] = e;
+        }
+        {  // every lane holds the totals of the diagonals whose first cell it computed (Sweep::expectations)
+            double v = likelihood;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            if (lane == 0) dst[105] = v;
+        }
+    };
     const size_t slot = blockIdx.x;
     for (;;) {
         // Every lane takes part in the ticket fetch (lane 0 adds 1, the others add 0; hipcc folds this into one
@@ -2210,7 +2246,26 @@ cpecan_pairhmm_sweep(const KArgs a) {
         const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? 1u : 0u);
 #endif
         const int tk = __builtin_amdgcn_readfirstlane((int)ticket);
-        if (tk >= a.regionCount + (MODE == kModeFused ? a.itemCount : 0)) break;
+        int tkRegion = tk;  // (SLOTS: the region of virtual region tk)
+        if constexpr (SLOTS) {
+            if (tk >= a.regionCount * a.nModels) break;
+            const int vs = tk / a.regionCount;
+            tkRegion = tk - vs * a.regionCount;
+            if (vs != curSlot) {
+                if (EMIT == CPECAN_EMIT_EXPECT) {  // what this wave has summed belongs to the slot it leaves
+                    flushExpect(curSlot);
+#pragma unroll
+                    for (int i = 0; i < kNT; i++) tAcc[i] = 0.0;
+                    likelihood = 0.0;
+                    __syncthreads();
+                    for (int i = lane; i < kECopies * 80; i += CPK_WAVE) eLds[i] = 0.0;
+                }
+                curSlot = vs;
+                mp = &a.slotModels[vs].m;
+                fill_weights<S>(wt, *mp, a.slotModels[vs].kc, lane);
+                __syncthreads();
+            }
+        } else if (tk >= a.regionCount + (MODE == kModeFused ? a.itemCount : 0)) break;
         // kModeTrace: the queue holds (region, segment) items, longest first; kModeFused: regions, then items; else regions
         const bool traceRole = MODE == kModeTrace || (MODE == kModeFused && tk >= a.regionCount);  // wave-uniform
         const bool forwardRole = MODE == kModeForward || (MODE == kModeFused && !traceRole);
@@ -2224,7 +2279,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
             else __builtin_amdgcn_s_setprio(0);
         }
 #endif
-        const int r = traceRole ? a.items[ti].region : a.regionBase + tk;
+        const int r = traceRole ? a.items[ti].region : a.regionBase + tkRegion;
         const int itemSeg = traceRole ? a.items[ti].seg : 0;
 
         const CpkRegion &rg = a.regions[r];
@@ -2278,7 +2333,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
             double total = 0.0;  // LOG_ONE for two empty sequences (:889-891)
             if (N > 0) {
                 sw.dc.load(0);
-                const double *startPrior = rg.raggedLeft ? m.raggedStart : m.start;
+                const double *startPrior = rg.raggedLeft ? mp->raggedStart : mp->start;
                 const CpkDiag g0 = sw.dc.get(0, false);
                 double *cur0 = sw.fbuf1(0);
                 if (lane < S) cur0[lane] = startPrior[lane];
@@ -2294,7 +2349,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
                     }
                 }
                 if (FAST) sw.flushTail();
-                const double *endPrior = rg.raggedRight ? m.raggedEnd : m.end;
+                const double *endPrior = rg.raggedRight ? mp->raggedEnd : mp->end;
                 const double *last = sw.fbuf1(N);
                 const int W = sw.f1.width;
                 total = NEG_INF;  // dpDiagonal_dotProduct (:513-523) over the cells of diagonal N, every lane alike
@@ -2305,13 +2360,13 @@ cpecan_pairhmm_sweep(const KArgs a) {
                     total = logadd(lg, total, t);
                 }
             }
-            if (lane == 0) a.forwardOut[r] = total;
+            if (lane == 0) a.forwardOut[(SLOTS ? (size_t)curSlot * a.geo.nRegions : (size_t)0) + r] = total;
             continue;
         }
         if (N > 0) {
             sw.dc.load(0);
             // diagonal 0: the single cell (0,0) holds the start prior (pairwiseAligner.c:776-777)
-            const double *startPrior = rg.raggedLeft ? m.raggedStart : m.start;
+            const double *startPrior = rg.raggedLeft ? mp->raggedStart : mp->start;
             if (!traceRole) {
                 const CpkDiag g0 = sw.dc.get(0, false);
                 double *cur = sw.fbuf1(0);
@@ -2409,7 +2464,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
 #ifdef CPK_DIAGNOSTICS
                 if (a.geo.debug & 2) continue;  // diagnostic build only: time the forward sweep alone (no traceback, no output)
 #endif
-                const double *endPrior = (sg.atEnd && rg.raggedRight) ? m.raggedEnd : m.end;
+                const double *endPrior = (sg.atEnd && rg.raggedRight) ? mp->raggedEnd : mp->end;
                 int nCand[NL];
                 if constexpr (ABS) sw.template tracebackAbs<NL, true>(sg, endPrior, (a.geo.debug & 1) ? a.dbgFb + rg.dbgCellOff : nullptr, nCand);
                 else if constexpr (INSWEEP != 0) sw.tracebackExpect(sg, endPrior, (a.geo.debug & 1) ? a.dbgFb + rg.dbgCellOff : nullptr);
@@ -2457,32 +2512,5 @@ cpecan_pairhmm_sweep(const KArgs a) {
         for (int l = 0; l < NL; l++)
             if (MODE == kModeWhole && lane == 0) a.outCounts[(size_t)l * a.geo.nRegions + r] = count[l];
     }
-    if (EMIT == CPECAN_EMIT_EXPECT) {
-        // one partial result per resident wave: [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood
-        __syncthreads();
-        double *dst = a.expectOut + (size_t)blockIdx.x * 128;
-        constexpr int kFrom5[13] = {0, 1, 0, 3, 0, 1, 2, 3, 4, 0, 2, 0, 4}, kTo5[13] = {1, 1, 3, 3, 0, 0, 0, 0, 0, 2, 2, 4, 4};
-        constexpr int kFrom3[9] = {0, 1, 2, 0, 1, 2, 0, 2, 1}, kTo3[9] = {1, 1, 1, 0, 0, 0, 2, 2, 2};
-        for (int i = lane; i < 25; i += CPK_WAVE) dst[i] = 0.0;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < kNT; i++) {
-            double v = tAcc[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            const int idx = S == 5 ? kFrom5[i] * 5 + kTo5[i] : kFrom3[i] * 3 + kTo3[i];
-            if (lane == 0) dst[idx] = v;
-        }
-        for (int i = lane; i < 80; i += CPK_WAVE) {
-            double e = 0.0;
-            for (int k = 0; k < kECopies; k++) e += eLds[k * 80 + i];
-            dst[25 + i] = e;
-        }
-        {  // every lane holds the totals of the diagonals whose first cell it computed (Sweep::expectations)
-            double v = likelihood;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            if (lane == 0) dst[105] = v;
-        }
-    }
+    if (EMIT == CPECAN_EMIT_EXPECT) flushExpect(curSlot);
 }

@@ -26,8 +26,10 @@ __host__ __device__ constexpr int team_header_doubles(bool expect = false) {
 // EMIT (round 4): CPECAN_EMIT_MATCH, or CPECAN_EMIT_INDEL -- the three lists of diagonalCalculationPosteriorProbs
 // (pairwiseAligner.c:691-733: match, gapX, gapY; what getShiftedMEAAlignment needs): every state of every forward diagonal
 // goes to the ring, a wave keeps the candidates of three lists per diagonal and the waves exchange three counts.
-template <int S, int T, int EMIT = CPECAN_EMIT_MATCH>
+// SLOTS: the build for reserved batches (cf. cpecan_pairhmm_sweep): the slot of a ticket is the same for the whole workgroup.
+template <int S, int T, int EMIT = CPECAN_EMIT_MATCH, bool SLOTS = false>
 __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a) {
+    static_assert(!SLOTS || EMIT == CPECAN_EMIT_EXPECT, "model slots: expectation emitter");
     // ... or CPECAN_EMIT_EXPECT: the traceback parks B of the emitted cells (`bring`, the layout Sweep::traceback writes),
     // wave 0 folds the totals, and the T waves share the second pass (Sweep::expectations: every T-th item of 64 cells each),
     // every wave with transition sums of its own, the emission sums of the workgroup in LDS.
@@ -38,14 +40,16 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
     constexpr int R = 3 * S;
     using SweepT = Sweep<S, true, R>;
     const int tid = threadIdx.x, wave = tid / CPK_WAVE, lane = tid & (CPK_WAVE - 1);
-    const CpkModel &m = *a.model;
+    const CpkModel *mp = SLOTS ? &a.slotModels[0].m : a.model;  // (SLOTS: the model of the slot this workgroup holds)
+    int curSlot = 0;
     const int stride = a.geo.rollStride;
 
     // LDS (doubles): logAdd cubics | emissions | weights | exchange area | rolling rows | symbol strings
     logadd_fp_mode();  // (every wave: fill_cubics below sets it for the one wave that fills the table)
     if (wave == 0) {
         fill_cubics(lds);
-        fill_weights<S>(lds + kLdsCubics + kLdsEm, m, a.kc, lane);
+        if constexpr (SLOTS) fill_weights<S>(lds + kLdsCubics + kLdsEm, *mp, a.slotModels[0].kc, lane);
+        else fill_weights<S>(lds + kLdsCubics + kLdsEm, *mp, a.kc, lane);
     }
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
     double *em = lds + kLdsCubics;
@@ -67,8 +71,38 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
 
     // forward diagonal d (d >= -1), state s of cell k: frow(d)[s + k * R]
     auto frow = [&](int d) { return roll + R + ((d + 3) % 3) * S; };
+    // one partial result per WAVE (cpecan_pairhmm_sweep writes one per workgroup of one wave; SLOTS: per slot and wave):
+    // [0,25) transitions [from*S+to], [25,105) emissions -- the workgroup's, by wave 0 -- [105] likelihood
+    auto flushExpect = [&](int vs) __attribute__((always_inline)) {
+        __syncthreads();
+        double *dst = a.expectOut + ((SLOTS ? (size_t)vs * gridDim.x + blockIdx.x : (size_t)blockIdx.x) * T + wave) * 128;
+        constexpr int kFrom5[13] = {0, 1, 0, 3, 0, 1, 2, 3, 4, 0, 2, 0, 4}, kTo5[13] = {1, 1, 3, 3, 0, 0, 0, 0, 0, 2, 2, 4, 4};
+        constexpr int kFrom3[9] = {0, 1, 2, 0, 1, 2, 0, 2, 1}, kTo3[9] = {1, 1, 1, 0, 0, 0, 2, 2, 2};
+        for (int i = lane; i < 106; i += CPK_WAVE) dst[i] = 0.0;
+        __threadfence_block();
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kNT; i++) {
+            double v = tAcc[i];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            const int idx = S == 5 ? kFrom5[i] * 5 + kTo5[i] : kFrom3[i] * 3 + kTo3[i];
+            if (lane == 0) dst[idx] = v;
+        }
+        if (wave == 0) {
+            for (int i = lane; i < 80; i += CPK_WAVE) {
+                double e = 0.0;
+                for (int k = 0; k < kExpectCopies; k++) e += eLds[k * 80 + i];
+                dst[25 + i] = e;
+            }
+        }
+        double v = likelihood;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) dst[105] = v;
+    };
     const size_t slot = blockIdx.x;
-    const float logThr = (float)log(m.threshold);
+    const float logThr = (float)log(mp->threshold);
     for (;;) {
         if (wave == 0) {  // wave-uniform test; inside, every lane takes part (see the note in cpecan_pairhmm_sweep)
             const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? 1u : 0u);
@@ -78,8 +112,25 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
         __syncthreads();
         const int tk = xi[0];
         __syncthreads();  // everyone has read the ticket before the next one overwrites it
-        if (tk >= a.regionCount) break;
-        const int r = a.regionBase + tk;
+        int tkRegion = tk;  // (SLOTS: the region of virtual region tk)
+        if constexpr (SLOTS) {
+            if (tk >= a.regionCount * a.nModels) break;
+            const int vs = tk / a.regionCount;
+            tkRegion = tk - vs * a.regionCount;
+            if (vs != curSlot) {  // what the workgroup has summed belongs to the slot it leaves
+                flushExpect(curSlot);
+#pragma unroll
+                for (int i = 0; i < kNT; i++) tAcc[i] = 0.0;
+                likelihood = 0.0;
+                __syncthreads();
+                for (int i = tid; i < kExpectCopies * 80; i += CPK_WAVE * T) eLds[i] = 0.0;
+                curSlot = vs;
+                mp = &a.slotModels[vs].m;
+                if (wave == 0) fill_weights<S>(lds + kLdsCubics + kLdsEm, *mp, a.slotModels[vs].kc, lane);
+                __syncthreads();
+            }
+        } else if (tk >= a.regionCount) break;
+        const int r = a.regionBase + tkRegion;
         const CpkRegion &rg = a.regions[r];
         const int lX = rg.lX, lY = rg.lY, N = lX + lY;
         const uint8_t *gx = a.symbols + rg.seqXOff, *gy = a.symbols + rg.seqYOff;
@@ -126,7 +177,7 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
 #endif
         if (N > 0) {
             sw.dc.load(0);
-            const double *startPrior = rg.raggedLeft ? m.raggedStart : m.start;
+            const double *startPrior = rg.raggedLeft ? mp->raggedStart : mp->start;
             CpkDiag f1 = sw.dc.get(0, false), f2 = f1;  // table entries of the two previous forward diagonals
             if (tid < S) {
                 frow(0)[tid] = startPrior[tid];
@@ -192,7 +243,7 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
                 if (a.geo.debug & 2) continue;  // diagnostic (CPECAN_DEBUG_SKIP=2): the forward sweep alone, no output
 #endif
                 // ---- traceback of the segment (pairwiseAligner.c:796-862) ----
-                const double *endPrior = (sg.atEnd && rg.raggedRight) ? m.raggedEnd : m.end;
+                const double *endPrior = (sg.atEnd && rg.raggedRight) ? mp->raggedEnd : mp->end;
                 double ep[S];
 #pragma unroll
                 for (int s = 0; s < S; s++) ep[s] = endPrior[s];
@@ -439,34 +490,5 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
             if (tid == 0) a.outCounts[(size_t)l * a.geo.nRegions + r] = count[l];
         // count lives in wave 0 only: tid 0 is lane 0 of wave 0
     }
-    if (kExpect) {
-        // one partial result per WAVE (cpecan_pairhmm_sweep writes one per workgroup of one wave): [0,25) transitions
-        // [from*S+to], [25,105) emissions -- the workgroup's, by wave 0 -- [105] likelihood
-        __syncthreads();
-        double *dst = a.expectOut + ((size_t)blockIdx.x * T + wave) * 128;
-        constexpr int kFrom5[13] = {0, 1, 0, 3, 0, 1, 2, 3, 4, 0, 2, 0, 4}, kTo5[13] = {1, 1, 3, 3, 0, 0, 0, 0, 0, 2, 2, 4, 4};
-        constexpr int kFrom3[9] = {0, 1, 2, 0, 1, 2, 0, 2, 1}, kTo3[9] = {1, 1, 1, 0, 0, 0, 2, 2, 2};
-        for (int i = lane; i < 106; i += CPK_WAVE) dst[i] = 0.0;
-        __threadfence_block();
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < kNT; i++) {
-            double v = tAcc[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            const int idx = S == 5 ? kFrom5[i] * 5 + kTo5[i] : kFrom3[i] * 3 + kTo3[i];
-            if (lane == 0) dst[idx] = v;
-        }
-        if (wave == 0) {
-            for (int i = lane; i < 80; i += CPK_WAVE) {
-                double e = 0.0;
-                for (int k = 0; k < kExpectCopies; k++) e += eLds[k * 80 + i];
-                dst[25 + i] = e;
-            }
-        }
-        double v = likelihood;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == 0) dst[105] = v;
-    }
+    if (kExpect) flushExpect(curSlot);
 }

@@ -15,6 +15,7 @@ EXPORTS = [
     "cpecan_em_write_lastz_matrix", "cpecan_em_fasta_gc", "cpecan_em_write_model", "cpecan_em_trainer_create",
     "cpecan_em_trainer_destroy", "cpecan_em_trainer_read_fasta", "cpecan_em_trainer_add_sequence",
     "cpecan_em_trainer_set_devices", "cpecan_em_train", "cpecan_em_trainer_timing",
+    "cpecan_em_trainer_set_concurrent_trials",
 ]
 
 MODEL_TYPES = {"fiveState": api.fiveState, "fiveStateAsymmetric": api.fiveStateAsymmetric,
@@ -67,6 +68,7 @@ def _lib():
         L.cpecan_em_trainer_read_fasta.restype = C.c_int64
         L.cpecan_em_trainer_add_sequence.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int64]
         L.cpecan_em_trainer_set_devices.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
+        L.cpecan_em_trainer_set_concurrent_trials.argtypes = [vp, C.c_int]
         L.cpecan_em_train.argtypes = [vp, C.POINTER(realign._Cigar), C.c_int64, C.c_char_p, hp, dp]
         L.cpecan_em_trainer_timing.argtypes = [vp, C.POINTER(EmTiming)]
         _bound = True
@@ -201,6 +203,10 @@ class Trainer:
         devices = list(devices)
         arr = (C.c_int * max(1, len(devices)))(*devices)
         api._check(_lib().cpecan_em_trainer_set_devices(self._h, arr, len(devices)), "cpecan_em_trainer_set_devices")
+
+    def set_concurrent_trials(self, n):
+        """Random-restart trials per kernel launch (1 to 8; 1: one after another); more trials run in rounds."""
+        api._check(_lib().cpecan_em_trainer_set_concurrent_trials(self._h, int(n)), "cpecan_em_trainer_set_concurrent_trials")
 
     def train(self, cigars, output_model):
         """Runs every trial; returns (best Hmm, its running likelihoods)."""

@@ -15,7 +15,7 @@ EXPORTS = [
     "cpecan_realigner_realign", "cpecan_realigner_expectations",
     "cpecan_realigner_set_devices", "cpecan_realign_shard_bounds",
     "cpecan_expect_set_create", "cpecan_expect_set_run", "cpecan_expect_set_shards", "cpecan_expect_set_stats",
-    "cpecan_expect_set_destroy",
+    "cpecan_expect_set_destroy", "cpecan_expect_set_reserve_models", "cpecan_expect_set_run_models",
 ]
 
 

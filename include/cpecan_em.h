@@ -5,7 +5,9 @@
  * The sampled alignments are prepared, planned and uploaded ONCE as resident EXPECT batches (cpecan_expect_set_*, one per
  * device shard); every iteration swaps the model of those batches (cpecan_batch_set_model), runs only the kernels and does
  * the M-step on the host.  The reference runs one cPecanRealign --outputExpectations process per job and iteration
- * instead.  Random-restart trials run one after another on the same resident batches.
+ * instead.  Random-restart trials run one after another on the same resident batches, or -- after
+ * cpecan_em_trainer_set_concurrent_trials(t, n) -- in rounds of up to n side by side: the batches reserve n model slots
+ * (cpecan_batch_reserve_models, cpecan_hip.h) and an iteration of a round is ONE launch per shard for all its trials.
  *
  * Model files are written as cPecanEm.py's Hmm.write does -- "type t_0 .. t_{S*S-1} likelihood", then the S*16
  * emissions, then (after the last iteration) the running likelihoods, tab separated -- with every number printed to 17
@@ -80,6 +82,11 @@ int64_t cpecan_em_trainer_read_fasta(cpecan_em_trainer *t, const char *path);
 int cpecan_em_trainer_add_sequence(cpecan_em_trainer *t, const char *header, const char *seq, int64_t length);
 /* One resident shard per listed device (cpecan_realigner_set_devices); the shards' counts are summed on the host. */
 int cpecan_em_trainer_set_devices(cpecan_em_trainer *t, const int *devices, int nDevices);
+/* Trials per launch, 1 .. CPECAN_MAX_MODEL_SLOTS; 1 (the default): one trial after another.  With n > 1 cpecan_em_train
+ * draws every start model first, in trial order (trial k starts from the model it starts from in a sequential run), and
+ * runs the trials in rounds of up to n: an iteration of a round is one cpecan_expect_set_run_models plus the M-step of
+ * each trial.  Trial files, outputTrialHmms, the choice of the best trial, running likelihoods and timing are the same. */
+int cpecan_em_trainer_set_concurrent_trials(cpecan_em_trainer *t, int n);
 /* Samples the cigars, uploads them once and runs every trial's iterations.  Writes outputModel after every iteration
  * (with several trials: the trial's own file, <outputModel>_<i> with outputTrialHmms), then the trial with the highest
  * likelihood to outputModel, and the blast scoring matrix if one was asked for.  best (may be NULL) receives that model,

@@ -331,6 +331,24 @@ int cpecan_batch_run(cpecan_batch *b, void *stream);
  * set_model + run + download + cpecan_batch_expectations. */
 int cpecan_batch_set_model(cpecan_batch *b, const cpecan_model *m);
 
+/* ---- model slots: several models over one resident batch in a single launch ----
+ * cpecan_batch_reserve_models, before cpecan_batch_upload: the batch will evaluate up to nSlots models per run, 1 <= nSlots
+ * <= CPECAN_MAX_MODEL_SLOTS.  Only CPECAN_EMIT_EXPECT and CPECAN_EMIT_FORWARD batches (CPECAN_EINVAL otherwise: the other
+ * emitters' outputs are lists); CPECAN_ESTATE after upload.  Regions, band tables, schedules and symbols are uploaded once
+ * and shared; the queue of a launch holds n x regions virtual regions, slot-major, so a batch that leaves wave slots idle
+ * gets up to n times the waves, and everything that exists per wave is sized for that.  A batch that never reserves
+ * plans, launches and computes exactly as before.
+ * cpecan_batch_set_models, after upload: the n models (1 <= n <= the reserved count, each with the batch's state count)
+ * the next cpecan_batch_run evaluates; same checks and stream ordering as cpecan_batch_set_model, which on a reserved
+ * batch means set_models(b, m, 1).  Until the first call a reserved batch runs its own model in slot 0.
+ * The _slot getters read model `slot` of the last downloaded run (CPECAN_EINVAL outside 0 .. n - 1); the unslotted
+ * getters read slot 0. */
+#define CPECAN_MAX_MODEL_SLOTS 8
+int cpecan_batch_reserve_models(cpecan_batch *b, int nSlots);
+int cpecan_batch_set_models(cpecan_batch *b, const cpecan_model *models, int n);
+int cpecan_batch_expectations_slot(const cpecan_batch *b, int slot, cpecan_hmm *acc);
+int cpecan_batch_forward_prob_slot(const cpecan_batch *b, int slot, int64_t problem, double *logProb);
+
 /* Waits for the run, copies results to the host and orders them as the reference's lists. */
 int cpecan_batch_download(cpecan_batch *b);
 /* The same on a helper thread of the batch's own: _begin returns at once, _end waits for the helper and returns what

@@ -109,6 +109,13 @@ int cpecan_realigner_expectations(cpecan_realigner *r, const cpecan_cigar *in, i
 typedef struct cpecan_expect_set cpecan_expect_set;
 int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n);
 int cpecan_expect_set_run(cpecan_expect_set *s, const cpecan_model *m, cpecan_hmm *acc);
+/* Model slots (cpecan_batch_reserve_models, cpecan_hip.h).  A set takes its options from the realigner it is created
+ * from, so the reservation is made there, before cpecan_expect_set_create: the batches of every set created afterwards
+ * reserve nSlots models (1 .. CPECAN_MAX_MODEL_SLOTS; 0: plain batches again).  cpecan_expect_set_run_models is then n E-steps in one launch per
+ * shard, 1 <= n <= nSlots (a set that reserved nothing takes n = 1): every shard queues its launch before the first
+ * download waits, and accs[j] receives the counts of models[j], added in shard order as cpecan_expect_set_run adds them. */
+int cpecan_expect_set_reserve_models(cpecan_realigner *r, int nSlots);
+int cpecan_expect_set_run_models(cpecan_expect_set *s, const cpecan_model *models, int n, cpecan_hmm *accs);
 int cpecan_expect_set_shards(const cpecan_expect_set *s);
 /* Statistics of shard k's batch (launch form, waves, cells, kernel time of the last run); zeros for an empty shard. */
 int cpecan_expect_set_stats(const cpecan_expect_set *s, int shard, cpecan_stats *st);

@@ -7,6 +7,11 @@ expansion 10) or a smaller set; the model of each iteration is a different rando
 trials.  Prints one JSON line.
 
     python tools/em_bench.py [--pairs 100000] [--iterations 10] [--trials 3] [--full-calls 2]
+
+--models T measures model slots instead (cpecan_batch_reserve_models): T models in one launch of a reserved batch against
+the same T models one after another (set_model + run + download each) on a plain resident batch, rounds alternating.
+
+    python tools/em_bench.py --models 3 [--pairs 1000] [--iterations 15]
 """
 import argparse
 import json
@@ -21,6 +26,57 @@ from cpecan_amd import api, em  # noqa: E402
 from cpecan_amd.workload import CONFIGS, config_problems  # noqa: E402
 
 
+def slots_bench(a, p, arr, n, models):
+    T = a.models
+    pool = models  # at least T + 1 different models (main)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    with api.Batch(models[0], p, emit=api.EMIT_EXPECT, device=a.device) as plain, \
+            api.Batch(models[0], p, emit=api.EMIT_EXPECT, device=a.device) as slotted:
+        plain.add_prepared(arr, n)
+        plain.upload()
+        slotted.reserve_models(T)
+        slotted.add_prepared(arr, n)
+        slotted.upload()
+        seq_s, seq_ms, slot_s, slot_ms = [], [], [], []
+        for it in range(a.iterations + 2):  # two warm rounds
+            ms_ = [pool[(it * T + k) % len(pool)] for k in range(T)]
+            t = time.perf_counter()
+            kms = 0.0
+            for m in ms_:
+                plain.set_model(m)
+                plain.run()
+                plain.download()
+                plain.expectations(api.hmm_constructEmpty(0.0, api.fiveState))
+                kms += plain.stats().kernelMs
+            ts = time.perf_counter() - t
+            waves_seq = plain.stats().wavesPerLaunch
+            t = time.perf_counter()
+            slotted.set_models(ms_)
+            slotted.run()
+            slotted.download()
+            for k in range(T):
+                slotted.expectations(api.hmm_constructEmpty(0.0, api.fiveState), k)
+            tl = time.perf_counter() - t
+            if it >= 2:
+                seq_s.append(ts)
+                seq_ms.append(kms)
+                slot_s.append(tl)
+                slot_ms.append(slotted.stats().kernelMs)
+        st, ss = plain.stats(), slotted.stats()
+    print(json.dumps({
+        "what": "T models in one launch (model slots) vs T models one after another, same resident problems",
+        "models": T, "pairs": a.pairs, "regions": st.regions, "cells": st.cells, "rounds": a.iterations,
+        "sequential_s_median": med(seq_s), "sequential_s_min": min(seq_s), "sequential_s_max": max(seq_s),
+        "sequential_kernel_ms_median": med(seq_ms), "sequential_kernel_ms_min": min(seq_ms), "sequential_kernel_ms_max": max(seq_ms),
+        "sequential_waves_per_launch": waves_seq,
+        "slotted_s_median": med(slot_s), "slotted_s_min": min(slot_s), "slotted_s_max": max(slot_s),
+        "slotted_kernel_ms_median": med(slot_ms), "slotted_kernel_ms_min": min(slot_ms), "slotted_kernel_ms_max": max(slot_ms),
+        "slotted_waves_per_launch": ss.wavesPerLaunch,
+        "sequential_over_slotted": med(seq_s) / med(slot_s),
+        "sequential_over_slotted_kernel": med(seq_ms) / med(slot_ms),
+    }))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=CONFIGS["5"]["n_pairs"])
@@ -28,6 +84,7 @@ def main():
     ap.add_argument("--trials", type=int, default=3)
     ap.add_argument("--full-calls", type=int, default=2)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--models", type=int, default=0, help="T: model slots, T in one launch against T in a row")
     a = ap.parse_args()
     cfg = CONFIGS["5"]
     t0 = time.perf_counter()
@@ -36,7 +93,10 @@ def main():
     gen_s = time.perf_counter() - t0
     p = api.pairwiseAlignmentBandingParameters_construct(diagonalExpansion=cfg["expansion"])
     models = [api.hmm_getStateMachine(em.hmm_set_jukes_cantor(em.hmm_randomise(
-        api.hmm_constructEmpty(0.0, api.fiveState), 100 + k), 0.1)) for k in range(a.iterations * a.trials + 1)]
+        api.hmm_constructEmpty(0.0, api.fiveState), 100 + k), 0.1)) for k in range(max(a.iterations * a.trials, a.models) + 1)]
+
+    if a.models:
+        return slots_bench(a, p, arr, n, models)
 
     def full_call(sm):
         t = time.perf_counter()
