@@ -68,6 +68,15 @@ def main():
         got = api.computeForwardProbability(sx, sy, a, p, sm(mtype), False, False)
         want = ob.forward_prob(ob.model(mtype), sx, sy, a, ob.params(diagonalExpansion=40), False, False)
         assert got == want, ("forward", mtype, got, want)
+    # ... on wide diagonals (four 64-lane groups; 701 cells of five states, the widest that keep their rows in LDS) and on
+    # the global-memory kernel (721 cells of five states, 1121 of three: over the LDS path's 64 KB), ragged ends
+    p = api.pairwiseAlignmentBandingParameters_construct()
+    for mtype, length, rl, rr in ((0, 200, True, False), (3, 200, False, True), (0, 700, False, True), (0, 720, True, True), (2, 1120, False, False)):
+        sx, sy, _ = make_pair(7, mtype, length, 0)
+        sy = (sy + b"A" * length)[:length]  # the widest diagonal has length + 1 cells
+        got = api.computeForwardProbability(sx, sy, (), p, sm(mtype), rl, rr)
+        want = ob.forward_prob(ob.model(mtype), sx, sy, (), ob.params(), rl, rr)
+        assert got == want, ("forward", mtype, length, got, want)
     print("exact: forward probabilities equal", flush=True)
 
 
