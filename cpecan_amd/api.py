@@ -80,7 +80,7 @@ class ProblemRuns(C.Structure):
 class AnchorParams(C.Structure):
     """cpecan_anchor_params: seed, substitution scores and thresholds of the anchor finder."""
     _fields_ = [("seed", C.c_char * 32), ("maxSeedOccurrences", C.c_int32), ("scores", C.c_int32 * 25),
-                ("xDrop", C.c_int32), ("hspThreshold", C.c_int32), ("maxHsps", C.c_int32), ("reserved", C.c_int32)]
+                ("xDrop", C.c_int32), ("hspThreshold", C.c_int32), ("maxHsps", C.c_int32), ("seedTransitions", C.c_int32)]
 
 
 class AnchorProblem(C.Structure):

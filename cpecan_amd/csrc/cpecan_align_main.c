@@ -6,6 +6,7 @@
  * file order, for each the targets in file order (the reference iterates hash tables, so it defines no order).
  * --strand both does what the reference leaves open at cPecanAlign.c:116-117: every pair is tried against the query and
  * its reverse complement, and a pair on the minus strand gets a cigar with "<length> 0 -" for the query.
+ * --seedTransitions lets a seed hit of the anchor finder carry one transition (cpecan_anchor_params.seedTransitions = 1).
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -28,7 +29,8 @@ typedef struct {
 
 static void usage(void) {
     fprintf(stderr, "cpecan_align [options] target.fa query.fa > cigars\n"
-                    "-y --loadHmm FILE  -g --device N  -s --strand plus|minus|both (default plus)  -h --help\n");
+                    "-y --loadHmm FILE  -g --device N  -s --strand plus|minus|both (default plus)\n"
+                    "-t --seedTransitions (anchor seed hits may carry one transition)  -h --help\n");
 }
 
 static int fail(const char *what) {
@@ -100,13 +102,14 @@ static int by_x(const void *a, const void *b) {
 int main(int argc, char **argv) {
     const char *hmmFile = NULL;
     long long device = 0;
-    int strandMode = CPECAN_STRAND_PLUS;
+    int strandMode = CPECAN_STRAND_PLUS, seedTransitions = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
                                        {"strand", required_argument, 0, 's'},
+                                       {"seedTransitions", no_argument, 0, 't'},
                                        {0, 0, 0, 0}};
-    for (int key; (key = getopt_long(argc, argv, "hy:g:s:", longOpts, NULL)) != -1;) {
+    for (int key; (key = getopt_long(argc, argv, "hy:g:s:t", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
         case 'y': hmmFile = optarg; break;
@@ -117,6 +120,7 @@ int main(int argc, char **argv) {
             else if (strcmp(optarg, "both") == 0) strandMode = CPECAN_STRAND_BOTH;
             else { usage(); return 1; }
             break;
+        case 't': seedTransitions = 1; break;
         default: usage(); return 1;
         }
     }
@@ -133,6 +137,9 @@ int main(int argc, char **argv) {
     }
     cpecan_params params;
     cpecan_params_default(&params); /* :102 */
+    cpecan_anchor_params anchorParams;
+    cpecan_anchor_params_default(&anchorParams);
+    anchorParams.seedTransitions = seedTransitions;
     const int64_t trim = 14, anchorMatrix = 500 * 500, repeatMaskMatrix = 500 * 500; /* pairwiseAligner.c:1340-1342 */
     const double gapGamma = 0.5;                                                     /* :1345 */
     Records targets = {0}, queries = {0};
@@ -161,7 +168,7 @@ int main(int argc, char **argv) {
             ap[i].lY = queries.r[q].length;
         }
     if (status == 0 && n > 0) {
-        if (cpecan_find_anchor_runs_many_stranded(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix, NULL,
+        if (cpecan_find_anchor_runs_many_stranded(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix, &anchorParams,
                                                   (int)device, strandMode, runs, nRuns, NULL, strands) != CPECAN_OK)
             status = fail("anchors");
     }

@@ -24,6 +24,7 @@ int cpecan_anchor_params_default(cpecan_anchor_params *p) {
     p->xDrop = 910;
     p->hspThreshold = 800;
     p->maxHsps = 4096;
+    p->seedTransitions = 0; /* lastz's own default is 1 (--transition); DESIGN.md section 7 */
     return CPECAN_OK;
 }
 
@@ -67,6 +68,10 @@ static int find_runs(const char *who, const cpecan_anchor_problem *problems, int
     }
     if (memchr(params->seed, 0, sizeof params->seed) == NULL) {
         cpk_set_error("%s: the seed is not terminated", who);
+        return CPECAN_EINVAL;
+    }
+    if (params->seedTransitions != 0 && params->seedTransitions != 1) {
+        cpk_set_error("%s: seedTransitions is 0 or 1", who);
         return CPECAN_EINVAL;
     }
     for (int64_t i = 0; i < n; i++) {
@@ -152,7 +157,7 @@ static int find_runs(const char *who, const cpecan_anchor_problem *problems, int
         memcpy(bytes + top[k].xOff + q->lX, q->sY, (size_t)q->lY);
     }
     if ((rc = cpk_anchor_open(&ctx, device, bytes, nBytes, nExtra)) != CPECAN_OK) goto done;
-    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, top, nTop, (int32_t)trim, &topRuns, &ms)) != CPECAN_OK) goto done;
+    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, params->seedTransitions, top, nTop, (int32_t)trim, &topRuns, &ms)) != CPECAN_OK) goto done;
 
     /* The strand of every problem; what does not go on is dropped from the list: the twin that lost and, with BOTH, the
      * problems at or under the size limit, which were there to be scored. */
@@ -216,7 +221,7 @@ static int find_runs(const char *who, const cpecan_anchor_problem *problems, int
         }
         if (stats) stats[owner[k]].largestGapTop = largest;
     }
-    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, sub, nGaps, (int32_t)trim, &subRuns, &ms)) != CPECAN_OK) goto done;
+    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, params->seedTransitions, sub, nGaps, (int32_t)trim, &subRuns, &ms)) != CPECAN_OK) goto done;
 
     /* splice: the gaps of a problem are in increasing order, each in front of the top-level run it ends at */
     rc = CPECAN_ENOMEM;

@@ -248,7 +248,7 @@ typedef struct {
     int32_t lX, lY;
     int32_t softMask;   /* windows with a lower-case base at a seed position are skipped */
     int32_t capX, capY; /* key slots: the window counts rounded up to a power of two */
-    int32_t hspCap;     /* HSP slots: the hit count rounded up to a power of two */
+    int32_t hspCap;     /* HSP slots, and hit-list slots with seedTransitions: the hit count rounded up to a power of two */
     int64_t keyXOff, keyYOff, hspOff;
     int32_t hits, hsps, chained, nRuns, capped, flags;
     int64_t columns;
@@ -266,10 +266,11 @@ typedef struct CpkAnchorCtx CpkAnchorCtx;
 /* Copies the nBytes raw sequence bytes to `device` and packs them into symbols there; behind them (from the next even
  * symbol index on) the buffer has room for nExtra symbols more, for the reverse complements of a pass. */
 int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes, int64_t nExtra);
-/* Steps 1-5 of the anchor finder on n problems.  seed: '0' / '1' string.  *runs receives a malloc'd array of triples
- * (x, y, length) relative to each problem; problem i owns triples hspOff .. hspOff + nRuns - 1.  *ms: kernel time added. */
-int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, CpkAnchorProblem *probs, int64_t n,
-                    int32_t trim, int32_t **runs, double *ms);
+/* Steps 1-5 of the anchor finder on n problems.  seed: '0' / '1' string; seedTransitions: 0, or 1 for hits that carry one
+ * transition (cpecan_anchor_params).  *runs receives a malloc'd array of triples (x, y, length) relative to each problem;
+ * problem i owns triples hspOff .. hspOff + nRuns - 1.  *ms: kernel time added. */
+int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, int seedTransitions, CpkAnchorProblem *probs,
+                    int64_t n, int32_t trim, int32_t **runs, double *ms);
 void cpk_anchor_close(CpkAnchorCtx *c);
 
 #ifdef __cplusplus

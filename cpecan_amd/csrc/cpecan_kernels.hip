@@ -1726,8 +1726,8 @@ extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *by
     return CPECAN_OK;
 }
 
-extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seedText, CpkAnchorProblem *probs,
-                               int64_t n, int32_t trim, int32_t **runsOut, double *ms) {
+extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seedText, int seedTransitions,
+                               CpkAnchorProblem *probs, int64_t n, int32_t trim, int32_t **runsOut, double *ms) {
     *runsOut = nullptr;
     if (n <= 0) return CPECAN_OK;
     CpkAnchorSeed seed = {};
@@ -1742,14 +1742,17 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
         }
     }
     if (seed.span < 1 || seed.span > 31 || seed.weight < 1 || seed.weight > CPK_ANCHOR_MAX_WEIGHT || prm->maxSeedOccurrences < 1 ||
-        prm->maxHsps < 1 || prm->xDrop < 0 || trim < 0) {
+        prm->maxHsps < 1 || prm->xDrop < 0 || trim < 0 || seedTransitions < 0 || seedTransitions > 1) {
         cpk_set_error("anchor parameters: the seed is 1..31 characters of 0 / 1 with 1..%d ones; maxSeedOccurrences, maxHsps >= 1; "
-                      "xDrop, trim >= 0", CPK_ANCHOR_MAX_WEIGHT);
+                      "xDrop, trim >= 0; seedTransitions 0 or 1", CPK_ANCHOR_MAX_WEIGHT);
         return CPECAN_EINVAL;
     }
     CPK_ON_DEVICE(c->device);
     PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
     hipStream_t st = sc.stream;
+    // A Y window has at most maxSeedOccurrences hits per word it is looked up under: its own and, with seedTransitions, one
+    // per compared base.  The bound below keeps a problem's hit count, an int32 like its list sizes, at or under 2^30.
+    const int64_t hitsPerWindow = (int64_t)prm->maxSeedOccurrences * (seedTransitions ? 1 + seed.weight : 1);
     int64_t nKeys = 0;
     int maxCap = 1, maxRc = 0;
     for (int64_t i = 0; i < n; i++) {
@@ -1768,7 +1771,7 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
         }
         if (p.flags & CPK_ANCHOR_RC_Y) maxRc = std::max(maxRc, p.lY);
         if (p.lX < 0 || p.lY < 0 || p.xOff < 0 || p.yOff < 0 || p.xOff + p.lX > c->nSym || p.yOff + p.lY > c->nSym ||
-            p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * prm->maxSeedOccurrences > (1 << 30)) {
+            p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * hitsPerWindow > (1 << 30)) {
             cpk_set_error("anchor problem %lld: sequences outside the buffer, longer than 2^24, or too many seed occurrences allowed",
                           (long long)i);
             return CPECAN_EINVAL;
@@ -1807,8 +1810,12 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpk_anchor_sort_keys, dim3((unsigned)n, 2), dim3(maxCap >= 4096 ? 1024 : 256), 0, st, dProbs, dKeys);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cpk_anchor_hits<false>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
-                       (int4 *)nullptr, (int32_t *)nullptr);
+    if (seedTransitions)
+        hipLaunchKernelGGL(cpk_anchor_join<false>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, dKeys, prm->maxSeedOccurrences,
+                           seed.weight, (int2 *)nullptr, (int32_t *)nullptr);
+    else
+        hipLaunchKernelGGL(cpk_anchor_hits<false>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
+                           (int4 *)nullptr, (int32_t *)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->evB, st));
     HIP_TRY(hipMemcpyAsync(probs, dProbs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -1816,23 +1823,39 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
     HIP_TRY(hipEventElapsedTime(&part, c->evA, c->evB));
     *ms += part;
     int64_t nSlots = 0;
+    int maxHits = 1;
     for (int64_t i = 0; i < n; i++) {
         probs[i].hspCap = anchor_pow2(std::max(probs[i].hits, 1));
         probs[i].hspOff = nSlots;
         nSlots += probs[i].hspCap;
+        maxHits = std::max(maxHits, probs[i].hits);
     }
     int4 *dHsps = nullptr;
+    int2 *dHits = nullptr;  // seedTransitions: the hit list of every problem, the HSP list's slots and offsets
     int32_t *dCount = nullptr, *dBest = nullptr, *dPred = nullptr, *dRuns = nullptr;
     if (int rc = sc.alloc(&dHsps, (size_t)nSlots)) return rc;
-    if (int rc = sc.alloc(&dCount, (size_t)n)) return rc;
+    const size_t nCount = (size_t)n * (seedTransitions ? 2 : 1);  // HSPs handed out, then the hits written
+    if (seedTransitions) {
+        if (int rc = sc.alloc(&dHits, (size_t)nSlots)) return rc;
+    }
+    if (int rc = sc.alloc(&dCount, nCount)) return rc;
     if (int rc = sc.alloc(&dBest, (size_t)nSlots)) return rc;
     if (int rc = sc.alloc(&dPred, (size_t)nSlots)) return rc;
     if (int rc = sc.alloc(&dRuns, (size_t)nSlots * 3)) return rc;
     HIP_TRY(hipMemcpyAsync(dProbs, probs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(dCount, 0, sizeof(int32_t) * (size_t)n, st));
+    HIP_TRY(hipMemsetAsync(dCount, 0, sizeof(int32_t) * nCount, st));
     HIP_TRY(hipEventRecord(c->evA, st));
-    hipLaunchKernelGGL(cpk_anchor_hits<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
-                       dHsps, dCount);
+    if (seedTransitions) {
+        hipLaunchKernelGGL(cpk_anchor_join<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, dKeys, prm->maxSeedOccurrences,
+                           seed.weight, dHits, dCount + n);
+        HIP_TRY(hipGetLastError());
+        const unsigned hitChunks = (unsigned)std::min(1024, (maxHits + 255) / 256);
+        hipLaunchKernelGGL(cpk_anchor_extend, dim3((unsigned)n, hitChunks), dim3(256), 0, st, dProbs, c->dSym, dHits, *prm, seed.span,
+                           dHsps, dCount);
+    } else {
+        hipLaunchKernelGGL(cpk_anchor_hits<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
+                           dHsps, dCount);
+    }
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(cpk_anchor_chain, dim3((unsigned)n), dim3(256), 0, st, dProbs, dHsps, dCount, dBest, dPred, dRuns,
                        prm->maxHsps, trim);

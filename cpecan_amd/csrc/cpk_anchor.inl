@@ -205,6 +205,93 @@ __global__ void __launch_bounds__(256) cpk_anchor_hits(CpkAnchorProblem *probs, 
     }
 }
 
+// Step 1c with seedTransitions == 1.  One lane per Y window: 1 + weight lookups among X's sorted keys, its own word and the
+// word with one compared base replaced by its transition partner (XOR 2 on the base's two bits: a <-> g, c <-> t).  Only
+// words that pass the occurrence filter on their own side seed.  An X and a Y window match by at most one variant, so the
+// hits of a lane are distinct.  WRITE == false counts them; WRITE == true appends them as (wx, wy) to the problem's hit
+// list, which has the problem's hspCap slots at hspOff (slot order is arbitrary: the HSPs they extend to are sorted).
+// The lookups are a loop of the same length in every lane; the extension is a kernel of its own with one HIT per lane,
+// because a lane here holds up to (1 + weight) * maxSeedOccurrences hits and most lanes hold none.
+template <bool WRITE>
+__global__ void __launch_bounds__(256) cpk_anchor_join(CpkAnchorProblem *probs, const unsigned long long *keys, int maxOcc, int weight,
+                                                       int2 *hitList, int32_t *nHit) {
+    const int p = blockIdx.x;
+    const CpkAnchorProblem pr = probs[p];
+    const unsigned long long *kx = keys + pr.keyXOff, *ky = keys + pr.keyYOff;
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < pr.capY; i += gridDim.y * blockDim.x) {
+        const unsigned long long key = ky[i];
+        if (key == CPK_ANCHOR_KEY_NONE) continue;
+        const unsigned long long w = key >> 32;
+        const int y0 = anchor_lower_bound(ky, pr.capY, w), y1 = anchor_lower_bound(ky, pr.capY, w + 1);
+        if (y1 - y0 > maxOcc) continue;
+        const int wy = (int)(unsigned)key;
+        int count = 0;
+        for (int v = 0; v <= weight; v++) {
+            const unsigned long long wv = v == 0 ? w : w ^ (2ull << (2 * (v - 1)));
+            const int x0 = anchor_lower_bound(kx, pr.capX, wv), x1 = anchor_lower_bound(kx, pr.capX, wv + 1);
+            if (x1 == x0 || x1 - x0 > maxOcc) continue;
+            if (WRITE) {
+                const int slot = atomicAdd(&nHit[p], x1 - x0);
+                for (int h = x0; h < x1; h++)
+                    if (slot + (h - x0) < pr.hspCap) hitList[pr.hspOff + slot + (h - x0)] = make_int2((int)(unsigned)kx[h], wy);
+            }
+            count += x1 - x0;
+        }
+        if (!WRITE && count > 0) atomicAdd(&probs[p].hits, count);
+    }
+}
+
+// Step 2 with seedTransitions == 1.  One lane per hit of the problem's list: the x-drop walk, threshold test and slot
+// hand-out of cpk_anchor_hits<true>, column for column.
+__global__ void __launch_bounds__(256) cpk_anchor_extend(const CpkAnchorProblem *probs, const uint8_t *sym, const int2 *hitList,
+                                                         CpkAnchorParams prm, int span, int4 *hsps, int32_t *nHsp) {
+    __shared__ int sc[25];
+    if (threadIdx.x < 25) sc[threadIdx.x] = prm.scores[threadIdx.x];
+    __syncthreads();
+    const int p = blockIdx.x;
+    const CpkAnchorProblem pr = probs[p];
+    const int nHits = min(pr.hits, pr.hspCap);
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < nHits; i += gridDim.y * blockDim.x) {
+        const int2 hit = hitList[pr.hspOff + i];
+        const int wx = hit.x, wy = hit.y;
+        int score = 0;
+        for (int k = 0; k < span; k++) score += anchor_score(sc, anchor_sym(sym, pr.xOff + wx + k), anchor_sym(sym, pr.yOff + wy + k));
+        int lenR = 0, lenL = 0;
+        {
+            const int room = min(pr.lX - (wx + span), pr.lY - (wy + span));
+            const int64_t gx = pr.xOff + wx + span, gy = pr.yOff + wy + span;
+            int sum = 0, best = 0;
+            for (int k = 0; k < room; k++) {
+                sum += anchor_score(sc, anchor_sym(sym, gx + k), anchor_sym(sym, gy + k));
+                if (sum > best) {
+                    best = sum;
+                    lenR = k + 1;
+                }
+                if (sum < best - prm.xDrop) break;
+            }
+            score += best;
+        }
+        {
+            const int room = min(wx, wy);
+            const int64_t gx = pr.xOff + wx - 1, gy = pr.yOff + wy - 1;
+            int sum = 0, best = 0;
+            for (int k = 0; k < room; k++) {
+                sum += anchor_score(sc, anchor_sym(sym, gx - k), anchor_sym(sym, gy - k));
+                if (sum > best) {
+                    best = sum;
+                    lenL = k + 1;
+                }
+                if (sum < best - prm.xDrop) break;
+            }
+            score += best;
+        }
+        if (score >= prm.hspThreshold) {
+            const int slot = atomicAdd(&nHsp[p], 1);
+            if (slot < pr.hspCap) hsps[pr.hspOff + slot] = make_int4(wx - lenL, wy - lenL, span + lenL + lenR, score);
+        }
+    }
+}
+
 #define CPK_ANCHOR_HSP_NONE make_int4(0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000)
 struct AnchorHspByPlace {  // (x, y, length); fillers last
     __device__ bool operator()(const int4 &a, const int4 &b) const {

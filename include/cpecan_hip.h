@@ -149,8 +149,9 @@ int64_t cpecan_filter_to_remove_overlap(const int64_t *pairs, int64_t n, int64_t
 /* ---- the anchor finder: anchors from the two sequences alone ----
  * Fills the role lastz has in the reference (getBlastPairsForPairwiseAlignmentParameters, pairwiseAligner.c:1005-1196)
  * with a finder of this library's own, defined in DESIGN.md section 7; it is NOT lastz and does not reproduce its output.
- * Per problem: (1) spaced-seed words of X and Y; words that occur more than maxSeedOccurrences times on either side are
- * dropped; a hit is a pair of windows with equal words; (2) ungapped x-drop extension of every hit to an HSP, kept from
+ * Per problem: (1) spaced-seed words of X and Y; words that occur more than maxSeedOccurrences times on their own side are
+ * dropped; a hit is a pair of windows with equal words or, with seedTransitions 1, words that differ by one transition
+ * (a <-> g or c <-> t) at one compared position, as lastz --transition allows; (2) ungapped x-drop extension of every hit to an HSP, kept from
  * hspThreshold up, exact duplicates dropped; (3) at most maxHsps HSPs, the best by (score descending, x, y, length);
  * (4) the heaviest chain of HSPs that follow each other without overlap in X or Y, no gap penalty; (5) every chained HSP
  * minus `trim` columns at either end is an anchor run; (6) one level of recursion into every gap between consecutive
@@ -164,10 +165,11 @@ typedef struct cpecan_anchor_params {
     int32_t xDrop;
     int32_t hspThreshold;
     int32_t maxHsps;            /* per problem; cpecan_anchor_stats.capped tells when it cut */
-    int32_t reserved;
+    int32_t seedTransitions;    /* 0: the words of a hit are equal; 1: they may differ by one transition; else CPECAN_EINVAL */
 } cpecan_anchor_params;
-/* lastz's defaults where it has them: seed 1110100110010101111 (12 of 19, no transitions), HOXD70 with -100 for N,
- * xDrop 910, hspThreshold 800 (--hspthresh=800, :1034); maxSeedOccurrences 1 and maxHsps 4096 are this library's. */
+/* lastz's defaults where it has them: seed 1110100110010101111 (12 of 19), HOXD70 with -100 for N, xDrop 910,
+ * hspThreshold 800 (--hspthresh=800, :1034); maxSeedOccurrences 1 and maxHsps 4096 are this library's, and so is
+ * seedTransitions 0 (lastz's default is --transition, which is seedTransitions 1). */
 int cpecan_anchor_params_default(cpecan_anchor_params *p);
 
 typedef struct cpecan_anchor_problem {
