@@ -83,6 +83,11 @@ class AnchorParams(C.Structure):
                 ("xDrop", C.c_int32), ("hspThreshold", C.c_int32), ("maxHsps", C.c_int32), ("seedTransitions", C.c_int32)]
 
 
+class AnchorOptions(C.Structure):
+    """cpecan_anchor_options: what cpecan_anchor_params has no room for (anchor_options makes one)."""
+    _fields_ = [("transitionHspThreshold", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class AnchorProblem(C.Structure):
     """cpecan_anchor_problem: one element of cpecan_find_anchor_runs_many."""
     _fields_ = [("sX", C.c_char_p), ("lX", C.c_int64), ("sY", C.c_char_p), ("lY", C.c_int64)]
@@ -150,6 +155,7 @@ EXPORTS = [
     "cpecan_anchor_params_default", "cpecan_find_anchor_runs_many", "cpecan_find_anchor_runs", "cpecan_find_anchor_runs_once",
     "cpecan_reverse_complement", "cpecan_find_anchor_runs_many_stranded", "cpecan_batch_add_many_runs_stranded",
     "cpecan_batch_problem_strand",
+    "cpecan_anchor_options_default", "cpecan_find_anchor_runs_many_with_options", "cpecan_find_anchor_runs_once_with_options",
     "cpecan_batch_reserve_models", "cpecan_batch_set_models", "cpecan_batch_expectations_slot",
     "cpecan_batch_forward_prob_slot",
 ]
@@ -253,6 +259,10 @@ def lib():
     L.cpecan_find_anchor_runs_many_stranded.argtypes = [
         C.POINTER(AnchorProblem), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(AnchorParams), C.c_int,
         C.c_int, C.POINTER(i64p), i64p, C.POINTER(AnchorStats), C.POINTER(StrandResult)]
+    L.cpecan_anchor_options_default.argtypes = [C.POINTER(AnchorOptions)]
+    L.cpecan_find_anchor_runs_many_with_options.argtypes = (L.cpecan_find_anchor_runs_many_stranded.argtypes +
+                                                            [C.POINTER(AnchorOptions)])
+    L.cpecan_find_anchor_runs_once_with_options.argtypes = L.cpecan_find_anchor_runs_once.argtypes + [C.POINTER(AnchorOptions)]
     L.cpecan_batch_add_many_runs_stranded.argtypes = [vp, C.POINTER(ProblemRuns), i32p, C.c_int64]
     L.cpecan_batch_add_many_runs_stranded.restype = C.c_int64
     L.cpecan_batch_problem_strand.argtypes = [vp, C.c_int64]
@@ -392,6 +402,15 @@ def anchor_params_default(**overrides):
     return q
 
 
+def anchor_options(transitionHspThreshold=0):
+    """cpecan_anchor_options_default with the threshold set: what an HSP must score that no seed hit with equal words
+    extends to (seedTransitions 1); 0 = hspThreshold, i.e. no threshold of its own."""
+    o = AnchorOptions()
+    _check(lib().cpecan_anchor_options_default(C.byref(o)), "cpecan_anchor_options_default")
+    o.transitionHspThreshold = int(transitionHspThreshold)
+    return o
+
+
 def reverse_complement(s):
     """cpecan_reverse_complement: the bytes reversed, A<->T, C<->G in either case, every other byte as it is."""
     s = _bytes(s)
@@ -403,10 +422,11 @@ def reverse_complement(s):
 def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
                                    anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
                                    repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
-                                   strand="both"):
+                                   strand="both", options=None):
     """cpecan_find_anchor_runs_many_stranded on (sX, sY, ...) tuples: ([int64[nRuns, 4] per problem], [statistics dict per
     problem], [{"strand": "plus" | "minus", "scorePlus", "scoreMinus"} per problem]).  Runs of a minus problem are in the
-    coordinates of (sX, reverse_complement(sY))."""
+    coordinates of (sX, reverse_complement(sY)).  options: an AnchorOptions (anchor_options); the call is then
+    cpecan_find_anchor_runs_many_with_options."""
     problems = list(problems)
     n = len(problems)
     arr = (AnchorProblem * max(1, n))()
@@ -420,11 +440,13 @@ def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expa
     counts = (C.c_int64 * max(1, n))()
     stats = (AnchorStats * max(1, n))()
     strands = (StrandResult * max(1, n))()
-    _check(lib().cpecan_find_anchor_runs_many_stranded(arr, n, trim, expansion, anchorMatrixBiggerThanThis,
-                                                       repeatMaskMatrixBiggerThanThis,
-                                                       C.byref(params) if params is not None else None, device,
-                                                       _strand_mode(strand), runs, counts, stats, strands),
-           "cpecan_find_anchor_runs_many_stranded")
+    args = (arr, n, trim, expansion, anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis,
+            C.byref(params) if params is not None else None, device, _strand_mode(strand), runs, counts, stats, strands)
+    if options is None:
+        _check(lib().cpecan_find_anchor_runs_many_stranded(*args), "cpecan_find_anchor_runs_many_stranded")
+    else:
+        _check(lib().cpecan_find_anchor_runs_many_with_options(*args, C.byref(options)),
+               "cpecan_find_anchor_runs_many_with_options")
     out = []
     for i in range(n):
         c = counts[i]
@@ -440,12 +462,13 @@ def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expa
 def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
                           anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
                           repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
-                          strand="plus"):
+                          strand="plus", options=None):
     """cpecan_find_anchor_runs_many on (sX, sY, ...) tuples: ([int64[nRuns, 4] per problem], [statistics dict per problem]).
-    strand: "plus" (that function), "minus" or "both" (find_anchor_runs_many_stranded without the strand results)."""
-    if _strand_mode(strand) != STRAND_PLUS:
+    strand: "plus" (that function), "minus" or "both" (find_anchor_runs_many_stranded without the strand results).
+    options: an AnchorOptions; with one the call is find_anchor_runs_many_stranded's, whatever the strand."""
+    if _strand_mode(strand) != STRAND_PLUS or options is not None:
         return find_anchor_runs_many_stranded(problems, trim, expansion, anchorMatrixBiggerThanThis,
-                                              repeatMaskMatrixBiggerThanThis, params, device, strand)[:2]
+                                              repeatMaskMatrixBiggerThanThis, params, device, strand, options)[:2]
     problems = list(problems)
     n = len(problems)
     arr = (AnchorProblem * max(1, n))()
@@ -475,13 +498,15 @@ def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
 
 def find_anchor_runs(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
                      anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
-                     repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, strand="plus"):
+                     repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, strand="plus",
+                     options=None):
     """cpecan_find_anchor_runs: (int64[nRuns, 4] of (x, y, length, expansion), statistics dict), on the current device.
-    strand "minus" / "both": one problem of find_anchor_runs_many_stranded on the current device, same return value."""
-    if _strand_mode(strand) != STRAND_PLUS:
+    strand "minus" / "both", or options (an AnchorOptions): one problem of find_anchor_runs_many_stranded on the current
+    device, same return value."""
+    if _strand_mode(strand) != STRAND_PLUS or options is not None:
         runs, stats, _ = find_anchor_runs_many_stranded([(sX, sY)], trim, expansion, anchorMatrixBiggerThanThis,
                                                         repeatMaskMatrixBiggerThanThis, params,
-                                                        lib().cpecan_current_device(), strand)
+                                                        lib().cpecan_current_device(), strand, options)
         return runs[0], stats[0]
     sx, sy = _bytes(sX), _bytes(sY)
     runs, cnt, st = C.POINTER(C.c_int64)(), C.c_int64(), AnchorStats()
@@ -496,13 +521,18 @@ def find_anchor_runs(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
     return out, st.as_dict()
 
 
-def find_anchor_runs_once(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20, softMask=True, params=None):
-    """cpecan_find_anchor_runs_once: steps 1-5 alone (one getBlastPairs call of the reference), int64[nRuns, 4]."""
+def find_anchor_runs_once(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20, softMask=True, params=None, options=None):
+    """cpecan_find_anchor_runs_once: steps 1-5 alone (one getBlastPairs call of the reference), int64[nRuns, 4].  options:
+    an AnchorOptions; the call is then its C twin cpecan_find_anchor_runs_once_with_options."""
     sx, sy = _bytes(sX), _bytes(sY)
     runs, cnt = C.POINTER(C.c_int64)(), C.c_int64()
-    _check(lib().cpecan_find_anchor_runs_once(sx, len(sx), sy, len(sy), trim, expansion, int(softMask),
-                                              C.byref(params) if params is not None else None, C.byref(runs), C.byref(cnt)),
-           "cpecan_find_anchor_runs_once")
+    args = (sx, len(sx), sy, len(sy), trim, expansion, int(softMask), C.byref(params) if params is not None else None,
+            C.byref(runs), C.byref(cnt))
+    if options is None:
+        _check(lib().cpecan_find_anchor_runs_once(*args), "cpecan_find_anchor_runs_once")
+    else:
+        _check(lib().cpecan_find_anchor_runs_once_with_options(*args, C.byref(options)),
+               "cpecan_find_anchor_runs_once_with_options")
     out = np.zeros((0, 4), dtype=np.int64)
     if cnt.value:
         out = np.ctypeslib.as_array(runs, shape=(cnt.value * 4,)).copy().reshape(cnt.value, 4)
@@ -609,25 +639,25 @@ class Batch:
     def add_many_unanchored(self, problems, trim=CONSTRAINT_DIAGONAL_TRIM,
                             anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
                             repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
-                            strand="plus"):
+                            strand="plus", options=None):
         """problems: iterable of (sX, sY[, raggedLeft, raggedRight]) without anchors: the anchors of all of them are found
         in one anchor batch on `device` (the batch's device) with the batch's diagonalExpansion, then the problems are added
         as runs.  Returns (index of the first, anchor statistics per problem).  strand "minus" / "both": a problem on the
         minus strand is added as (sX, reverse complement of sY) -- the batch makes the reverse complement itself -- and its
         results are in those coordinates; the statistics then carry "strand", "scorePlus" and "scoreMinus" as well, and
-        problem_strand(i) reads the strand back."""
+        problem_strand(i) reads the strand back.  options: an AnchorOptions for the anchor batch."""
         problems = list(problems)
         n = len(problems)
         stranded = _strand_mode(strand) != STRAND_PLUS
         if stranded:
             runs, stats, strands = find_anchor_runs_many_stranded(problems, trim, self._p.diagonalExpansion,
                                                                   anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis,
-                                                                  params, device, strand)
+                                                                  params, device, strand, options)
             for st, sr in zip(stats, strands):
                 st.update(sr)
         else:
             runs, stats = find_anchor_runs_many(problems, trim, self._p.diagonalExpansion, anchorMatrixBiggerThanThis,
-                                                repeatMaskMatrixBiggerThanThis, params, device)
+                                                repeatMaskMatrixBiggerThanThis, params, device, options=options)
         arr = (ProblemRuns * max(1, n))()
         keep = []
         for i, pr in enumerate(problems):
@@ -757,20 +787,20 @@ def getAlignedPairsUsingAnchors(sM, sX, sY, anchorPairs, p, alignmentHasRaggedLe
 def getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, constraintDiagonalTrim=CONSTRAINT_DIAGONAL_TRIM,
                                                 anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
                                                 repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS,
-                                                anchorParams=None):
+                                                anchorParams=None, anchorOptions=None):
     """impl/pairwiseAligner.c:1162 with this library's anchor finder in lastz's place: int64[n, 3] anchors (x, y,
-    p.diagonalExpansion); none up to anchorMatrixBiggerThanThis."""
+    p.diagonalExpansion); none up to anchorMatrixBiggerThanThis.  anchorOptions: an AnchorOptions (anchor_options)."""
     if len(_bytes(sX)) * len(_bytes(sY)) <= anchorMatrixBiggerThanThis:
         return np.zeros((0, 3), dtype=np.int64)
     runs, _ = find_anchor_runs(sX, sY, constraintDiagonalTrim, p.diagonalExpansion, anchorMatrixBiggerThanThis,
-                               repeatMaskMatrixBiggerThanThis, anchorParams)
+                               repeatMaskMatrixBiggerThanThis, anchorParams, options=anchorOptions)
     return runs_to_anchors(runs)
 
 
 def getAlignedPairs(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False, **anchoring):
     """impl/pairwiseAligner.c:1481: getAlignedPairsUsingAnchors with the anchors found from the two sequences.  anchoring:
     constraintDiagonalTrim, anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis (the reference's defaults),
-    anchorParams."""
+    anchorParams, anchorOptions (getAlignedPairsWithIndels and getExpectations take the same)."""
     anchors = getBlastPairsForPairwiseAlignmentParameters(sX, sY, p, **anchoring)
     return getAlignedPairsUsingAnchors(sM, sX, sY, anchors, p, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd)
 
@@ -778,7 +808,8 @@ def getAlignedPairs(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHas
 def getAlignedPairsStranded(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alignmentHasRaggedRightEnd=False, strand="both",
                             constraintDiagonalTrim=CONSTRAINT_DIAGONAL_TRIM,
                             anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
-                            repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, anchorParams=None):
+                            repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, anchorParams=None,
+                            anchorOptions=None):
     """getAlignedPairs for a query that may lie on the other strand (the step cPecanAlign.c:116-117 leaves open):
     (pairs, "plus" | "minus", (scorePlus, scoreMinus)).  The pairs of a minus result are those of
     getAlignedPairs(sM, sX, reverse_complement(sY), ...): y there is position len(sY) - 1 - y of sY."""
@@ -786,7 +817,7 @@ def getAlignedPairsStranded(sM, sX, sY, p, alignmentHasRaggedLeftEnd=False, alig
     with Batch(sM, p, EMIT_MATCH, device) as b:
         _, stats = b.add_many_unanchored([(sX, sY, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd)],
                                          constraintDiagonalTrim, anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis,
-                                         anchorParams, device, strand)
+                                         anchorParams, device, strand, anchorOptions)
         chosen = b.problem_strand(0)
         b.upload()
         b.run()

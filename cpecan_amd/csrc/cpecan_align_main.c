@@ -7,6 +7,7 @@
  * --strand both does what the reference leaves open at cPecanAlign.c:116-117: every pair is tried against the query and
  * its reverse complement, and a pair on the minus strand gets a cigar with "<length> 0 -" for the query.
  * --seedTransitions lets a seed hit of the anchor finder carry one transition (cpecan_anchor_params.seedTransitions = 1).
+ * --transitionHspThreshold N asks N of an HSP that only such hits extend to (cpecan_anchor_options); it needs --seedTransitions.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -30,7 +31,9 @@ typedef struct {
 static void usage(void) {
     fprintf(stderr, "cpecan_align [options] target.fa query.fa > cigars\n"
                     "-y --loadHmm FILE  -g --device N  -s --strand plus|minus|both (default plus)\n"
-                    "-t --seedTransitions (anchor seed hits may carry one transition)  -h --help\n");
+                    "-t --seedTransitions (anchor seed hits may carry one transition)  -h --help\n"
+                    "-T --transitionHspThreshold N (with --seedTransitions: an HSP that no exact seed hit extends to must score N;\n"
+                    "   at least the HSP threshold, 800)\n");
 }
 
 static int fail(const char *what) {
@@ -102,14 +105,16 @@ static int by_x(const void *a, const void *b) {
 int main(int argc, char **argv) {
     const char *hmmFile = NULL;
     long long device = 0;
-    int strandMode = CPECAN_STRAND_PLUS, seedTransitions = 0;
+    int strandMode = CPECAN_STRAND_PLUS, seedTransitions = 0, haveThreshold = 0;
+    long long transitionHspThreshold = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
                                        {"strand", required_argument, 0, 's'},
                                        {"seedTransitions", no_argument, 0, 't'},
+                                       {"transitionHspThreshold", required_argument, 0, 'T'},
                                        {0, 0, 0, 0}};
-    for (int key; (key = getopt_long(argc, argv, "hy:g:s:t", longOpts, NULL)) != -1;) {
+    for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
         case 'y': hmmFile = optarg; break;
@@ -121,8 +126,19 @@ int main(int argc, char **argv) {
             else { usage(); return 1; }
             break;
         case 't': seedTransitions = 1; break;
+        case 'T':
+            if (sscanf(optarg, "%lld", &transitionHspThreshold) != 1 || transitionHspThreshold < 0 || transitionHspThreshold > 0x7fffffffLL) {
+                usage();
+                return 1;
+            }
+            haveThreshold = 1;
+            break;
         default: usage(); return 1;
         }
+    }
+    if (haveThreshold && !seedTransitions) {
+        fprintf(stderr, "cpecan_align: --transitionHspThreshold needs --seedTransitions\n");
+        return 1;
     }
     if (argc - optind != 2) { /* cPecanAlign.c:93-96 */
         usage();
@@ -140,6 +156,9 @@ int main(int argc, char **argv) {
     cpecan_anchor_params anchorParams;
     cpecan_anchor_params_default(&anchorParams);
     anchorParams.seedTransitions = seedTransitions;
+    cpecan_anchor_options anchorOptions;
+    cpecan_anchor_options_default(&anchorOptions);
+    anchorOptions.transitionHspThreshold = (int32_t)transitionHspThreshold;
     const int64_t trim = 14, anchorMatrix = 500 * 500, repeatMaskMatrix = 500 * 500; /* pairwiseAligner.c:1340-1342 */
     const double gapGamma = 0.5;                                                     /* :1345 */
     Records targets = {0}, queries = {0};
@@ -168,8 +187,9 @@ int main(int argc, char **argv) {
             ap[i].lY = queries.r[q].length;
         }
     if (status == 0 && n > 0) {
-        if (cpecan_find_anchor_runs_many_stranded(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix, &anchorParams,
-                                                  (int)device, strandMode, runs, nRuns, NULL, strands) != CPECAN_OK)
+        if (cpecan_find_anchor_runs_many_with_options(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix,
+                                                      &anchorParams, (int)device, strandMode, runs, nRuns, NULL, strands,
+                                                      haveThreshold ? &anchorOptions : NULL) != CPECAN_OK)
             status = fail("anchors");
     }
     if (status == 0 && n > 0) {

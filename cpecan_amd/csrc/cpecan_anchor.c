@@ -28,6 +28,12 @@ int cpecan_anchor_params_default(cpecan_anchor_params *p) {
     return CPECAN_OK;
 }
 
+int cpecan_anchor_options_default(cpecan_anchor_options *o) {
+    if (!o) return CPECAN_EINVAL;
+    memset(o, 0, sizeof *o);
+    return CPECAN_OK;
+}
+
 typedef struct {
     int64_t problem; /* index of the top-level problem this gap belongs to */
     int64_t pX, pY;  /* offset of the gap inside it */
@@ -55,7 +61,7 @@ int cpecan_reverse_complement(const char *s, int64_t l, char *out) {
 static int find_runs(const char *who, const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
                      int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis, const cpecan_anchor_params *params,
                      int device, int strandMode, int once, int softMaskTop, int64_t **runs, int64_t *nRuns, cpecan_anchor_stats *stats,
-                     cpecan_strand_result *strands) {
+                     cpecan_strand_result *strands, const cpecan_anchor_options *options) {
     if (n < 0 || (n > 0 && (!problems || !runs || !nRuns)) || trim < 0 || trim > (1 << 24) || strandMode < CPECAN_STRAND_PLUS ||
         strandMode > CPECAN_STRAND_BOTH) {
         cpk_set_error("%s: bad arguments", who);
@@ -73,6 +79,21 @@ static int find_runs(const char *who, const cpecan_anchor_problem *problems, int
     if (params->seedTransitions != 0 && params->seedTransitions != 1) {
         cpk_set_error("%s: seedTransitions is 0 or 1", who);
         return CPECAN_EINVAL;
+    }
+    /* step 2's threshold for an HSP that only variant hits extend to; hspThreshold says: no class is told from the other */
+    int32_t variantThreshold = params->hspThreshold;
+    if (options) {
+        for (int k = 0; k < 7; k++)
+            if (options->reserved[k] != 0) {
+                cpk_set_error("%s: a reserved word of the options is not 0", who);
+                return CPECAN_EINVAL;
+            }
+        if (options->transitionHspThreshold < 0 ||
+            (options->transitionHspThreshold != 0 && options->transitionHspThreshold < params->hspThreshold)) {
+            cpk_set_error("%s: transitionHspThreshold is 0 or at least hspThreshold", who);
+            return CPECAN_EINVAL;
+        }
+        if (options->transitionHspThreshold != 0) variantThreshold = options->transitionHspThreshold;
     }
     for (int64_t i = 0; i < n; i++) {
         runs[i] = NULL;
@@ -157,7 +178,7 @@ static int find_runs(const char *who, const cpecan_anchor_problem *problems, int
         memcpy(bytes + top[k].xOff + q->lX, q->sY, (size_t)q->lY);
     }
     if ((rc = cpk_anchor_open(&ctx, device, bytes, nBytes, nExtra)) != CPECAN_OK) goto done;
-    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, params->seedTransitions, top, nTop, (int32_t)trim, &topRuns, &ms)) != CPECAN_OK) goto done;
+    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, params->seedTransitions, variantThreshold, top, nTop, (int32_t)trim, &topRuns, &ms)) != CPECAN_OK) goto done;
 
     /* The strand of every problem; what does not go on is dropped from the list: the twin that lost and, with BOTH, the
      * problems at or under the size limit, which were there to be scored. */
@@ -221,7 +242,7 @@ static int find_runs(const char *who, const cpecan_anchor_problem *problems, int
         }
         if (stats) stats[owner[k]].largestGapTop = largest;
     }
-    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, params->seedTransitions, sub, nGaps, (int32_t)trim, &subRuns, &ms)) != CPECAN_OK) goto done;
+    if ((rc = cpk_anchor_pass(ctx, &prm, params->seed, params->seedTransitions, variantThreshold, sub, nGaps, (int32_t)trim, &subRuns, &ms)) != CPECAN_OK) goto done;
 
     /* splice: the gaps of a problem are in increasing order, each in front of the top-level run it ends at */
     rc = CPECAN_ENOMEM;
@@ -307,20 +328,31 @@ done:
     return rc;
 }
 
+int cpecan_find_anchor_runs_many_with_options(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                              int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                                              const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
+                                              int64_t *nRuns, cpecan_anchor_stats *stats, cpecan_strand_result *strands,
+                                              const cpecan_anchor_options *options) {
+    return find_runs("cpecan_find_anchor_runs_many_with_options", problems, n, trim, expansion, anchorMatrixBiggerThanThis,
+                     repeatMaskMatrixBiggerThanThis, params, device, strandMode, 0, 1, runs, nRuns, stats, strands, options);
+}
+
 int cpecan_find_anchor_runs_many_stranded(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
                                           int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
                                           const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
                                           int64_t *nRuns, cpecan_anchor_stats *stats, cpecan_strand_result *strands) {
-    return find_runs("cpecan_find_anchor_runs_many_stranded", problems, n, trim, expansion, anchorMatrixBiggerThanThis,
-                     repeatMaskMatrixBiggerThanThis, params, device, strandMode, 0, 1, runs, nRuns, stats, strands);
+    return cpecan_find_anchor_runs_many_with_options(problems, n, trim, expansion, anchorMatrixBiggerThanThis,
+                                                     repeatMaskMatrixBiggerThanThis, params, device, strandMode, runs, nRuns, stats,
+                                                     strands, NULL);
 }
 
 int cpecan_find_anchor_runs_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
                                  int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
                                  const cpecan_anchor_params *params, int device, int64_t **runs, int64_t *nRuns,
                                  cpecan_anchor_stats *stats) {
-    return find_runs("cpecan_find_anchor_runs_many", problems, n, trim, expansion, anchorMatrixBiggerThanThis,
-                     repeatMaskMatrixBiggerThanThis, params, device, CPECAN_STRAND_PLUS, 0, 1, runs, nRuns, stats, NULL);
+    return cpecan_find_anchor_runs_many_with_options(problems, n, trim, expansion, anchorMatrixBiggerThanThis,
+                                                     repeatMaskMatrixBiggerThanThis, params, device, CPECAN_STRAND_PLUS, runs, nRuns,
+                                                     stats, NULL, NULL);
 }
 
 int cpecan_find_anchor_runs(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
@@ -332,13 +364,20 @@ int cpecan_find_anchor_runs(const char *sX, int64_t lX, const char *sY, int64_t 
                                         cpk_current_device(), runs, nRuns, stats);
 }
 
-int cpecan_find_anchor_runs_once(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
-                                 int softMask, const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns) {
+/* Steps 1-5 alone are a mode of find_runs the arguments of the entry point above cannot ask for, so this one has a twin. */
+int cpecan_find_anchor_runs_once_with_options(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim,
+                                              int64_t expansion, int softMask, const cpecan_anchor_params *params,
+                                              int64_t **runs, int64_t *nRuns, const cpecan_anchor_options *options) {
     if (!runs || !nRuns) {
         cpk_set_error("cpecan_find_anchor_runs_once: bad arguments");
         return CPECAN_EINVAL;
     }
     const cpecan_anchor_problem q = {sX, lX, sY, lY};
     return find_runs("cpecan_find_anchor_runs_once", &q, 1, trim, expansion, 0, 0, params, cpk_current_device(), CPECAN_STRAND_PLUS,
-                     1, softMask, runs, nRuns, NULL, NULL);
+                     1, softMask, runs, nRuns, NULL, NULL, options);
+}
+
+int cpecan_find_anchor_runs_once(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim, int64_t expansion,
+                                 int softMask, const cpecan_anchor_params *params, int64_t **runs, int64_t *nRuns) {
+    return cpecan_find_anchor_runs_once_with_options(sX, lX, sY, lY, trim, expansion, softMask, params, runs, nRuns, NULL);
 }

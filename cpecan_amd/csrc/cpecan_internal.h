@@ -267,10 +267,11 @@ typedef struct CpkAnchorCtx CpkAnchorCtx;
  * symbol index on) the buffer has room for nExtra symbols more, for the reverse complements of a pass. */
 int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes, int64_t nExtra);
 /* Steps 1-5 of the anchor finder on n problems.  seed: '0' / '1' string; seedTransitions: 0, or 1 for hits that carry one
- * transition (cpecan_anchor_params).  *runs receives a malloc'd array of triples (x, y, length) relative to each problem;
+ * transition (cpecan_anchor_params); variantThreshold: what an HSP must score that only such hits extend to
+ * (cpecan_anchor_options; >= prm->hspThreshold, and equal to it for none of its own).  *runs receives a malloc'd array of triples (x, y, length) relative to each problem;
  * problem i owns triples hspOff .. hspOff + nRuns - 1.  *ms: kernel time added. */
-int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, int seedTransitions, CpkAnchorProblem *probs,
-                    int64_t n, int32_t trim, int32_t **runs, double *ms);
+int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, int seedTransitions, int variantThreshold,
+                    CpkAnchorProblem *probs, int64_t n, int32_t trim, int32_t **runs, double *ms);
 void cpk_anchor_close(CpkAnchorCtx *c);
 
 #ifdef __cplusplus

@@ -1727,7 +1727,7 @@ extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *by
 }
 
 extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seedText, int seedTransitions,
-                               CpkAnchorProblem *probs, int64_t n, int32_t trim, int32_t **runsOut, double *ms) {
+                               int variantThreshold, CpkAnchorProblem *probs, int64_t n, int32_t trim, int32_t **runsOut, double *ms) {
     *runsOut = nullptr;
     if (n <= 0) return CPECAN_OK;
     CpkAnchorSeed seed = {};
@@ -1742,9 +1742,11 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
         }
     }
     if (seed.span < 1 || seed.span > 31 || seed.weight < 1 || seed.weight > CPK_ANCHOR_MAX_WEIGHT || prm->maxSeedOccurrences < 1 ||
-        prm->maxHsps < 1 || prm->xDrop < 0 || trim < 0 || seedTransitions < 0 || seedTransitions > 1) {
+        prm->maxHsps < 1 || prm->xDrop < 0 || trim < 0 || seedTransitions < 0 || seedTransitions > 1 ||
+        variantThreshold < prm->hspThreshold) {
         cpk_set_error("anchor parameters: the seed is 1..31 characters of 0 / 1 with 1..%d ones; maxSeedOccurrences, maxHsps >= 1; "
-                      "xDrop, trim >= 0; seedTransitions 0 or 1", CPK_ANCHOR_MAX_WEIGHT);
+                      "xDrop, trim >= 0; seedTransitions 0 or 1; the threshold of variant-seeded HSPs >= hspThreshold",
+                      CPK_ANCHOR_MAX_WEIGHT);
         return CPECAN_EINVAL;
     }
     CPK_ON_DEVICE(c->device);
@@ -1850,8 +1852,8 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
                            seed.weight, dHits, dCount + n);
         HIP_TRY(hipGetLastError());
         const unsigned hitChunks = (unsigned)std::min(1024, (maxHits + 255) / 256);
-        hipLaunchKernelGGL(cpk_anchor_extend, dim3((unsigned)n, hitChunks), dim3(256), 0, st, dProbs, c->dSym, dHits, *prm, seed.span,
-                           dHsps, dCount);
+        hipLaunchKernelGGL(cpk_anchor_extend, dim3((unsigned)n, hitChunks), dim3(256), 0, st, dProbs, c->dSym, dHits, *prm, variantThreshold,
+                           seed.span, dHsps, dCount);
     } else {
         hipLaunchKernelGGL(cpk_anchor_hits<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
                            dHsps, dCount);

@@ -14,6 +14,7 @@
 #define CPK_ANCHOR_MAX_WEIGHT 15 /* word < 2^30: a key (word << 32 | position) never equals the all-ones filler */
 #define CPK_ANCHOR_KEY_NONE (~0ull)
 #define CPK_ANCHOR_NO_KEY (-0x7fffffffffffffffLL - 1)
+#define CPK_ANCHOR_HIT_EXACT (1 << 24) /* in the y of a listed hit (wy < 2^24): the two words are equal */
 
 struct CpkAnchorSeed {
     int32_t span, weight;
@@ -210,6 +211,7 @@ __global__ void __launch_bounds__(256) cpk_anchor_hits(CpkAnchorProblem *probs, 
 // words that pass the occurrence filter on their own side seed.  An X and a Y window match by at most one variant, so the
 // hits of a lane are distinct.  WRITE == false counts them; WRITE == true appends them as (wx, wy) to the problem's hit
 // list, which has the problem's hspCap slots at hspOff (slot order is arbitrary: the HSPs they extend to are sorted).
+// The hits of the lane's own word (v == 0) are the exact ones: their wy carries CPK_ANCHOR_HIT_EXACT.
 // The lookups are a loop of the same length in every lane; the extension is a kernel of its own with one HIT per lane,
 // because a lane here holds up to (1 + weight) * maxSeedOccurrences hits and most lanes hold none.
 template <bool WRITE>
@@ -232,8 +234,9 @@ __global__ void __launch_bounds__(256) cpk_anchor_join(CpkAnchorProblem *probs, 
             if (x1 == x0 || x1 - x0 > maxOcc) continue;
             if (WRITE) {
                 const int slot = atomicAdd(&nHit[p], x1 - x0);
+                const int wyClass = v == 0 ? wy | CPK_ANCHOR_HIT_EXACT : wy;
                 for (int h = x0; h < x1; h++)
-                    if (slot + (h - x0) < pr.hspCap) hitList[pr.hspOff + slot + (h - x0)] = make_int2((int)(unsigned)kx[h], wy);
+                    if (slot + (h - x0) < pr.hspCap) hitList[pr.hspOff + slot + (h - x0)] = make_int2((int)(unsigned)kx[h], wyClass);
             }
             count += x1 - x0;
         }
@@ -241,10 +244,14 @@ __global__ void __launch_bounds__(256) cpk_anchor_join(CpkAnchorProblem *probs, 
     }
 }
 
-// Step 2 with seedTransitions == 1.  One lane per hit of the problem's list: the x-drop walk, threshold test and slot
-// hand-out of cpk_anchor_hits<true>, column for column.
+// Step 2 with seedTransitions == 1.  One lane per hit of the problem's list: the x-drop walk and slot hand-out of
+// cpk_anchor_hits<true>, column for column, and the threshold of the hit's class: hspThreshold for an exact hit,
+// variantThreshold (>= hspThreshold; equal to it unless cpecan_anchor_options says otherwise) for a variant hit.  An HSP
+// that hits of both classes extend to is appended by the exact ones whatever the others do, and cpk_anchor_chain drops
+// its duplicates: the kept set does not depend on the order of the lanes.
 __global__ void __launch_bounds__(256) cpk_anchor_extend(const CpkAnchorProblem *probs, const uint8_t *sym, const int2 *hitList,
-                                                         CpkAnchorParams prm, int span, int4 *hsps, int32_t *nHsp) {
+                                                         CpkAnchorParams prm, int variantThreshold, int span, int4 *hsps,
+                                                         int32_t *nHsp) {
     __shared__ int sc[25];
     if (threadIdx.x < 25) sc[threadIdx.x] = prm.scores[threadIdx.x];
     __syncthreads();
@@ -253,7 +260,8 @@ __global__ void __launch_bounds__(256) cpk_anchor_extend(const CpkAnchorProblem 
     const int nHits = min(pr.hits, pr.hspCap);
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < nHits; i += gridDim.y * blockDim.x) {
         const int2 hit = hitList[pr.hspOff + i];
-        const int wx = hit.x, wy = hit.y;
+        const int wx = hit.x, wy = hit.y & (CPK_ANCHOR_HIT_EXACT - 1);
+        const int threshold = (hit.y & CPK_ANCHOR_HIT_EXACT) ? prm.hspThreshold : variantThreshold;
         int score = 0;
         for (int k = 0; k < span; k++) score += anchor_score(sc, anchor_sym(sym, pr.xOff + wx + k), anchor_sym(sym, pr.yOff + wy + k));
         int lenR = 0, lenL = 0;
@@ -285,7 +293,7 @@ __global__ void __launch_bounds__(256) cpk_anchor_extend(const CpkAnchorProblem 
             }
             score += best;
         }
-        if (score >= prm.hspThreshold) {
+        if (score >= threshold) {
             const int slot = atomicAdd(&nHsp[p], 1);
             if (slot < pr.hspCap) hsps[pr.hspOff + slot] = make_int4(wx - lenL, wy - lenL, span + lenL + lenR, score);
         }

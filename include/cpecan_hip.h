@@ -152,7 +152,8 @@ int64_t cpecan_filter_to_remove_overlap(const int64_t *pairs, int64_t n, int64_t
  * Per problem: (1) spaced-seed words of X and Y; words that occur more than maxSeedOccurrences times on their own side are
  * dropped; a hit is a pair of windows with equal words or, with seedTransitions 1, words that differ by one transition
  * (a <-> g or c <-> t) at one compared position, as lastz --transition allows; (2) ungapped x-drop extension of every hit to an HSP, kept from
- * hspThreshold up, exact duplicates dropped; (3) at most maxHsps HSPs, the best by (score descending, x, y, length);
+ * hspThreshold up -- with cpecan_anchor_options.transitionHspThreshold T, an HSP that no hit with equal words extends to is
+ * kept from T up -- exact duplicates dropped; (3) at most maxHsps HSPs, the best by (score descending, x, y, length);
  * (4) the heaviest chain of HSPs that follow each other without overlap in X or Y, no gap penalty; (5) every chained HSP
  * minus `trim` columns at either end is an anchor run; (6) one level of recursion into every gap between consecutive
  * anchors whose matrix is larger than anchorMatrixBiggerThanThis (:1175-1191), soft masking on at the top level and in a
@@ -231,6 +232,31 @@ int cpecan_find_anchor_runs_many_stranded(const cpecan_anchor_problem *problems,
                                           int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
                                           const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
                                           int64_t *nRuns, cpecan_anchor_stats *stats, cpecan_strand_result *strands);
+
+/* ---- options beyond cpecan_anchor_params, which is full ----
+ * transitionHspThreshold T (step 2): with seedTransitions 1 a hit is EXACT when its two words are equal and a VARIANT hit
+ * otherwise.  An extended HSP is kept iff its score reaches hspThreshold and (it reaches T or at least one exact hit
+ * extends to it).  Everything after that is unchanged, and T holds wherever step 2 runs: the top level, the gaps of step
+ * 6, both orientations of step 0.  T == hspThreshold (or 0) is the result without options; T == INT32_MAX is the result of
+ * seedTransitions 0 in everything but cpecan_anchor_stats.hits, which counts every hit whatever becomes of it.  With
+ * seedTransitions 0 there is no variant hit and T has no effect.  tests/anchor_model_threshold.py states it in Python. */
+typedef struct cpecan_anchor_options {
+    int32_t transitionHspThreshold; /* 0: the same as hspThreshold; otherwise >= hspThreshold */
+    int32_t reserved[7];            /* must be 0 */
+} cpecan_anchor_options;            /* 32 bytes */
+int cpecan_anchor_options_default(cpecan_anchor_options *o); /* all 0 */
+/* cpecan_find_anchor_runs_many_stranded with options; NULL = the defaults, and then it IS that function: every entry point
+ * above is a call of this one with NULL.  A negative threshold, one in (0, hspThreshold) or a nonzero reserved word is
+ * CPECAN_EINVAL, refused before a device is looked for. */
+int cpecan_find_anchor_runs_many_with_options(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                              int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
+                                              const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
+                                              int64_t *nRuns, cpecan_anchor_stats *stats, cpecan_strand_result *strands,
+                                              const cpecan_anchor_options *options);
+/* cpecan_find_anchor_runs_once with options: steps 1-5 alone have no place among the arguments above. */
+int cpecan_find_anchor_runs_once_with_options(const char *sX, int64_t lX, const char *sY, int64_t lY, int64_t trim,
+                                              int64_t expansion, int softMask, const cpecan_anchor_params *params,
+                                              int64_t **runs, int64_t *nRuns, const cpecan_anchor_options *options);
 
 /* The reference's cell-level primitives (inc/pairwiseAligner.h:186-237: cell_calculateForward / Backward,
  * diagonalCalculationForward / Backward, the posterior of :683-685), which its unit tests link, evaluated on the caller's

@@ -2,7 +2,9 @@
 around the anchor kernels of both passes), and the stage's share of a getAlignedPairs-style call (Batch.add_many_unanchored
 + upload + run + download: anchor kernels beside the DP kernels, as profiles/anchor_stage.txt), on the three ENCODE pairs
 and on 256 seeded 3 kb pairs.  Every figure: smallest, median and largest of `repeats` calls, off and on interleaved.
-Usage: python tools/anchor_transitions_bench.py [repeats] [off]       (off: only the off case, for a library without the option)"""
+Usage: python tools/anchor_transitions_bench.py [repeats] [off] [--transitionHspThreshold N]
+off: only the off case, for a library without the option.  --transitionHspThreshold N: a third case, mode 2, which is
+seedTransitions 1 with cpecan_anchor_options.transitionHspThreshold = N."""
 import os
 import statistics
 import sys
@@ -20,11 +22,21 @@ def spread(v):
 
 
 def main():
-    repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-    modes = (0,) if "off" in sys.argv[2:] else (0, 1)
+    argv = list(sys.argv[1:])
+    threshold = None
+    if "--transitionHspThreshold" in argv:
+        at = argv.index("--transitionHspThreshold")
+        threshold = int(argv[at + 1])
+        del argv[at:at + 2]
+    repeats = int(argv[0]) if argv else 7
+    modes = (0,) if "off" in argv[1:] else (0, 1) if threshold is None else (0, 1, 2)
     params = {0: api.anchor_params_default()}
+    options = {0: None, 1: None}
     if 1 in modes:
         params[1] = api.anchor_params_default(seedTransitions=1)
+    if 2 in modes:
+        params[2] = params[1]
+        options[2] = api.anchor_options(transitionHspThreshold=threshold)
     cases = [("ENCODE human / chimp", [rc.encode_human_chimp()[:2]]), ("ENCODE human / dog", [rc.encode_human_other("dog")[:2]]),
              ("ENCODE human / mouse", [rc.encode_human_other("mouse")[:2]]),
              ("256 seeded 3 kb pairs", [ac.random_pair(1000 + i, 3000) for i in range(256)])]
@@ -32,12 +44,14 @@ def main():
     p = api.pairwiseAlignmentBandingParameters_construct()
     api.find_anchor_runs_many(cases[1][1])  # first call: module load, pools
     print("library %s; ms as min median max of %d calls" % (api.LIB_PATH, repeats))
+    if threshold is not None:
+        print("seedTransitions 2 stands for seedTransitions 1 with transitionHspThreshold %d" % threshold)
     for name, problems in cases:
         ms = {t: [] for t in modes}
         st = {}
         for _ in range(repeats):
             for t in modes:
-                _, stats = api.find_anchor_runs_many(problems, params=params[t])
+                _, stats = api.find_anchor_runs_many(problems, params=params[t], options=options[t])
                 ms[t].append(stats[0]["kernelMs"])
                 st[t] = stats
         for t in modes:
@@ -49,7 +63,8 @@ def main():
             anchor, dp, cells = [], [], 0
             for _ in range(3):
                 with api.Batch(sm, p) as b:
-                    _, stats = b.add_many_unanchored([(sx, sy, True, True) for sx, sy in problems], params=params[t])
+                    _, stats = b.add_many_unanchored([(sx, sy, True, True) for sx, sy in problems], params=params[t],
+                                                          options=options[t])
                     b.upload()
                     b.run()
                     b.download()
