@@ -419,6 +419,25 @@ def reverse_complement(s):
     return out.raw
 
 
+def _anchor_problems(problems):
+    """(sX, sY, ...) tuples as a cpecan_anchor_problem array: (array, n, the bytes it points to)."""
+    keep = [(_bytes(pr[0]), _bytes(pr[1])) for pr in problems]
+    arr = (AnchorProblem * max(1, len(keep)))()
+    for i, (sx, sy) in enumerate(keep):
+        arr[i].sX, arr[i].lX, arr[i].sY, arr[i].lY = sx, len(sx), sy, len(sy)
+    return arr, len(keep), keep
+
+
+def _take_runs(runs, count):
+    """One malloc'd list of `count` quadruples as int64[count, 4]; the list goes back to the library."""
+    out = np.zeros((0, 4), dtype=np.int64)
+    if count:
+        out = np.ctypeslib.as_array(runs, shape=(count * 4,)).copy().reshape(count, 4)
+    if runs:
+        lib().cpecan_free(C.cast(runs, C.c_void_p))
+    return out
+
+
 def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
                                    anchorMatrixBiggerThanThis=ANCHOR_MATRIX_BIGGER_THAN_THIS,
                                    repeatMaskMatrixBiggerThanThis=REPEAT_MASK_MATRIX_BIGGER_THAN_THIS, params=None, device=0,
@@ -427,14 +446,7 @@ def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expa
     problem], [{"strand": "plus" | "minus", "scorePlus", "scoreMinus"} per problem]).  Runs of a minus problem are in the
     coordinates of (sX, reverse_complement(sY)).  options: an AnchorOptions (anchor_options); the call is then
     cpecan_find_anchor_runs_many_with_options."""
-    problems = list(problems)
-    n = len(problems)
-    arr = (AnchorProblem * max(1, n))()
-    keep = []
-    for i, pr in enumerate(problems):
-        sx, sy = _bytes(pr[0]), _bytes(pr[1])
-        keep.append((sx, sy))
-        arr[i].sX, arr[i].lX, arr[i].sY, arr[i].lY = sx, len(sx), sy, len(sy)
+    arr, n, keep = _anchor_problems(problems)
     i64p = C.POINTER(C.c_int64)
     runs = (i64p * max(1, n))()
     counts = (C.c_int64 * max(1, n))()
@@ -447,15 +459,7 @@ def find_anchor_runs_many_stranded(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expa
     else:
         _check(lib().cpecan_find_anchor_runs_many_with_options(*args, C.byref(options)),
                "cpecan_find_anchor_runs_many_with_options")
-    out = []
-    for i in range(n):
-        c = counts[i]
-        if c:
-            out.append(np.ctypeslib.as_array(runs[i], shape=(c * 4,)).copy().reshape(c, 4))
-        else:
-            out.append(np.zeros((0, 4), dtype=np.int64))
-        if runs[i]:
-            lib().cpecan_free(C.cast(runs[i], C.c_void_p))
+    out = [_take_runs(runs[i], counts[i]) for i in range(n)]
     return out, [stats[i].as_dict() for i in range(n)], [strands[i].as_dict() for i in range(n)]
 
 
@@ -469,14 +473,7 @@ def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
     if _strand_mode(strand) != STRAND_PLUS or options is not None:
         return find_anchor_runs_many_stranded(problems, trim, expansion, anchorMatrixBiggerThanThis,
                                               repeatMaskMatrixBiggerThanThis, params, device, strand, options)[:2]
-    problems = list(problems)
-    n = len(problems)
-    arr = (AnchorProblem * max(1, n))()
-    keep = []
-    for i, pr in enumerate(problems):
-        sx, sy = _bytes(pr[0]), _bytes(pr[1])
-        keep.append((sx, sy))
-        arr[i].sX, arr[i].lX, arr[i].sY, arr[i].lY = sx, len(sx), sy, len(sy)
+    arr, n, keep = _anchor_problems(problems)
     i64p = C.POINTER(C.c_int64)
     runs = (i64p * max(1, n))()
     counts = (C.c_int64 * max(1, n))()
@@ -484,15 +481,7 @@ def find_anchor_runs_many(problems, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
     _check(lib().cpecan_find_anchor_runs_many(arr, n, trim, expansion, anchorMatrixBiggerThanThis,
                                               repeatMaskMatrixBiggerThanThis, C.byref(params) if params is not None else None,
                                               device, runs, counts, stats), "cpecan_find_anchor_runs_many")
-    out = []
-    for i in range(n):
-        c = counts[i]
-        if c:
-            out.append(np.ctypeslib.as_array(runs[i], shape=(c * 4,)).copy().reshape(c, 4))
-        else:
-            out.append(np.zeros((0, 4), dtype=np.int64))
-        if runs[i]:
-            lib().cpecan_free(C.cast(runs[i], C.c_void_p))
+    out = [_take_runs(runs[i], counts[i]) for i in range(n)]
     return out, [stats[i].as_dict() for i in range(n)]
 
 
@@ -513,12 +502,7 @@ def find_anchor_runs(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20,
     _check(lib().cpecan_find_anchor_runs(sx, len(sx), sy, len(sy), trim, expansion, anchorMatrixBiggerThanThis,
                                          repeatMaskMatrixBiggerThanThis, C.byref(params) if params is not None else None,
                                          C.byref(runs), C.byref(cnt), C.byref(st)), "cpecan_find_anchor_runs")
-    out = np.zeros((0, 4), dtype=np.int64)
-    if cnt.value:
-        out = np.ctypeslib.as_array(runs, shape=(cnt.value * 4,)).copy().reshape(cnt.value, 4)
-    if runs:
-        lib().cpecan_free(C.cast(runs, C.c_void_p))
-    return out, st.as_dict()
+    return _take_runs(runs, cnt.value), st.as_dict()
 
 
 def find_anchor_runs_once(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20, softMask=True, params=None, options=None):
@@ -533,12 +517,7 @@ def find_anchor_runs_once(sX, sY, trim=CONSTRAINT_DIAGONAL_TRIM, expansion=20, s
     else:
         _check(lib().cpecan_find_anchor_runs_once_with_options(*args, C.byref(options)),
                "cpecan_find_anchor_runs_once_with_options")
-    out = np.zeros((0, 4), dtype=np.int64)
-    if cnt.value:
-        out = np.ctypeslib.as_array(runs, shape=(cnt.value * 4,)).copy().reshape(cnt.value, 4)
-    if runs:
-        lib().cpecan_free(C.cast(runs, C.c_void_p))
-    return out
+    return _take_runs(runs, cnt.value)
 
 
 def runs_to_anchors(runs):

@@ -262,17 +262,86 @@ typedef struct {
     int32_t maxSeedOccurrences, xDrop, hspThreshold, maxHsps;
 } CpkAnchorParams;
 
+/* What a pass needs beside its problems; cpk_anchor_check (cpecan_anchor.c) builds it once per call. */
+typedef struct {
+    CpkAnchorParams prm;      /* handed to the kernels by value */
+    char seed[32];            /* '0' / '1', terminated */
+    int32_t seedTransitions;  /* 0, or 1 for hits that carry one transition (cpecan_anchor_params) */
+    int32_t variantThreshold; /* what an HSP must score that only such hits extend to (cpecan_anchor_options);
+                               * >= prm.hspThreshold, and equal to it for no threshold of its own */
+    int32_t trim;
+} CpkAnchorPass;
+
+/* What cpk_anchor_pass_plan works out of a pass and its problem list without a device, and cpk_anchor_pass_size of the
+ * hit counts that come back in the middle of the pass. */
+typedef struct {
+    struct {
+        int32_t span, weight;
+        uint8_t pos[16];
+    } seed;                /* the layout of the kernels' CpkAnchorSeed (cpk_anchor.inl) */
+    int32_t transitions;   /* the pass takes the transition path: join, hit lists, extend */
+    int32_t maxCap, maxRc; /* most key slots of one sequence; longest reverse complement to write (0: none) */
+    int32_t maxHits;       /* sizing: most hits of one problem, at least 1 */
+    int64_t hitsPerWindow; /* most hits a Y window can have */
+    int64_t nKeys;         /* key slots of the pass */
+    int64_t nSlots;        /* sizing: HSP slots of the pass */
+    int64_t nCounters;     /* sizing: per problem the HSPs handed out and, on the transition path, the hits written */
+} CpkAnchorPlan;
+
 typedef struct CpkAnchorCtx CpkAnchorCtx;
 /* Copies the nBytes raw sequence bytes to `device` and packs them into symbols there; behind them (from the next even
  * symbol index on) the buffer has room for nExtra symbols more, for the reverse complements of a pass. */
 int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *bytes, int64_t nBytes, int64_t nExtra);
-/* Steps 1-5 of the anchor finder on n problems.  seed: '0' / '1' string; seedTransitions: 0, or 1 for hits that carry one
- * transition (cpecan_anchor_params); variantThreshold: what an HSP must score that only such hits extend to
- * (cpecan_anchor_options; >= prm->hspThreshold, and equal to it for none of its own).  *runs receives a malloc'd array of triples (x, y, length) relative to each problem;
- * problem i owns triples hspOff .. hspOff + nRuns - 1.  *ms: kernel time added. */
-int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seed, int seedTransitions, int variantThreshold,
-                    CpkAnchorProblem *probs, int64_t n, int32_t trim, int32_t **runs, double *ms);
+/* The host half of a pass; touches no device.  Parses the seed, checks the pass and the contract of the problem list
+ * against a buffer of nSym symbols of which the first nForward are the packed bytes (CPECAN_EINVAL), and fills capX, capY,
+ * keyXOff, keyYOff and zeroed counters into every problem. */
+int cpk_anchor_pass_plan(const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int64_t nSym, int64_t nForward,
+                         CpkAnchorPlan *plan);
+/* The second sizing step: hspCap and hspOff of every problem from its hit count. */
+void cpk_anchor_pass_size(CpkAnchorProblem *probs, int64_t n, CpkAnchorPlan *plan);
+/* Steps 1-5 of the anchor finder on n problems of the context's buffer.  *runs receives a malloc'd array of triples
+ * (x, y, length) relative to each problem (NULL for n == 0); problem i owns triples hspOff .. hspOff + nRuns - 1, and
+ * nothing else is promised about where a problem's triples lie.  *ms: kernel time added. */
+int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int32_t **runs, double *ms);
 void cpk_anchor_close(CpkAnchorCtx *c);
+
+/* ---- the stages of a call (cpecan_anchor.c); none of them touches a device ---- */
+/* What a call carries beside the pass: the entry point's arguments and outputs. */
+typedef struct {
+    const char *who; /* the entry point, for the error texts */
+    const cpecan_anchor_problem *problems;
+    int64_t n;
+    int64_t expansion, anchorMatrixBiggerThanThis, repeatMaskMatrixBiggerThanThis;
+    int32_t device, strandMode;
+    int32_t once;        /* steps 1-5 alone on every problem whatever its size, no recursion (cpecan_find_anchor_runs_once) */
+    int32_t softMaskTop; /* soft masking of the top level; only `once` asks for 0 (:1168) */
+    int64_t **runs;
+    int64_t *nRuns;
+    cpecan_anchor_stats *stats;    /* or NULL */
+    cpecan_strand_result *strands; /* or NULL */
+} CpkAnchorCall;
+
+/* The problems of one pass.  owner: the caller's problem (top level) or the index in the top-level list (gaps); before:
+ * the top-level run a gap stands in front of, nRuns for the gap behind the last. */
+typedef struct {
+    CpkAnchorProblem *probs;
+    int64_t *owner, *before;
+    int64_t n, cap;
+} CpkAnchorList;
+void cpk_anchor_list_free(CpkAnchorList *l);
+
+/* Check: arguments, params (NULL: the defaults) and options (or NULL) into *pass; outputs zeroed, strands at their defaults. */
+int cpk_anchor_check(const CpkAnchorCall *c, int64_t trim, const cpecan_anchor_params *params,
+                     const cpecan_anchor_options *options, CpkAnchorPass *pass);
+/* Layout: the top-level list, twins included, and the malloc'd buffer of its sequences (NULL for an empty list). */
+int cpk_anchor_layout(const CpkAnchorCall *c, CpkAnchorList *top, uint8_t **bytes, int64_t *nBytes, int64_t *nExtra);
+/* Strand pick, after the top-level pass: scores into c->strands, the list compacted to what goes on. */
+void cpk_anchor_pick(const CpkAnchorCall *c, CpkAnchorList *top);
+/* Gaps: the rectangles between the top-level runs that are still too large become the list of the second pass. */
+int cpk_anchor_gaps(const CpkAnchorCall *c, const CpkAnchorList *top, const int32_t *topRuns, CpkAnchorList *sub);
+/* Splice: both run lists into c->runs, c->nRuns and c->stats. */
+int cpk_anchor_splice(const CpkAnchorCall *c, const CpkAnchorList *top, const int32_t *topRuns, const CpkAnchorList *sub,
+                      const int32_t *subRuns, double kernelMs);
 
 #ifdef __cplusplus
 }

@@ -1726,42 +1726,42 @@ extern "C" int cpk_anchor_open(CpkAnchorCtx **out, int device, const uint8_t *by
     return CPECAN_OK;
 }
 
-extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, const char *seedText, int seedTransitions,
-                               int variantThreshold, CpkAnchorProblem *probs, int64_t n, int32_t trim, int32_t **runsOut, double *ms) {
-    *runsOut = nullptr;
-    if (n <= 0) return CPECAN_OK;
-    CpkAnchorSeed seed = {};
-    seed.span = (int32_t)strlen(seedText);
+static_assert(sizeof(CpkAnchorSeed) == sizeof(CpkAnchorPlan().seed), "CpkAnchorPlan holds the seed as the kernels take it");
+
+// The host half of a pass (cpecan_internal.h): the seed, the checks on the pass and on the problem list, the key slots.
+extern "C" int cpk_anchor_pass_plan(const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int64_t nSym, int64_t nForward,
+                                    CpkAnchorPlan *plan) {
+    const CpkAnchorParams &prm = pass->prm;
+    *plan = CpkAnchorPlan{};
+    auto &seed = plan->seed;
+    seed.span = (int32_t)strnlen(pass->seed, sizeof pass->seed);
     for (int i = 0; i < seed.span; i++) {
-        if (seedText[i] == '1') {
+        if (pass->seed[i] == '1') {
             if (seed.weight < CPK_ANCHOR_MAX_WEIGHT) seed.pos[seed.weight] = (uint8_t)i;
             seed.weight++;
-        } else if (seedText[i] != '0') {
+        } else if (pass->seed[i] != '0') {
             seed.weight = 0;
             break;
         }
     }
-    if (seed.span < 1 || seed.span > 31 || seed.weight < 1 || seed.weight > CPK_ANCHOR_MAX_WEIGHT || prm->maxSeedOccurrences < 1 ||
-        prm->maxHsps < 1 || prm->xDrop < 0 || trim < 0 || seedTransitions < 0 || seedTransitions > 1 ||
-        variantThreshold < prm->hspThreshold) {
+    if (seed.span < 1 || seed.span > 31 || seed.weight < 1 || seed.weight > CPK_ANCHOR_MAX_WEIGHT || prm.maxSeedOccurrences < 1 ||
+        prm.maxHsps < 1 || prm.xDrop < 0 || pass->trim < 0 || pass->seedTransitions < 0 || pass->seedTransitions > 1 ||
+        pass->variantThreshold < prm.hspThreshold) {
         cpk_set_error("anchor parameters: the seed is 1..31 characters of 0 / 1 with 1..%d ones; maxSeedOccurrences, maxHsps >= 1; "
                       "xDrop, trim >= 0; seedTransitions 0 or 1; the threshold of variant-seeded HSPs >= hspThreshold",
                       CPK_ANCHOR_MAX_WEIGHT);
         return CPECAN_EINVAL;
     }
-    CPK_ON_DEVICE(c->device);
-    PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
-    hipStream_t st = sc.stream;
+    plan->transitions = pass->seedTransitions;
     // A Y window has at most maxSeedOccurrences hits per word it is looked up under: its own and, with seedTransitions, one
     // per compared base.  The bound below keeps a problem's hit count, an int32 like its list sizes, at or under 2^30.
-    const int64_t hitsPerWindow = (int64_t)prm->maxSeedOccurrences * (seedTransitions ? 1 + seed.weight : 1);
-    int64_t nKeys = 0;
-    int maxCap = 1, maxRc = 0;
+    plan->hitsPerWindow = (int64_t)prm.maxSeedOccurrences * (plan->transitions ? 1 + seed.weight : 1);
+    plan->maxCap = plan->maxHits = 1;
     for (int64_t i = 0; i < n; i++) {
         CpkAnchorProblem &p = probs[i];
         // a reverse complement is written from the forward symbols into the area behind them, at an even index
-        if ((p.flags & CPK_ANCHOR_RC_Y) && (p.yFwd < 0 || p.lY < 0 || p.yFwd + p.lY > c->nForward || (p.yOff & 1) ||
-                                            p.yOff < ((c->nForward + 1) & ~(int64_t)1))) {
+        if ((p.flags & CPK_ANCHOR_RC_Y) && (p.yFwd < 0 || p.lY < 0 || p.yFwd + p.lY > nForward || (p.yOff & 1) ||
+                                            p.yOff < ((nForward + 1) & ~(int64_t)1))) {
             cpk_set_error("anchor problem %lld: the reverse complement does not go from the forward symbols to the area behind them",
                           (long long)i);
             return CPECAN_EINVAL;
@@ -1771,9 +1771,9 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
             cpk_set_error("anchor problem %lld: a twin follows the problem whose X it shares", (long long)i);
             return CPECAN_EINVAL;
         }
-        if (p.flags & CPK_ANCHOR_RC_Y) maxRc = std::max(maxRc, p.lY);
-        if (p.lX < 0 || p.lY < 0 || p.xOff < 0 || p.yOff < 0 || p.xOff + p.lX > c->nSym || p.yOff + p.lY > c->nSym ||
-            p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * hitsPerWindow > (1 << 30)) {
+        if (p.flags & CPK_ANCHOR_RC_Y) plan->maxRc = std::max(plan->maxRc, p.lY);
+        if (p.lX < 0 || p.lY < 0 || p.xOff < 0 || p.yOff < 0 || p.xOff + p.lX > nSym || p.yOff + p.lY > nSym ||
+            p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * plan->hitsPerWindow > (1 << 30)) {
             cpk_set_error("anchor problem %lld: sequences outside the buffer, longer than 2^24, or too many seed occurrences allowed",
                           (long long)i);
             return CPECAN_EINVAL;
@@ -1782,94 +1782,119 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorParams *prm, cons
         p.capY = anchor_pow2(std::max(p.lY - seed.span + 1, 1));
         if (p.flags & CPK_ANCHOR_SHARE_X) {  // X's words are made and sorted once per pair
             p.keyXOff = probs[i - 1].keyXOff;
-            p.keyYOff = nKeys;
-            nKeys += p.capY;
+            p.keyYOff = plan->nKeys;
+            plan->nKeys += p.capY;
         } else {
-            p.keyXOff = nKeys;
-            p.keyYOff = nKeys + p.capX;
-            nKeys += (int64_t)p.capX + p.capY;
+            p.keyXOff = plan->nKeys;
+            p.keyYOff = plan->nKeys + p.capX;
+            plan->nKeys += (int64_t)p.capX + p.capY;
         }
-        maxCap = std::max(maxCap, std::max(p.capX, p.capY));
+        plan->maxCap = std::max(plan->maxCap, std::max(p.capX, p.capY));
         p.hits = p.hsps = p.chained = p.nRuns = p.capped = p.score = p.pad = 0;
         p.columns = 0;
         p.hspCap = 0;
         p.hspOff = 0;
     }
+    return CPECAN_OK;
+}
+
+// The hit counts are back: the HSP list of every problem, which is its hit list too on the transition path.
+extern "C" void cpk_anchor_pass_size(CpkAnchorProblem *probs, int64_t n, CpkAnchorPlan *plan) {
+    plan->nSlots = 0;
+    plan->maxHits = 1;
+    for (int64_t i = 0; i < n; i++) {
+        probs[i].hspCap = anchor_pow2(std::max(probs[i].hits, 1));
+        probs[i].hspOff = plan->nSlots;
+        plan->nSlots += probs[i].hspCap;
+        plan->maxHits = std::max(plan->maxHits, probs[i].hits);
+    }
+    plan->nCounters = n * (plan->transitions ? 2 : 1);  // HSPs handed out, then the hits written
+}
+
+extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int32_t **runsOut,
+                               double *ms) {
+    *runsOut = nullptr;
+    if (n <= 0) return CPECAN_OK;
+    CpkAnchorPlan plan;
+    if (int rc = cpk_anchor_pass_plan(pass, probs, n, c->nSym, c->nForward, &plan)) return rc;
+    const CpkAnchorParams &prm = pass->prm;
+    CpkAnchorSeed seed;
+    memcpy(&seed, &plan.seed, sizeof seed);
+    CPK_ON_DEVICE(c->device);
+    PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
+    hipStream_t st = sc.stream;
+    const size_t probBytes = sizeof(CpkAnchorProblem) * (size_t)n;
+    const dim3 perProblem((unsigned)n), perChunk((unsigned)n, (unsigned)std::min(64, (plan.maxCap + 1023) / 1024));
     CpkAnchorProblem *dProbs = nullptr;
     unsigned long long *dKeys = nullptr;
     if (int rc = sc.alloc(&dProbs, (size_t)n)) return rc;
-    if (int rc = sc.alloc(&dKeys, (size_t)nKeys)) return rc;
-    const unsigned chunks = (unsigned)std::min(64, (maxCap + 1023) / 1024);
+    if (int rc = sc.alloc(&dKeys, (size_t)plan.nKeys)) return rc;
     float part = 0.f;
-    HIP_TRY(hipMemcpyAsync(dProbs, probs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyHostToDevice, st));
+
+    // round 1: steps 0 and 1, the hits counted
+    HIP_TRY(hipMemcpyAsync(dProbs, probs, probBytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(c->evA, st));
-    if (maxRc > 0) {  // step 0, only in a pass that has a minus strand
-        const unsigned rcChunks = (unsigned)std::min(1024, (maxRc / 2 + 256) / 256);
+    if (plan.maxRc > 0) {  // step 0, only in a pass that has a minus strand
+        const unsigned rcChunks = (unsigned)std::min(1024, (plan.maxRc / 2 + 256) / 256);
         hipLaunchKernelGGL(cpk_anchor_revcomp, dim3((unsigned)n, rcChunks), dim3(256), 0, st, dProbs, c->dSym);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(cpk_anchor_words, dim3((unsigned)n, chunks, 2), dim3(256), 0, st, dProbs, c->dSym, seed, dKeys);
+    hipLaunchKernelGGL(cpk_anchor_words, dim3(perChunk.x, perChunk.y, 2), dim3(256), 0, st, dProbs, c->dSym, seed, dKeys);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cpk_anchor_sort_keys, dim3((unsigned)n, 2), dim3(maxCap >= 4096 ? 1024 : 256), 0, st, dProbs, dKeys);
+    hipLaunchKernelGGL(cpk_anchor_sort_keys, dim3((unsigned)n, 2), dim3(plan.maxCap >= 4096 ? 1024 : 256), 0, st, dProbs, dKeys);
     HIP_TRY(hipGetLastError());
-    if (seedTransitions)
-        hipLaunchKernelGGL(cpk_anchor_join<false>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, dKeys, prm->maxSeedOccurrences,
-                           seed.weight, (int2 *)nullptr, (int32_t *)nullptr);
+    if (plan.transitions)
+        hipLaunchKernelGGL(cpk_anchor_join<false>, perChunk, dim3(256), 0, st, dProbs, dKeys, prm.maxSeedOccurrences, seed.weight,
+                           (int2 *)nullptr, (int32_t *)nullptr);
     else
-        hipLaunchKernelGGL(cpk_anchor_hits<false>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
+        hipLaunchKernelGGL(cpk_anchor_hits<false>, perChunk, dim3(256), 0, st, dProbs, c->dSym, dKeys, prm, seed.span,
                            (int4 *)nullptr, (int32_t *)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->evB, st));
-    HIP_TRY(hipMemcpyAsync(probs, dProbs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(probs, dProbs, probBytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipEventElapsedTime(&part, c->evA, c->evB));
     *ms += part;
-    int64_t nSlots = 0;
-    int maxHits = 1;
-    for (int64_t i = 0; i < n; i++) {
-        probs[i].hspCap = anchor_pow2(std::max(probs[i].hits, 1));
-        probs[i].hspOff = nSlots;
-        nSlots += probs[i].hspCap;
-        maxHits = std::max(maxHits, probs[i].hits);
-    }
+
+    // round 2: the lists sized by the hit counts; steps 2 to 5
+    cpk_anchor_pass_size(probs, n, &plan);
+    const size_t nSlots = (size_t)plan.nSlots;
     int4 *dHsps = nullptr;
-    int2 *dHits = nullptr;  // seedTransitions: the hit list of every problem, the HSP list's slots and offsets
+    int2 *dHits = nullptr;  // transition path: the hit list of every problem, the HSP list's slots and offsets
     int32_t *dCount = nullptr, *dBest = nullptr, *dPred = nullptr, *dRuns = nullptr;
-    if (int rc = sc.alloc(&dHsps, (size_t)nSlots)) return rc;
-    const size_t nCount = (size_t)n * (seedTransitions ? 2 : 1);  // HSPs handed out, then the hits written
-    if (seedTransitions) {
-        if (int rc = sc.alloc(&dHits, (size_t)nSlots)) return rc;
+    if (int rc = sc.alloc(&dHsps, nSlots)) return rc;
+    if (plan.transitions) {
+        if (int rc = sc.alloc(&dHits, nSlots)) return rc;
     }
-    if (int rc = sc.alloc(&dCount, nCount)) return rc;
-    if (int rc = sc.alloc(&dBest, (size_t)nSlots)) return rc;
-    if (int rc = sc.alloc(&dPred, (size_t)nSlots)) return rc;
-    if (int rc = sc.alloc(&dRuns, (size_t)nSlots * 3)) return rc;
-    HIP_TRY(hipMemcpyAsync(dProbs, probs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(dCount, 0, sizeof(int32_t) * nCount, st));
+    if (int rc = sc.alloc(&dCount, (size_t)plan.nCounters)) return rc;
+    if (int rc = sc.alloc(&dBest, nSlots)) return rc;
+    if (int rc = sc.alloc(&dPred, nSlots)) return rc;
+    if (int rc = sc.alloc(&dRuns, nSlots * 3)) return rc;
+    HIP_TRY(hipMemcpyAsync(dProbs, probs, probBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dCount, 0, sizeof(int32_t) * (size_t)plan.nCounters, st));
     HIP_TRY(hipEventRecord(c->evA, st));
-    if (seedTransitions) {
-        hipLaunchKernelGGL(cpk_anchor_join<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, dKeys, prm->maxSeedOccurrences,
-                           seed.weight, dHits, dCount + n);
+    if (plan.transitions) {
+        hipLaunchKernelGGL(cpk_anchor_join<true>, perChunk, dim3(256), 0, st, dProbs, dKeys, prm.maxSeedOccurrences, seed.weight, dHits,
+                           dCount + n);
         HIP_TRY(hipGetLastError());
-        const unsigned hitChunks = (unsigned)std::min(1024, (maxHits + 255) / 256);
-        hipLaunchKernelGGL(cpk_anchor_extend, dim3((unsigned)n, hitChunks), dim3(256), 0, st, dProbs, c->dSym, dHits, *prm, variantThreshold,
-                           seed.span, dHsps, dCount);
+        const unsigned hitChunks = (unsigned)std::min(1024, (plan.maxHits + 255) / 256);
+        hipLaunchKernelGGL(cpk_anchor_extend, dim3((unsigned)n, hitChunks), dim3(256), 0, st, dProbs, c->dSym, dHits, prm,
+                           pass->variantThreshold, seed.span, dHsps, dCount);
     } else {
-        hipLaunchKernelGGL(cpk_anchor_hits<true>, dim3((unsigned)n, chunks), dim3(256), 0, st, dProbs, c->dSym, dKeys, *prm, seed.span,
-                           dHsps, dCount);
+        hipLaunchKernelGGL(cpk_anchor_hits<true>, perChunk, dim3(256), 0, st, dProbs, c->dSym, dKeys, prm, seed.span, dHsps, dCount);
     }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cpk_anchor_chain, dim3((unsigned)n), dim3(256), 0, st, dProbs, dHsps, dCount, dBest, dPred, dRuns,
-                       prm->maxHsps, trim);
+    hipLaunchKernelGGL(cpk_anchor_chain, perProblem, dim3(256), 0, st, dProbs, dHsps, dCount, dBest, dPred, dRuns, prm.maxHsps,
+                       pass->trim);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->evB, st));
-    int32_t *runs = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)nSlots);
+    int32_t *runs = (int32_t *)malloc(sizeof(int32_t) * 3 * nSlots);
     if (!runs) {
         cpk_set_error("out of memory");
         return CPECAN_ENOMEM;
     }
-    hipError_t e = hipMemcpyAsync(probs, dProbs, sizeof(CpkAnchorProblem) * (size_t)n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(runs, dRuns, sizeof(int32_t) * 3 * (size_t)nSlots, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(probs, dProbs, probBytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(runs, dRuns, sizeof(int32_t) * 3 * nSlots, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipEventElapsedTime(&part, c->evA, c->evB);
     if (e != hipSuccess) {
