@@ -722,7 +722,7 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     if (in.knobs.traceHost)
         fprintf(stderr, "cpecan class %d: %d regions, widest diagonal %d, LDS %zu B (forward launch %zu B), waves %d / %d, %s%s%s%s%s\n", k,
                 c.regionCount, c.geo.maxWidth, c.ldsBytes, c.ldsBytesFwd, c.waves, c.wavesTrace,
-                c.split ? (c.fused ? "one launch" : "two launches") : (c.threads > CPK_WAVE ? "a team of waves per region" : "one wave per region"),
+                c.split ? (c.fused ? "one launch" : "two launches") : (c.threads > 4 * CPK_WAVE ? "a team of waves per region (eight)" : c.threads > CPK_WAVE ? "a team of waves per region (four)" : "one wave per region"),
                 c.geo.useGlobalRoll ? ", rolling rows in global memory" : "", c.abs ? ", absolute positions" : "",
                 c.dense ? ", three waves per SIMD" : "", c.geo.expInSweep ? ", expectation events inside the traceback" : "");
     c.ringEl = c.geo.ringCells * S;

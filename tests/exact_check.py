@@ -14,6 +14,7 @@ sys.path.insert(0, HERE)
 from cpecan_amd import api  # noqa: E402
 from cpecan_amd.workload import make_pair  # noqa: E402
 import oracle_binding as ob  # noqa: E402
+import indel_cases as ic  # noqa: E402
 
 
 def sm(mtype):
@@ -77,6 +78,25 @@ def main():
         got = api.computeForwardProbability(sx, sy, (), p, sm(mtype), rl, rr)
         want = ob.forward_prob(ob.model(mtype), sx, sy, (), ob.params(), rl, rr)
         assert got == want, ("forward", mtype, length, got, want)
+    # the three lists of the indel emitter from each of its list passes, under models whose X and Y numbers differ: one
+    # wave per region at a threshold that lists most cells, the packed kernel, the team of four waves
+    edge = ic.edges_case("threeStateAsymmetric")
+    one_wave = ic.Case("exact-65x65", edge.model, tuple(p for p in edge.problems if (len(p[0]), len(p[1])) == (65, 65))[1:2], dict(threshold=1e-4))
+    packed = ic.packed_cases("trained", 1e-3)[1][1]
+    packed = ic.Case("exact-packed", packed.model, packed.problems[:4], packed.pkw)
+    for case, knob in ((one_wave, None), (packed, "2"), (ic.team_cases("fiveStateAsymmetric", 1e-3)[0][2], None)):
+        if knob:
+            os.environ["CPECAN_PACKED"] = knob
+        with api.Batch(ic.model_pair(case.model)[0], api.pairwiseAlignmentBandingParameters_construct(**case.pkw), emit=api.EMIT_INDEL) as b:
+            b.add_many(case.problems)
+            b.upload()
+            b.run()
+            b.download()
+            for i, want in enumerate(ic.oracle_lists(case)):
+                for which in range(3):
+                    assert np.array_equal(np.asarray(b.result(i, which), dtype=np.int64), want[which]), (case.name, i, which)
+        os.environ.pop("CPECAN_PACKED", None)
+        print("exact: indel lists of %s equal (%d entries)" % (case.name, sum(len(t) for ls in ic.oracle_lists(case) for t in ls)), flush=True)
     print("exact: forward probabilities equal", flush=True)
 
 
