@@ -83,9 +83,16 @@ class AnchorParams(C.Structure):
                 ("xDrop", C.c_int32), ("hspThreshold", C.c_int32), ("maxHsps", C.c_int32), ("seedTransitions", C.c_int32)]
 
 
+def _options_word(k):
+    return property(lambda self: self.reserved[k], lambda self, v: self.reserved.__setitem__(k, int(v)))
+
+
 class AnchorOptions(C.Structure):
-    """cpecan_anchor_options: what cpecan_anchor_params has no room for (anchor_options makes one)."""
+    """cpecan_anchor_options: what cpecan_anchor_params has no room for (anchor_options makes one).  `reserved` stays the
+    seven words behind the threshold, as callers index them; the C struct has carved gappedExtension, yDrop and
+    gappedMaxDiagonals out of words 0 to 2, which the three properties read and write, and words 3 to 6 are reserved."""
     _fields_ = [("transitionHspThreshold", C.c_int32), ("reserved", C.c_int32 * 7)]
+    gappedExtension, yDrop, gappedMaxDiagonals = _options_word(0), _options_word(1), _options_word(2)
 
 
 class AnchorProblem(C.Structure):
@@ -402,12 +409,15 @@ def anchor_params_default(**overrides):
     return q
 
 
-def anchor_options(transitionHspThreshold=0):
-    """cpecan_anchor_options_default with the threshold set: what an HSP must score that no seed hit with equal words
-    extends to (seedTransitions 1); 0 = hspThreshold, i.e. no threshold of its own."""
+def anchor_options(transitionHspThreshold=0, gappedExtension=0, yDrop=0, gappedMaxDiagonals=0):
+    """cpecan_anchor_options_default with fields set.  transitionHspThreshold: what an HSP must score that no seed hit with
+    equal words extends to (seedTransitions 1); 0 = hspThreshold, i.e. no threshold of its own.  gappedExtension 1: the
+    chained HSPs are extended across indels before they are trimmed (include/cpecan_hip.h), with yDrop (0 = 9400) ending an
+    extension and at most gappedMaxDiagonals (0 = 4096; 64 .. 4096) anti-diagonals each; both want gappedExtension."""
     o = AnchorOptions()
     _check(lib().cpecan_anchor_options_default(C.byref(o)), "cpecan_anchor_options_default")
     o.transitionHspThreshold = int(transitionHspThreshold)
+    o.gappedExtension, o.yDrop, o.gappedMaxDiagonals = gappedExtension, yDrop, gappedMaxDiagonals
     return o
 
 

@@ -8,6 +8,8 @@
  * its reverse complement, and a pair on the minus strand gets a cigar with "<length> 0 -" for the query.
  * --seedTransitions lets a seed hit of the anchor finder carry one transition (cpecan_anchor_params.seedTransitions = 1).
  * --transitionHspThreshold N asks N of an HSP that only such hits extend to (cpecan_anchor_options); it needs --seedTransitions.
+ * --gapped extends the chained HSPs of the anchor finder across indels (cpecan_anchor_options.gappedExtension); --yDrop N
+ * sets what ends such an extension and needs --gapped.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -33,7 +35,8 @@ static void usage(void) {
                     "-y --loadHmm FILE  -g --device N  -s --strand plus|minus|both (default plus)\n"
                     "-t --seedTransitions (anchor seed hits may carry one transition)  -h --help\n"
                     "-T --transitionHspThreshold N (with --seedTransitions: an HSP that no exact seed hit extends to must score N;\n"
-                    "   at least the HSP threshold, 800)\n");
+                    "   at least the HSP threshold, 800)\n"
+                    "-G --gapped (gapped extension of the chained HSPs)  -Y --yDrop N (with --gapped; default 9400)\n");
 }
 
 static int fail(const char *what) {
@@ -106,15 +109,18 @@ int main(int argc, char **argv) {
     const char *hmmFile = NULL;
     long long device = 0;
     int strandMode = CPECAN_STRAND_PLUS, seedTransitions = 0, haveThreshold = 0;
-    long long transitionHspThreshold = 0;
+    long long transitionHspThreshold = 0, yDrop = 0;
+    int gapped = 0, haveYDrop = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
                                        {"strand", required_argument, 0, 's'},
                                        {"seedTransitions", no_argument, 0, 't'},
                                        {"transitionHspThreshold", required_argument, 0, 'T'},
+                                       {"gapped", no_argument, 0, 'G'},
+                                       {"yDrop", required_argument, 0, 'Y'},
                                        {0, 0, 0, 0}};
-    for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:", longOpts, NULL)) != -1;) {
+    for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:GY:", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
         case 'y': hmmFile = optarg; break;
@@ -133,11 +139,23 @@ int main(int argc, char **argv) {
             }
             haveThreshold = 1;
             break;
+        case 'G': gapped = 1; break;
+        case 'Y':
+            if (sscanf(optarg, "%lld", &yDrop) != 1 || yDrop < 1 || yDrop > 0x7fffffffLL) {
+                usage();
+                return 1;
+            }
+            haveYDrop = 1;
+            break;
         default: usage(); return 1;
         }
     }
     if (haveThreshold && !seedTransitions) {
         fprintf(stderr, "cpecan_align: --transitionHspThreshold needs --seedTransitions\n");
+        return 1;
+    }
+    if (haveYDrop && !gapped) {
+        fprintf(stderr, "cpecan_align: --yDrop needs --gapped\n");
         return 1;
     }
     if (argc - optind != 2) { /* cPecanAlign.c:93-96 */
@@ -159,6 +177,8 @@ int main(int argc, char **argv) {
     cpecan_anchor_options anchorOptions;
     cpecan_anchor_options_default(&anchorOptions);
     anchorOptions.transitionHspThreshold = (int32_t)transitionHspThreshold;
+    anchorOptions.gappedExtension = gapped;
+    anchorOptions.yDrop = (int32_t)yDrop;
     const int64_t trim = 14, anchorMatrix = 500 * 500, repeatMaskMatrix = 500 * 500; /* pairwiseAligner.c:1340-1342 */
     const double gapGamma = 0.5;                                                     /* :1345 */
     Records targets = {0}, queries = {0};
@@ -189,7 +209,7 @@ int main(int argc, char **argv) {
     if (status == 0 && n > 0) {
         if (cpecan_find_anchor_runs_many_with_options(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix,
                                                       &anchorParams, (int)device, strandMode, runs, nRuns, NULL, strands,
-                                                      haveThreshold ? &anchorOptions : NULL) != CPECAN_OK)
+                                                      haveThreshold || gapped ? &anchorOptions : NULL) != CPECAN_OK)
             status = fail("anchors");
     }
     if (status == 0 && n > 0) {

@@ -8,6 +8,8 @@
  * Strand: a problem that may lie on the minus strand gets a twin in the top-level pass whose
  * Y is the reverse complement, written on the device behind the forward symbols; the chain scores of the two decide, and
  * only the chosen orientation goes on to the gaps and the splice.
+ * Gapped extension (step 5b, cpecan_anchor_options.gappedExtension) is a flag and two values on every problem of both
+ * passes; the stages work on whatever runs a pass returns, so they do not know about it.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -127,7 +129,7 @@ int cpk_anchor_check(const CpkAnchorCall *c, int64_t trim, const cpecan_anchor_p
     memcpy(pass->prm.scores, params->scores, sizeof pass->prm.scores);
     memcpy(pass->seed, params->seed, sizeof pass->seed);
     if (options) {
-        for (int k = 0; k < 7; k++)
+        for (int k = 0; k < 4; k++)
             if (options->reserved[k] != 0) {
                 cpk_set_error("%s: a reserved word of the options is not 0", c->who);
                 return CPECAN_EINVAL;
@@ -138,6 +140,21 @@ int cpk_anchor_check(const CpkAnchorCall *c, int64_t trim, const cpecan_anchor_p
             return CPECAN_EINVAL;
         }
         if (options->transitionHspThreshold != 0) pass->variantThreshold = options->transitionHspThreshold;
+        /* step 5b; what it asks for reaches the passes with the problems (mark_gapped) */
+        if (options->gappedExtension != 0 && options->gappedExtension != 1) {
+            cpk_set_error("%s: gappedExtension is 0 or 1", c->who);
+            return CPECAN_EINVAL;
+        }
+        if (options->yDrop < 0 || (options->gappedMaxDiagonals != 0 && (options->gappedMaxDiagonals < CPK_ANCHOR_GAPPED_MIN_DIAGS ||
+                                                                        options->gappedMaxDiagonals > CPK_ANCHOR_GAPPED_MAX_DIAGS))) {
+            cpk_set_error("%s: yDrop is 0 or positive, gappedMaxDiagonals 0 or %d .. %d", c->who, CPK_ANCHOR_GAPPED_MIN_DIAGS,
+                          CPK_ANCHOR_GAPPED_MAX_DIAGS);
+            return CPECAN_EINVAL;
+        }
+        if (!options->gappedExtension && (options->yDrop != 0 || options->gappedMaxDiagonals != 0)) {
+            cpk_set_error("%s: yDrop and gappedMaxDiagonals want gappedExtension", c->who);
+            return CPECAN_EINVAL;
+        }
     }
     for (int64_t i = 0; i < n; i++) {
         c->runs[i] = NULL;
@@ -301,6 +318,16 @@ int cpk_anchor_splice(const CpkAnchorCall *c, const CpkAnchorList *top, const in
     return CPECAN_OK;
 }
 
+/* Step 5b on every problem of a list, with the options' values or what their zeros stand for; the options passed the check. */
+static void mark_gapped(CpkAnchorList *l, const cpecan_anchor_options *o) {
+    if (!o || !o->gappedExtension) return;
+    const int32_t diags = o->gappedMaxDiagonals ? o->gappedMaxDiagonals : CPK_ANCHOR_GAPPED_MAX_DIAGS;
+    for (int64_t k = 0; k < l->n; k++) {
+        l->probs[k].flags |= CPK_ANCHOR_GAPPED | (diags << CPK_ANCHOR_DIAGS_SHIFT);
+        l->probs[k].yDrop = o->yDrop ? o->yDrop : CPK_ANCHOR_GAPPED_Y_DROP;
+    }
+}
+
 /* The finder behind every entry point: check, device, layout, open, pass, pick, gaps, pass, splice, close. */
 static int find_runs(const CpkAnchorCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *options) {
     CpkAnchorPass pass;
@@ -319,9 +346,11 @@ static int find_runs(const CpkAnchorCall *c, int64_t trim, const cpecan_anchor_p
     }
     if ((rc = cpk_anchor_layout(c, &top, &bytes, &nBytes, &nExtra)) != CPECAN_OK || top.n == 0) goto done;
     if ((rc = cpk_anchor_open(&ctx, c->device, bytes, nBytes, nExtra)) != CPECAN_OK) goto done;
+    mark_gapped(&top, options);
     if ((rc = cpk_anchor_pass(ctx, &pass, top.probs, top.n, &topRuns, &ms)) != CPECAN_OK) goto done;
     cpk_anchor_pick(c, &top);
     if ((rc = cpk_anchor_gaps(c, &top, topRuns, &sub)) != CPECAN_OK) goto done;
+    mark_gapped(&sub, options);
     if ((rc = cpk_anchor_pass(ctx, &pass, sub.probs, sub.n, &subRuns, &ms)) != CPECAN_OK) goto done;
     rc = cpk_anchor_splice(c, &top, topRuns, &sub, subRuns, ms);
 done:

@@ -240,9 +240,19 @@ int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]);
  * flags: CPK_ANCHOR_RC_Y -- the pass first writes the reverse complement of the lY symbols at yFwd (forward symbols of the
  * buffer) to yOff, which is even and lies in the area cpk_anchor_open reserved behind them; CPK_ANCHOR_SHARE_X -- the
  * minus twin of the problem in front of it in the list: same xOff and lX, and it reads that problem's sorted X keys
- * instead of making its own. */
+ * instead of making its own; CPK_ANCHOR_GAPPED -- the problem's chain is extended into its gaps (step 5b) with the
+ * problem's yDrop and the CPK_ANCHOR_DIAGS(flags) anti-diagonals per extension that the flags hold above the bits.  The
+ * three values of cpecan_anchor_options travel with the problem, not with CpkAnchorPass: tests/anchor_stages.py mirrors
+ * that structure at its 160 bytes and hands buffers of that size to cpk_anchor_check and cpk_anchor_pass_plan. */
 #define CPK_ANCHOR_RC_Y 1
 #define CPK_ANCHOR_SHARE_X 2
+#define CPK_ANCHOR_GAPPED 4
+#define CPK_ANCHOR_DIAGS_SHIFT 8
+#define CPK_ANCHOR_DIAGS(flags) ((flags) >> CPK_ANCHOR_DIAGS_SHIFT)
+#define CPK_ANCHOR_GAPPED_BAND 31           /* cells with |i - j| <= 31: 63 matrix diagonals, one lane each */
+#define CPK_ANCHOR_GAPPED_Y_DROP 9400       /* CPECAN_ANCHOR_GAP_OPEN + 300 * CPECAN_ANCHOR_GAP_EXTEND */
+#define CPK_ANCHOR_GAPPED_MAX_DIAGS 4096
+#define CPK_ANCHOR_GAPPED_MIN_DIAGS 64
 typedef struct {
     int64_t xOff, yOff; /* first symbol of X / Y in the context's buffer */
     int32_t lX, lY;
@@ -254,7 +264,7 @@ typedef struct {
     int64_t columns;
     int64_t yFwd;  /* CPK_ANCHOR_RC_Y: first symbol of the forward Y */
     int32_t score; /* the chain score of step 4 (sum of the chained HSPs' scores; 0 without an HSP) */
-    int32_t pad;
+    int32_t yDrop; /* CPK_ANCHOR_GAPPED: > 0; otherwise 0.  The host fills it */
 } CpkAnchorProblem;
 
 typedef struct {
@@ -299,9 +309,22 @@ int cpk_anchor_pass_plan(const CpkAnchorPass *pass, CpkAnchorProblem *probs, int
                          CpkAnchorPlan *plan);
 /* The second sizing step: hspCap and hspOff of every problem from its hit count. */
 void cpk_anchor_pass_size(CpkAnchorProblem *probs, int64_t n, CpkAnchorPlan *plan);
+/* The sizing step of a pass that extends chains (step 5b), after the chains came back: nRows -- the 64-byte scratch rows of
+ * all extensions, one per anti-diagonal; nRuns -- the run triples the assembly may write; maxGaps -- most gaps of one
+ * problem.  cpk_anchor_gapped_size also fills where every problem's rows and runs start (n + 1 values each, the last the
+ * total); touches no device.  A pass whose rows pass CPK_ANCHOR_GAPPED_BUDGET_ROWS runs its gaps in several launches,
+ * each ending at the gap boundary cpk_anchor_gapped_slice_end picks. */
+typedef struct {
+    int64_t nRows, nRuns;
+    int32_t maxGaps, pad;
+} CpkAnchorGappedPlan;
+#define CPK_ANCHOR_GAPPED_BUDGET_ROWS ((int64_t)4 << 20) /* 256 MiB of scratch */
+void cpk_anchor_gapped_size(const CpkAnchorProblem *probs, int64_t n, int64_t *rowBase, int64_t *runBase, CpkAnchorGappedPlan *plan);
+int64_t cpk_anchor_gapped_slice_end(const int64_t *bounds, int64_t nBounds, int64_t lo, int64_t budgetRows);
 /* Steps 1-5 of the anchor finder on n problems of the context's buffer.  *runs receives a malloc'd array of triples
  * (x, y, length) relative to each problem (NULL for n == 0); problem i owns triples hspOff .. hspOff + nRuns - 1, and
- * nothing else is promised about where a problem's triples lie.  *ms: kernel time added. */
+ * nothing else is promised about where a problem's triples lie: a pass that extends chains (CPK_ANCHOR_GAPPED) moves
+ * hspOff, because a problem can then have more runs than HSP slots.  *ms: kernel time added. */
 int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int32_t **runs, double *ms);
 void cpk_anchor_close(CpkAnchorCtx *c);
 

@@ -1771,6 +1771,13 @@ extern "C" int cpk_anchor_pass_plan(const CpkAnchorPass *pass, CpkAnchorProblem 
             cpk_set_error("anchor problem %lld: a twin follows the problem whose X it shares", (long long)i);
             return CPECAN_EINVAL;
         }
+        const int diags = CPK_ANCHOR_DIAGS(p.flags);
+        if ((p.flags & CPK_ANCHOR_GAPPED) ? p.yDrop <= 0 || diags < CPK_ANCHOR_GAPPED_MIN_DIAGS || diags > CPK_ANCHOR_GAPPED_MAX_DIAGS
+                                          : p.yDrop != 0 || diags != 0) {
+            cpk_set_error("anchor problem %lld: a gapped extension has a yDrop > 0 and %d .. %d anti-diagonals, and no other problem "
+                          "has either", (long long)i, CPK_ANCHOR_GAPPED_MIN_DIAGS, CPK_ANCHOR_GAPPED_MAX_DIAGS);
+            return CPECAN_EINVAL;
+        }
         if (p.flags & CPK_ANCHOR_RC_Y) plan->maxRc = std::max(plan->maxRc, p.lY);
         if (p.lX < 0 || p.lY < 0 || p.xOff < 0 || p.yOff < 0 || p.xOff + p.lX > nSym || p.yOff + p.lY > nSym ||
             p.lX > (1 << 24) || p.lY > (1 << 24) || (int64_t)p.lY * plan->hitsPerWindow > (1 << 30)) {
@@ -1790,7 +1797,7 @@ extern "C" int cpk_anchor_pass_plan(const CpkAnchorPass *pass, CpkAnchorProblem 
             plan->nKeys += (int64_t)p.capX + p.capY;
         }
         plan->maxCap = std::max(plan->maxCap, std::max(p.capX, p.capY));
-        p.hits = p.hsps = p.chained = p.nRuns = p.capped = p.score = p.pad = 0;
+        p.hits = p.hsps = p.chained = p.nRuns = p.capped = p.score = 0;
         p.columns = 0;
         p.hspCap = 0;
         p.hspOff = 0;
@@ -1809,6 +1816,119 @@ extern "C" void cpk_anchor_pass_size(CpkAnchorProblem *probs, int64_t n, CpkAnch
         plan->maxHits = std::max(plan->maxHits, probs[i].hits);
     }
     plan->nCounters = n * (plan->transitions ? 2 : 1);  // HSPs handed out, then the hits written
+}
+
+// Step 5b, after the chains are back: where the scratch rows and the runs of every problem start.  rowBase and runBase
+// hold n + 1 values each, the last the total.
+extern "C" void cpk_anchor_gapped_size(const CpkAnchorProblem *probs, int64_t n, int64_t *rowBase, int64_t *runBase,
+                                       CpkAnchorGappedPlan *plan) {
+    *plan = CpkAnchorGappedPlan{};
+    for (int64_t i = 0; i < n; i++) {
+        const bool gapped = probs[i].flags & CPK_ANCHOR_GAPPED;
+        rowBase[i] = plan->nRows;
+        runBase[i] = plan->nRuns;
+        plan->nRows += gapped ? probs[i].columns : 0;  // cpk_anchor_chain_untrimmed left the rows there
+        // every block takes a row at least, and the chained HSPs come on top; a chain that is not extended is trimmed already
+        plan->nRuns += gapped ? probs[i].columns + probs[i].chained : probs[i].nRuns;
+        if (gapped) plan->maxGaps = std::max(plan->maxGaps, probs[i].chained + 1);
+    }
+    rowBase[n] = plan->nRows;
+    runBase[n] = plan->nRuns;
+}
+
+// The end of the launch that starts at row lo: the last of the gap boundaries (ascending, the last one the total) that is
+// at most budgetRows behind lo.  A gap has at most 2 * CPK_ANCHOR_GAPPED_MAX_DIAGS rows, so with a budget of that much the
+// end lies behind lo.
+extern "C" int64_t cpk_anchor_gapped_slice_end(const int64_t *bounds, int64_t nBounds, int64_t lo, int64_t budgetRows) {
+    int64_t a = 0, b = nBounds;  // the first boundary beyond lo + budgetRows
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        if (bounds[mid] <= lo + budgetRows) a = mid + 1;
+        else b = mid;
+    }
+    return a > 0 ? bounds[a - 1] : lo;
+}
+
+// The end of a pass that extends chains (step 5b); evA is recorded.  The chains come back untrimmed with their row counts,
+// the host sizes scratch, block list and runs, the extensions run -- in several launches when the scratch would pass the
+// budget -- and the assembly trims.
+static int anchor_pass_gapped(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, PostScratch &sc,
+                              CpkAnchorProblem *dProbs, int4 *dHsps, int32_t *dCount, int32_t *dBest, int32_t *dPred, int32_t *dChain,
+                              size_t nSlots, int32_t **runsOut, double *ms) {
+    hipStream_t st = sc.stream;
+    const size_t probBytes = sizeof(CpkAnchorProblem) * (size_t)n, nGaps = nSlots + (size_t)n;  // chained + 1 <= hspCap + 1 per problem
+    float part = 0.f;
+    int32_t *dGapRow = nullptr;
+    int2 *dCounts = nullptr;
+    if (int rc = sc.alloc(&dGapRow, nGaps)) return rc;
+    if (int rc = sc.alloc(&dCounts, nGaps)) return rc;
+    HIP_TRY(hipMemsetAsync(dGapRow, 0, sizeof(int32_t) * nGaps, st));
+    HIP_TRY(hipMemsetAsync(dCounts, 0, sizeof(int2) * nGaps, st));
+    hipLaunchKernelGGL(cpk_anchor_chain_untrimmed, dim3((unsigned)n), dim3(256), 0, st, dProbs, dHsps, dCount, dBest, dPred, dChain,
+                       pass->prm.maxHsps, pass->trim, dGapRow);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evB, st));
+    HIP_TRY(hipMemcpyAsync(probs, dProbs, probBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&part, c->evA, c->evB));
+    *ms += part;
+
+    // round 3: the extensions and the assembly
+    CpkAnchorGappedPlan plan;
+    std::vector<int64_t> base(2 * ((size_t)n + 1));
+    int64_t *rowBase = base.data(), *runBase = rowBase + n + 1;
+    cpk_anchor_gapped_size(probs, n, rowBase, runBase, &plan);
+    const int64_t budget = CPK_ANCHOR_GAPPED_BUDGET_ROWS;
+    std::vector<int64_t> bounds;  // only a pass over the budget needs the gap boundaries
+    if (plan.nRows > budget) {
+        std::vector<int32_t> gapRow(nGaps);
+        HIP_TRY(hipMemcpy(gapRow.data(), dGapRow, sizeof(int32_t) * nGaps, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; i++)
+            for (int g = 0; (probs[i].flags & CPK_ANCHOR_GAPPED) && g <= probs[i].chained; g++)
+                bounds.push_back(rowBase[i] + gapRow[(size_t)probs[i].hspOff + (size_t)i + (size_t)g]);
+        bounds.push_back(plan.nRows);
+    }
+    int64_t *dBase = nullptr;
+    uint8_t *dTrace = nullptr;
+    int32_t *dBlocks = nullptr, *dRunsOut = nullptr;
+    const size_t nRunsCap = (size_t)std::max<int64_t>(plan.nRuns, 1);
+    if (int rc = sc.alloc(&dBase, base.size())) return rc;
+    if (int rc = sc.alloc(&dTrace, (size_t)std::max<int64_t>(std::min(plan.nRows, budget), 1) * 64)) return rc;
+    if (int rc = sc.alloc(&dBlocks, (size_t)std::max<int64_t>(plan.nRows, 1) * 3)) return rc;
+    if (int rc = sc.alloc(&dRunsOut, nRunsCap * 3)) return rc;
+    HIP_TRY(hipMemcpyAsync(dBase, base.data(), sizeof(int64_t) * base.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(c->evA, st));
+    for (int64_t lo = 0; lo < plan.nRows;) {
+        const int64_t hi = bounds.empty() ? plan.nRows : cpk_anchor_gapped_slice_end(bounds.data(), (int64_t)bounds.size(), lo, budget);
+        if (hi <= lo) {
+            cpk_set_error("anchor finder: a gap's extensions do not fit the scratch budget");
+            return CPECAN_EINVAL;
+        }
+        hipLaunchKernelGGL(cpk_anchor_gapped, dim3((unsigned)n, (unsigned)plan.maxGaps), dim3(64), 0, st, dProbs, c->dSym, pass->prm,
+                           dChain, dGapRow, dBase, lo, hi, dTrace, dBlocks, dCounts);
+        HIP_TRY(hipGetLastError());
+        lo = hi;
+    }
+    hipLaunchKernelGGL(cpk_anchor_assemble, dim3((unsigned)n), dim3(64), 0, st, dProbs, dChain, dGapRow, dBase, dBase + n + 1, dBlocks,
+                       dCounts, dRunsOut, pass->trim);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evB, st));
+    int32_t *runs = (int32_t *)malloc(sizeof(int32_t) * 3 * nRunsCap);
+    if (!runs) {
+        cpk_set_error("out of memory");
+        return CPECAN_ENOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(probs, dProbs, probBytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(runs, dRunsOut, sizeof(int32_t) * 3 * nRunsCap, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&part, c->evA, c->evB);
+    if (e != hipSuccess) {
+        free(runs);
+        HIP_TRY(e);
+    }
+    *ms += part;
+    *runsOut = runs;
+    return CPECAN_OK;
 }
 
 extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int32_t **runsOut,
@@ -1884,6 +2004,9 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAn
         hipLaunchKernelGGL(cpk_anchor_hits<true>, perChunk, dim3(256), 0, st, dProbs, c->dSym, dKeys, prm, seed.span, dHsps, dCount);
     }
     HIP_TRY(hipGetLastError());
+    bool gapped = false;
+    for (int64_t i = 0; i < n; i++) gapped = gapped || (probs[i].flags & CPK_ANCHOR_GAPPED);
+    if (gapped) return anchor_pass_gapped(c, pass, probs, n, sc, dProbs, dHsps, dCount, dBest, dPred, dRuns, nSlots, runsOut, ms);
     hipLaunchKernelGGL(cpk_anchor_chain, perProblem, dim3(256), 0, st, dProbs, dHsps, dCount, dBest, dPred, dRuns, prm.maxHsps,
                        pass->trim);
     HIP_TRY(hipGetLastError());

@@ -2,7 +2,8 @@
 // Integer work over a batch of sequence pairs: spaced-seed words, a k-mer join on sorted (word, position) keys, ungapped
 // x-drop extension with one hit per lane, and per-problem sort / duplicate removal / chaining with one workgroup per
 // problem.  Every result is defined on sets and sorted orders: the atomics below only hand out slots of lists that are
-// sorted before anything reads their order.
+// sorted before anything reads their order.  With cpecan_anchor_options.gappedExtension the chain is then extended into
+// the gaps between its HSPs, one wave per gap, before it is trimmed (step 5b, at the end of this file).
 //
 // Symbols are held as in stage_symbols (cpk_device_common.inl): two to a byte, low nibble = even index; the code is
 // 0..3 = a c g t, CPK_SYM_N = anything else, and bit 3 marks a lower-case (soft-masked) base.  X and Y strings of all
@@ -331,8 +332,18 @@ __device__ __forceinline__ long long anchor_block_max(long long v, long long *re
 
 // Steps 2 (duplicates) to 5, one workgroup per problem.  hsps: the problem's hspCap slots, of which the first nHsp[p] were
 // filled by cpk_anchor_hits; best / pred: hspCap ints each; runs: hspCap triples (x, y, length), relative to the problem.
-__global__ void __launch_bounds__(256) cpk_anchor_chain(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp, int32_t *bestAll,
-                                                        int32_t *predAll, int32_t *runsAll, int maxHsps, int trim) {
+//
+// UNTRIMMED (cpk_anchor_chain_untrimmed, step 5b): the pass extends chains, and a problem with CPK_ANCHOR_GAPPED leaves
+// its chain in `runs` as it is, in chain order, with nRuns == 0; gapRow gets, at hspOff + p + g for gap g = 0 .. chained,
+// the scratch rows of the gaps in front of g (anchor_gap_rows), and `columns` their total, which the host sizes by.
+__device__ __forceinline__ int anchor_gap_rows(int m, int n, bool right, bool left, int maxDiags) {
+    const int rows = min(m + n, maxDiags);
+    return (right ? rows : 0) + (left ? rows : 0);
+}
+
+template <bool UNTRIMMED>
+__device__ __forceinline__ void anchor_chain_body(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp, int32_t *bestAll,
+                                                  int32_t *predAll, int32_t *runsAll, int maxHsps, int trim, int32_t *gapRow) {
     __shared__ long long red[16];
     __shared__ int shCount;
     const int p = blockIdx.x, tid = threadIdx.x, nT = blockDim.x;
@@ -398,9 +409,28 @@ __global__ void __launch_bounds__(256) cpk_anchor_chain(CpkAnchorProblem *probs,
         // step 5: walk back from the end, then write the trimmed runs in increasing order (best[] is free: it holds the walk)
         int m = 0;
         for (int i = n > 0 ? (int)~(unsigned)endKey : -1; i >= 0; i = pred[i]) best[m++] = i;
-        int nRuns = 0;
+        int nRuns = 0, toTrim = m;
         long long columns = 0;
-        for (int k = m - 1; k >= 0; k--) {
+        if (UNTRIMMED && (pr.flags & CPK_ANCHOR_GAPPED)) {
+            int32_t *rowAt = gapRow + pr.hspOff + p;
+            const int maxDiags = CPK_ANCHOR_DIAGS(pr.flags);
+            int pX = 0, pY = 0;
+            for (int g = 0; g <= m; g++) {
+                rowAt[g] = (int32_t)columns;
+                int4 h = make_int4(pr.lX, pr.lY, 0, 0);
+                if (g < m) {
+                    h = hsp[best[m - 1 - g]];
+                    runs[3 * g] = h.x;
+                    runs[3 * g + 1] = h.y;
+                    runs[3 * g + 2] = h.z;
+                }
+                columns += anchor_gap_rows(h.x - pX, h.y - pY, g >= 1, g < m, maxDiags);
+                pX = h.x + h.z;
+                pY = h.y + h.z;
+            }
+            toTrim = 0;  // step 5 comes after the extension (cpk_anchor_assemble)
+        }
+        for (int k = toTrim - 1; k >= 0; k--) {
             const int4 h = hsp[best[k]];
             const int len = h.z - 2 * trim;
             if (len > 0) {
@@ -418,4 +448,223 @@ __global__ void __launch_bounds__(256) cpk_anchor_chain(CpkAnchorProblem *probs,
         probs[p].capped = capped;
         probs[p].score = n > 0 ? (int32_t)(endKey >> 32) : 0;  // the chain score: the strand score of a top-level pass
     }
+}
+
+__global__ void __launch_bounds__(256) cpk_anchor_chain(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp, int32_t *bestAll,
+                                                        int32_t *predAll, int32_t *runsAll, int maxHsps, int trim) {
+    anchor_chain_body<false>(probs, hspsAll, nHsp, bestAll, predAll, runsAll, maxHsps, trim, nullptr);
+}
+
+__global__ void __launch_bounds__(256) cpk_anchor_chain_untrimmed(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp,
+                                                                  int32_t *bestAll, int32_t *predAll, int32_t *runsAll, int maxHsps,
+                                                                  int trim, int32_t *gapRow) {
+    anchor_chain_body<true>(probs, hspsAll, nHsp, bestAll, predAll, runsAll, maxHsps, trim, gapRow);
+}
+
+// ---- step 5b: gapped extension of the chain (include/cpecan_hip.h: cpecan_anchor_options.gappedExtension) ----
+// One wave per (problem, gap) runs the gap's right and left extension, applies the overlap rule and writes the gap's blocks;
+// no wave waits for another.  Lane l owns the matrix diagonal i - j = l - 32 (lane 0 owns none), and the states of the two
+// anti-diagonals before d are in registers: the I predecessor (i - 1, j) is lane l - 1 of d - 1, the D predecessor
+// (i, j - 1) lane l + 1 of d - 1, the M predecessor (i - 1, j - 1) the same lane of d - 2.  A wave shift (DPP wave_shr /
+// wave_shl, which cross the 16-lane rows) fetches the neighbours; a lane without a source keeps NO_PATH.
+// NO_PATH stands for minus infinity: a state is a real sum (above -2^20: 4096 anti-diagonals of at most 130 each) or
+// exactly NO_PATH, because nothing is derived from a NO_PATH source.
+#define CPK_ANCHOR_NO_PATH (-(1 << 29))
+#define CPK_ANCHOR_IS_PATH(v) ((v) > CPK_ANCHOR_NO_PATH / 2)
+
+__device__ __forceinline__ int anchor_lane_below(int v) {  // lane l: lane l - 1's v
+    return __builtin_amdgcn_update_dpp(CPK_ANCHOR_NO_PATH, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+__device__ __forceinline__ int anchor_lane_above(int v) {  // lane l: lane l + 1's v
+    return __builtin_amdgcn_update_dpp(CPK_ANCHOR_NO_PATH, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
+
+struct AnchorReach {
+    int best, i, j;  // the best M cell; best == 0: the extension is empty
+};
+
+// The walk of one extension.  Symbol i of the gap's X is at xAt + dir * i (dir == -1: the reversed strings of a left
+// extension), likewise Y.  trace: dMax rows of 64 bytes, row d - 1 for anti-diagonal d; a lane's byte holds the source of
+// its M (bits 0-1: 0 M, 1 I, 2 D), of its I (bit 2: 0 M, 1 I) and of its D (bit 3: 0 M, 1 D).
+__device__ AnchorReach anchor_gapped_walk(const uint8_t *sym, const int *sc, int64_t xAt, int64_t yAt, int dir, int m, int n,
+                                          int yDrop, int dMax, uint8_t *trace) {
+    const int lane = threadIdx.x, k = lane - 32;
+    const int openExtend = CPECAN_ANCHOR_GAP_OPEN + CPECAN_ANCHOR_GAP_EXTEND;
+    int m1 = lane == 32 ? 0 : CPK_ANCHOR_NO_PATH, i1 = CPK_ANCHOR_NO_PATH, d1 = CPK_ANCHOR_NO_PATH;  // anti-diagonal d - 1
+    int x1 = m1, s1 = 0;                  // the largest of its three states and which (M, then I, then D)
+    int x2 = CPK_ANCHOR_NO_PATH, s2 = 0;  // the same of d - 2
+    AnchorReach r = {0, 0, 0};
+    int topBefore = 0;
+    for (int d = 1; d <= dMax; d++) {
+        const int i = (d + k) >> 1, j = (d - k) >> 1;
+        const bool cell = lane >= 1 && ((d + k) & 1) == 0 && i >= 0 && i <= m && j >= 0 && j <= n;
+        const int belowM = anchor_lane_below(m1), belowI = anchor_lane_below(i1);
+        const int aboveM = anchor_lane_above(m1), aboveD = anchor_lane_above(d1);
+        int mNew = CPK_ANCHOR_NO_PATH, iNew = CPK_ANCHOR_NO_PATH, dNew = CPK_ANCHOR_NO_PATH;
+        unsigned bits = 0;
+        if (cell) {
+            if (i >= 1 && j >= 1 && CPK_ANCHOR_IS_PATH(x2)) {
+                mNew = x2 + anchor_score(sc, anchor_sym(sym, xAt + (int64_t)dir * (i - 1)), anchor_sym(sym, yAt + (int64_t)dir * (j - 1)));
+                bits = (unsigned)s2;
+            }
+            if (i >= 1 && (CPK_ANCHOR_IS_PATH(belowM) || CPK_ANCHOR_IS_PATH(belowI))) {
+                const int open = belowM - openExtend, extend = belowI - CPECAN_ANCHOR_GAP_EXTEND;  // a tie goes to M
+                iNew = max(open, extend);
+                bits |= extend > open ? 4u : 0u;
+            }
+            if (j >= 1 && (CPK_ANCHOR_IS_PATH(aboveM) || CPK_ANCHOR_IS_PATH(aboveD))) {
+                const int open = aboveM - openExtend, extend = aboveD - CPECAN_ANCHOR_GAP_EXTEND;
+                dNew = max(open, extend);
+                bits |= extend > open ? 8u : 0u;
+            }
+        }
+        trace[(size_t)(d - 1) * 64 + lane] = (uint8_t)bits;
+        int xNew = mNew, sNew = 0;
+        if (iNew > xNew) xNew = iNew, sNew = 1;
+        if (dNew > xNew) xNew = dNew, sNew = 2;
+        // wave-uniform: the largest M of d, on the smallest i - j among equals, and top(d)
+        long long key = (long long)mNew * 64 + (63 - lane);
+        int top = xNew;
+        for (int o = 32; o > 0; o >>= 1) {
+            const long long u = __shfl_xor(key, o);
+            key = u > key ? u : key;
+            top = max(top, __shfl_xor(top, o));
+        }
+        const int dBest = (int)(key >> 6);
+        if (dBest > r.best) {  // strictly: the smallest d keeps it
+            const int kBest = 63 - (int)(key & 63) - 32;
+            r.best = dBest;
+            r.i = (d + kBest) >> 1;
+            r.j = (d - kBest) >> 1;
+        }
+        // both anti-diagonals a cell reads are under the bound: nothing that follows can reach it
+        if (top < r.best - yDrop && topBefore < r.best - yDrop) break;
+        topBefore = top;
+        x2 = x1, s2 = s1;
+        x1 = xNew, s1 = sNew;
+        m1 = mNew, i1 = iNew, d1 = dNew;
+    }
+    return r;
+}
+
+// The way back from the best cell in state M to (0, 0); every M step is the aligned column (i - 1, j - 1), and the maximal
+// runs of them on one matrix diagonal are the blocks.  The walk meets them from the last to the first.  A right extension
+// (left == false) has its corner (cX, cY) below: block (i, j, len) is (cX + i, cY + j, len), written from slot cap - 1
+// downwards so that they end up ascending in the last slots.  A left extension walked the reversed strings from the corner
+// above: the block is (cX - i - len, cY - j - len, len), ascending as met, written from slot 0 upwards.  Every lane walks;
+// lane 0 writes.  Returns the number of blocks (at most cap: a block takes two anti-diagonals and a gap between two one).
+__device__ int anchor_gapped_blocks(const uint8_t *trace, AnchorReach r, bool left, int cX, int cY, int32_t *out, int cap) {
+    int i = r.i, j = r.j, state = 0, nBlocks = 0, len = 0;
+    while (i >= 0 && j >= 0 && i + j > 0) {  // (0, 0) is reached in state M: I and D have no path there
+        const unsigned bits = trace[(size_t)(i + j - 1) * 64 + (i - j + 32)];
+        if (state == 0) {
+            i--, j--, len++;  // the block so far: (i, j, len)
+            state = (int)(bits & 3);
+            if (state != 0 || (i == 0 && j == 0)) {
+                if (threadIdx.x == 0 && nBlocks < cap) {
+                    int32_t *q = out + 3 * (left ? nBlocks : cap - 1 - nBlocks);
+                    q[0] = left ? cX - i - len : cX + i;
+                    q[1] = left ? cY - j - len : cY + j;
+                    q[2] = len;
+                }
+                nBlocks++;
+                len = 0;
+            }
+        } else if (state == 1) {
+            i--;
+            state = (bits & 4) ? 1 : 0;
+        } else {
+            j--;
+            state = (bits & 8) ? 2 : 0;
+        }
+    }
+    return min(nBlocks, cap);
+}
+
+// gapRow, rowBase: where the rows of a gap start (cpk_anchor_chain_untrimmed, cpk_anchor_gapped_size).  A launch does the
+// gaps whose rows start in [lo, hi), a range the host cuts at gap boundaries so that `trace` holds hi - lo rows.  blocks: a
+// triple per row of the whole pass, gap by gap as the rows lie: the right extension's, then the left one's.  counts: per gap
+// the blocks kept of either (zeroed before the first launch: a gap without rows is never visited).
+__global__ void __launch_bounds__(64) cpk_anchor_gapped(const CpkAnchorProblem *probs, const uint8_t *sym, CpkAnchorParams prm,
+                                                        const int32_t *chainAll, const int32_t *gapRow, const int64_t *rowBase,
+                                                        int64_t lo, int64_t hi, uint8_t *trace, int32_t *blocks, int2 *counts) {
+    __shared__ int sc[25];
+    if (threadIdx.x < 25) sc[threadIdx.x] = prm.scores[threadIdx.x];
+    __syncthreads();
+    const int p = blockIdx.x, g = blockIdx.y;
+    const CpkAnchorProblem pr = probs[p];
+    const int c = pr.chained;
+    if (!(pr.flags & CPK_ANCHOR_GAPPED) || g > c) return;
+    const int32_t *chain = chainAll + 3 * pr.hspOff;
+    const int aX = g ? chain[3 * (g - 1)] + chain[3 * (g - 1) + 2] : 0, aY = g ? chain[3 * (g - 1) + 1] + chain[3 * (g - 1) + 2] : 0;
+    const int bX = g < c ? chain[3 * g] : pr.lX, bY = g < c ? chain[3 * g + 1] : pr.lY;
+    const int m = bX - aX, n = bY - aY;
+    const bool right = g >= 1, left = g < c;
+    const int rows = min(m + n, CPK_ANCHOR_DIAGS(pr.flags)), rowsR = right ? rows : 0;
+    const int64_t row0 = rowBase[p] + gapRow[pr.hspOff + p + g];
+    if (rows == 0 || row0 < lo || row0 >= hi) return;
+    uint8_t *traceR = trace + (size_t)(row0 - lo) * 64, *traceL = traceR + (size_t)rowsR * 64;
+    int32_t *blocksR = blocks + 3 * row0, *blocksL = blocksR + 3 * rowsR;
+    AnchorReach R = {0, 0, 0}, L = {0, 0, 0};
+    if (right) R = anchor_gapped_walk(sym, sc, pr.xOff + aX, pr.yOff + aY, 1, m, n, pr.yDrop, rows, traceR);
+    if (left) L = anchor_gapped_walk(sym, sc, pr.xOff + bX - 1, pr.yOff + bY - 1, -1, m, n, pr.yDrop, rows, traceL);
+    if (R.i + L.i > m || R.j + L.j > n) {  // they overlap: the smaller best goes, the left one on a tie
+        if (R.best < L.best) R.best = 0;
+        else L.best = 0;
+    }
+    __threadfence();  // the bytes other lanes stored are read below
+    const int nR = R.best > 0 ? anchor_gapped_blocks(traceR, R, false, aX, aY, blocksR, rows) : 0;
+    const int nL = L.best > 0 ? anchor_gapped_blocks(traceL, L, true, bX, bY, blocksL, rows) : 0;
+    if (threadIdx.x == 0) counts[pr.hspOff + p + g] = make_int2(nR, nL);
+}
+
+// Assembly and step 5, thread 0 of a workgroup per problem as in cpk_anchor_chain: per gap the right blocks, the left
+// blocks, then the next HSP; neighbours that continue each other merged; every merged block trimmed.  The problem's runs go
+// to runBase[p] of runsOut, where hspOff points afterwards; a problem whose chain was not extended has its runs copied.
+__global__ void __launch_bounds__(64) cpk_anchor_assemble(CpkAnchorProblem *probs, const int32_t *chainAll, const int32_t *gapRow,
+                                                          const int64_t *rowBase, const int64_t *runBase, const int32_t *blocks,
+                                                          const int2 *counts, int32_t *runsOut, int trim) {
+    if (threadIdx.x != 0) return;
+    const int p = blockIdx.x;
+    const CpkAnchorProblem pr = probs[p];
+    const int32_t *chain = chainAll + 3 * pr.hspOff;
+    int32_t *out = runsOut + 3 * runBase[p];
+    probs[p].hspOff = runBase[p];
+    if (!(pr.flags & CPK_ANCHOR_GAPPED)) {
+        for (int k = 0; k < 3 * pr.nRuns; k++) out[k] = chain[k];
+        return;
+    }
+    const int c = pr.chained, maxDiags = CPK_ANCHOR_DIAGS(pr.flags);
+    int nRuns = 0, x = 0, y = 0, len = 0, pX = 0, pY = 0;
+    long long columns = 0;
+    auto flush = [&]() {
+        if (len - 2 * trim > 0) {
+            out[3 * nRuns] = x + trim;
+            out[3 * nRuns + 1] = y + trim;
+            out[3 * nRuns + 2] = len - 2 * trim;
+            nRuns++;
+            columns += len - 2 * trim;
+        }
+    };
+    auto put = [&](int bx, int by, int blen) {
+        if (len > 0 && x + len == bx && y + len == by) {
+            len += blen;
+        } else {
+            flush();
+            x = bx, y = by, len = blen;
+        }
+    };
+    for (int g = 0; g <= c; g++) {
+        const int hX = g < c ? chain[3 * g] : pr.lX, hY = g < c ? chain[3 * g + 1] : pr.lY, hLen = g < c ? chain[3 * g + 2] : 0;
+        const int rowsR = g >= 1 ? min(hX - pX + hY - pY, maxDiags) : 0;
+        const int2 cnt = counts[pr.hspOff + p + g];
+        const int32_t *q = blocks + 3 * (rowBase[p] + gapRow[pr.hspOff + p + g] + rowsR);
+        for (int t = -cnt.x; t < cnt.y; t++) put(q[3 * t], q[3 * t + 1], q[3 * t + 2]);  // the right ones end where the left ones start
+        if (g < c) put(hX, hY, hLen);
+        pX = hX + hLen;
+        pY = hY + hLen;
+    }
+    flush();
+    probs[p].nRuns = nRuns;
+    probs[p].columns = columns;
 }

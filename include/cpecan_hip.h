@@ -148,7 +148,8 @@ int64_t cpecan_filter_to_remove_overlap(const int64_t *pairs, int64_t n, int64_t
 
 /* ---- the anchor finder: anchors from the two sequences alone ----
  * Fills the role lastz has in the reference (getBlastPairsForPairwiseAlignmentParameters, pairwiseAligner.c:1005-1196)
- * with a finder of this library's own, defined in DESIGN.md section 7; it is NOT lastz and does not reproduce its output.
+ * with a finder of this library's own, defined in DESIGN.md section 7; it is NOT lastz and does not reproduce its output
+ * (its gapped extension, cpecan_anchor_options.gappedExtension, is an option that is off by default).
  * Per problem: (1) spaced-seed words of X and Y; words that occur more than maxSeedOccurrences times on their own side are
  * dropped; a hit is a pair of windows with equal words or, with seedTransitions 1, words that differ by one transition
  * (a <-> g or c <-> t) at one compared position, as lastz --transition allows; (2) ungapped x-drop extension of every hit to an HSP, kept from
@@ -240,14 +241,37 @@ int cpecan_find_anchor_runs_many_stranded(const cpecan_anchor_problem *problems,
  * 6, both orientations of step 0.  T == hspThreshold (or 0) is the result without options; T == INT32_MAX is the result of
  * seedTransitions 0 in everything but cpecan_anchor_stats.hits, which counts every hit whatever becomes of it.  With
  * seedTransitions 0 there is no variant hit and T has no effect.  tests/anchor_model_threshold.py states it in Python. */
+/* gappedExtension 1 (step 5b): before step 5 trims it, the chain of step 4 is extended into the
+ * gaps between its HSPs.  Gap g = 0 .. c of a chain of c HSPs is the rectangle from the end of HSP g, (0, 0) for g = 0, to
+ * the start of HSP g + 1, (lX, lY) for g = c.  Gap g >= 1 gets a RIGHT extension from its lower corner and gap g < c a
+ * LEFT one from its upper corner, which is the right extension of the two reversed gap strings.  A right extension is a
+ * three-state affine-gap walk (M, I, D; no I <-> D step) over the cells (i, j) of the gap with |i - j| <= 31, one
+ * anti-diagonal d = i + j at a time up to min(m + n, gappedMaxDiagonals): substitution scores of the params, a gap of L
+ * columns costs CPECAN_ANCHOR_GAP_OPEN + L * CPECAN_ANCHOR_GAP_EXTEND (lastz's values for HOXD70).  It keeps the best M cell
+ * (the first on the smallest d, then the smallest i - j) and stops after an anti-diagonal when the largest value of that
+ * one AND of the one before are both more than yDrop under the best.  The aligned columns on the way from (0, 0) to the
+ * best cell, as maximal runs on one matrix diagonal, are the extension's blocks; with best == 0 it is empty.  When the two
+ * extensions of a gap overlap (iR + iL > m or jR + jL > n for their best cells) the one with the smaller best is dropped
+ * whole, the left one on a tie.  Per gap the right blocks, the left blocks, then the next HSP are concatenated, neighbours
+ * that continue each other are merged, and step 5 trims every merged block.  Runs, anchorColumns, both largestGap figures
+ * and the rectangles of step 6 come from this list; hits, hsps, chained, capped and the strand score are those of steps 1-4.
+ * It holds wherever steps 1-5 run: the top level, the gaps of step 6, both orientations of step 0.  Every tie is fixed:
+ * M before I before D for the source of M, M before I (D) for the source of I (D).  tests/anchor_model_gapped.py states
+ * it in Python.  gappedExtension 0 is the result and the launches without it. */
+#define CPECAN_ANCHOR_GAP_OPEN 400
+#define CPECAN_ANCHOR_GAP_EXTEND 30
 typedef struct cpecan_anchor_options {
     int32_t transitionHspThreshold; /* 0: the same as hspThreshold; otherwise >= hspThreshold */
-    int32_t reserved[7];            /* must be 0 */
+    int32_t gappedExtension;        /* 0 or 1 */
+    int32_t yDrop;                  /* 0: 9400 = GAP_OPEN + 300 * GAP_EXTEND, lastz's default; otherwise > 0 */
+    int32_t gappedMaxDiagonals;     /* 0: 4096; otherwise 64 .. 4096 */
+    int32_t reserved[4];            /* must be 0 */
 } cpecan_anchor_options;            /* 32 bytes */
 int cpecan_anchor_options_default(cpecan_anchor_options *o); /* all 0 */
 /* cpecan_find_anchor_runs_many_stranded with options; NULL = the defaults, and then it IS that function: every entry point
- * above is a call of this one with NULL.  A negative threshold, one in (0, hspThreshold) or a nonzero reserved word is
- * CPECAN_EINVAL, refused before a device is looked for. */
+ * above is a call of this one with NULL.  CPECAN_EINVAL, refused before a device is looked for: a negative threshold or
+ * one in (0, hspThreshold); gappedExtension outside {0, 1}; a negative yDrop; gappedMaxDiagonals outside 0, 64 .. 4096; a
+ * nonzero yDrop or gappedMaxDiagonals without gappedExtension; a nonzero reserved word. */
 int cpecan_find_anchor_runs_many_with_options(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
                                               int64_t anchorMatrixBiggerThanThis, int64_t repeatMaskMatrixBiggerThanThis,
                                               const cpecan_anchor_params *params, int device, int strandMode, int64_t **runs,
