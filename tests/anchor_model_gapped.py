@@ -7,6 +7,7 @@ other step reused from there.  Written from the definition: cells, three states,
     extend_chain(cx, cy, chain, score, yDrop, maxDiagonals) the merged, untrimmed blocks of a chain [(x, y, length)]
     anchors_once(sX, sY, trim, softMask, params, seedTransitions, threshold, gapped, yDrop, gappedMaxDiagonals)
     find_anchor_runs(...) / find_anchor_runs_stranded(...)  step 6 and step 0 around them
+    gap_rows(chain, lX, lY, maxDiagonals)                   the scratch rows a chain's extensions take in a pass
 
 gapped, yDrop and gappedMaxDiagonals travel beside the parameter dict as the C struct holds them: 0 / 1, 0 for 9400, 0 for
 4096.  With gapped == 0 this is anchor_model_threshold, integer for integer.
@@ -154,6 +155,21 @@ def extend_chain(cx, cy, chain, score, yDrop=Y_DROP, maxDiagonals=MAX_DIAGONALS)
         else:
             merged.append([x, y, length])
     return [tuple(b) for b in merged]
+
+
+def gap_rows_each(chain, lX, lY, maxDiagonals=MAX_DIAGONALS):
+    """anchor_gap_rows of cpk_anchor.inl for every gap g = 0 .. len(chain) of a chain [(x, y, length)]: the scratch rows of
+    its extensions, min(m + n, maxDiagonals) for the right one (g >= 1) and as many for the left one (g < len(chain))."""
+    c = len(chain)
+    corners = [(0, 0)] + [(x + length, y + length) for x, y, length in chain]
+    starts = [(x, y) for x, y, length in chain] + [(lX, lY)]
+    return [((g >= 1) + (g < c)) * min(starts[g][0] - corners[g][0] + starts[g][1] - corners[g][1], maxDiagonals)
+            for g in range(c + 1)]
+
+
+def gap_rows(chain, lX, lY, maxDiagonals=MAX_DIAGONALS):
+    """The scratch rows of a problem in a pass with step 5b: anchor_gap_rows summed over the gaps of its chain."""
+    return sum(gap_rows_each(chain, lX, lY, maxDiagonals))
 
 
 def anchors_once(sX, sY, trim, softMask, params, seedTransitions=0, threshold=0, gapped=0, yDrop=0, gappedMaxDiagonals=0):
