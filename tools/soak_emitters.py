@@ -3,7 +3,8 @@
 choice of kernels, with the packed kernel off (CPECAN_PACKED=0), with the team kernel forced from 100 cells (CPECAN_TEAM=100) or
 off (CPECAN_TEAM=0), and -- expectations -- with the second pass everywhere (CPECAN_EXP_INSWEEP=0).  The three lists of the indel
 emitter must be identical under every setting; the expectation counts within 1e-8 of one another (the order of the sums differs)
-and, every other round, within 1e-5 of the oracle's.  usage: python tools/soak_emitters.py [rounds] [seed]"""
+and, every other round, within 1e-5 of the oracle's.
+The fixed cases -- every build of the expectation emitter per problem against the oracle -- are tests/test_gpu_expect.py.  usage: python tools/soak_emitters.py [rounds] [seed]"""
 import os, random, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
