@@ -38,6 +38,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <algorithm>
 #include <atomic>
 #include <utility>
@@ -84,6 +85,7 @@ extern "C" const char *cpk_last_error(void) { return g_err; }
 // ------------------------------------------------------------------------------------------------
 // host side of the HIP TU: memory, launch, timing
 // ------------------------------------------------------------------------------------------------
+#include "cpk_kernel_table.inl"
 #include "cpk_plan.inl"
 
 // ------------------------------------------------------------------------------------------------
@@ -892,7 +894,7 @@ static int stage_reserve(CpkDevice *d, size_t bytes) {
 // become queue items, longest first
 static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regions, const CpkSegment *segs, int S, std::vector<CpkItem> *items) {
     for (LaunchClass &c : classes) {
-        if (!c.split) continue;
+        if (!c.split()) continue;
         int64_t ringAt = 0;  // in doubles, from the class's ring pointer (dRing + oRing)
         c.itemBase = (int64_t)items->size();
         std::vector<std::pair<int64_t, CpkItem>> byCost;
@@ -907,7 +909,7 @@ static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regio
                 // fused: a segment's forward values exist when the forward wave has passed its top diagonal -- items in
                 // the order in which they become ready (that diagonal), longest first among equals
                 const int64_t cost = (int64_t)(sg.dTop - sg.tbPrev) * rg.maxWidth;
-                byCost.push_back({c.fused ? ((int64_t)0x7fffffff - sg.dTop) * ((int64_t)1 << 32) + (cost >> 8) : cost, CpkItem{(int32_t)di, si}});
+                byCost.push_back({c.fused() ? ((int64_t)0x7fffffff - sg.dTop) * ((int64_t)1 << 32) + (cost >> 8) : cost, CpkItem{(int32_t)di, si}});
             }
         }
         std::stable_sort(byCost.begin(), byCost.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
@@ -926,7 +928,7 @@ static KConsts kconsts_of(const CpkModel *model) {
 static void count_waves(CpkDevice *d) {
     d->totalWaves = 0;
     for (const LaunchClass &c : d->classes)
-        d->totalWaves += (c.split && c.wavesTrace > c.waves ? c.wavesTrace : c.wavesWith(d->activeModels)) * (c.threads / CPK_WAVE);
+        d->totalWaves += (c.split() && c.wavesTrace > c.waves ? c.wavesTrace : c.wavesWith(d->activeModels)) * (c.threads / CPK_WAVE);
 }
 
 // Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch).
@@ -981,7 +983,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
             c.oBring = oBring;
             c.oGroll = oGroll;
             c.oExpect = oExpect;
-            oRing += c.split ? c.ringTotal : c.subSlots * c.ringEl;
+            oRing += c.split() ? c.ringTotal : c.subSlots * c.ringEl;
             oRing = (oRing + 1) & ~(int64_t)1;  // the rings of a split class start on 16 bytes (Sweep::ringPut)
             oCand += c.subSlots * c.candEl;
             oRef += c.subSlots * c.refEl;
@@ -990,9 +992,9 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
             oGroll += c.subSlots * c.grollEl;
             oExpect += (int64_t)slotCount * c.waves * (c.threads / CPK_WAVE) * 128;  // a partial result per wave (and slot)
             if (c.ldsBytes > kLdsPathMaxBytes) {
-                HIP_TRY(hipFuncSetAttribute((const void *)c.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
-                if (c.fnTrace)
-                    HIP_TRY(hipFuncSetAttribute((const void *)c.fnTrace, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
+                HIP_TRY(hipFuncSetAttribute((const void *)c.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
+                if (c.fnTrace())
+                    HIP_TRY(hipFuncSetAttribute((const void *)c.fnTrace(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
             }
         }
         if (int rc = dev_alloc(d, &d->dRing, (size_t)oRing + 256)) return rc;
@@ -1042,7 +1044,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     if (int rc = dev_alloc(d, &d->dItems, items.empty() ? 1 : items.size())) return rc;
     {
         bool anyFused = false;
-        for (const LaunchClass &c : d->classes) anyFused = anyFused || c.fused;
+        for (const LaunchClass &c : d->classes) anyFused = anyFused || c.fused();
         if (anyFused)
             if (int rc = dev_alloc(d, &d->dProgress, (size_t)geo->nRegions + 1)) return rc;
     }
@@ -1104,7 +1106,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         const bool tableWave = !(twEnv && atoi(twEnv) == 0);
         int64_t nSplitRegions = 0;
         for (const LaunchClass &c : d->classes)
-            if (c.split && tableWave) {
+            if (c.split() && tableWave) {
                 hipLaunchKernelGGL(cpecan_build_diag_table_wave, dim3((unsigned)c.regionCount), dim3(64), 0, io, d->dRegions, c.regionBase,
                                    dAnchors, anchorStride, d->dSegs, geo->nStates, d->dDiags, d->dDiagPos, expansion, dynamic);
                 HIP_TRY(hipGetLastError());
@@ -1264,7 +1266,7 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
         p.bring = d->dBring ? d->dBring + c.oBring : nullptr;
         p.expectOut = d->dExpect + c.oExpect;
         p.queue = d->dQueue + i;
-        if (c.fused) {
+        if (c.fused()) {
             p.items = d->dItems + c.itemBase;
             p.itemCount = (int32_t)c.itemCount;
         }
@@ -1286,14 +1288,14 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
         }
         hipStream_t cs = onCaller ? st : d->sideStream[i];
         if (!onCaller) HIP_TRY(hipStreamWaitEvent(cs, d->evStart, 0));
-        hipLaunchKernelGGL(c.fn, dim3((unsigned)c.wavesWith(d->activeModels)), dim3((unsigned)c.threads), c.firstLdsBytes(), cs, p);
+        hipLaunchKernelGGL(c.fn(), dim3((unsigned)c.wavesWith(d->activeModels)), dim3((unsigned)c.threads), c.firstLdsBytes(), cs, p);
         HIP_TRY(hipGetLastError());
-        if (c.split && !c.fused) {  // the tracebacks of the class's regions, one queue item each, behind the forward launch
+        if (c.split() && !c.fused()) {  // the tracebacks of the class's regions, one queue item each, behind the forward launch
             KArgs t = p;
             t.items = d->dItems + c.itemBase;
             t.regionCount = (int32_t)c.itemCount;
             t.queue = d->dQueue + kMaxClasses + i;
-            hipLaunchKernelGGL(c.fnTrace, dim3((unsigned)c.wavesTrace), dim3((unsigned)c.threads), c.ldsBytes, cs, t);
+            hipLaunchKernelGGL(c.fnTrace(), dim3((unsigned)c.wavesTrace), dim3((unsigned)c.threads), c.ldsBytes, cs, t);
             HIP_TRY(hipGetLastError());
         }
         if (!onCaller) HIP_TRY(hipEventRecord(d->sideDone[i], cs));
@@ -1332,7 +1334,7 @@ extern "C" int cpk_device_download(CpkDevice *d, int32_t *counts, int32_t *segSt
             // run it again as two launches -- all forward sweeps, then all items -- which needs no hand-off inside a launch.
             bool any = false;
             for (LaunchClass &c : d->classes) {
-                if (!c.fused) continue;
+                if (!c.fused()) continue;
                 any = true;
                 unfuse(c);
             }
@@ -1658,11 +1660,10 @@ extern "C" int cpk_ref_cells(int device, const CpkModel *model, int mode, const 
 }
 
 extern "C" int64_t cpk_device_bytes(const CpkDevice *d) { return d->bytes; }
-extern "C" int cpk_device_form(const CpkDevice *d) {
-    if (d->classes.empty()) return CPECAN_FORM_WHOLE;
-    const LaunchClass &c = d->classes.back();
-    return (c.split ? (c.fused ? CPECAN_FORM_FUSED : CPECAN_FORM_SPLIT) : CPECAN_FORM_WHOLE) | (c.abs ? CPECAN_FORM_ABS : 0);
+static int form_code(const KernelForm &f) {  // CPECAN_FORM_* of a class, from the form of its first launch
+    return (f.mode == kModeFused ? CPECAN_FORM_FUSED : f.mode != kModeWhole ? CPECAN_FORM_SPLIT : CPECAN_FORM_WHOLE) | (f.abs ? CPECAN_FORM_ABS : 0);
 }
+extern "C" int cpk_device_form(const CpkDevice *d) { return d->classes.empty() ? CPECAN_FORM_WHOLE : form_code(d->classes.back().form); }
 extern "C" int cpk_device_waves(const CpkDevice *d) { return d->totalWaves; }
 
 // ------------------------------------------------------------------------------------------------

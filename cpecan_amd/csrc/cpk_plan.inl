@@ -1,8 +1,7 @@
-// cpk_plan.inl -- the launch plan of a batch: LaunchClass, the kernel pickers and plan_batch(), which decides every launch
-// of a run; cpk_device_upload (cpecan_kernels.hip) carries the plan out.
+// cpk_plan.inl -- the launch plan of a batch: LaunchClass and plan_batch(), which decides every launch of a run, its
+// kernels as forms of cpk_kernel_table.inl; cpk_device_upload (cpecan_kernels.hip) carries the plan out.
 // Part of the single HIP translation unit cpecan_kernels.hip (included there, behind the kernels); not compiled on its own.
 
-using KernelFn = void (*)(const KArgs);
 constexpr int kMaxClasses = CPK_WIDE_CLASSES + 6;  // wide classes + three packed ones, each of which may run as a split and a whole part
 
 // One kernel launch of a run: the regions [regionBase, regionBase + regionCount) of the device order, which share one
@@ -10,14 +9,17 @@ constexpr int kMaxClasses = CPK_WIDE_CLASSES + 6;  // wide classes + three packe
 struct LaunchClass {
     bool packed = false;
     int k = 0;           // class index within its kind (wide 0..3, packed 0..2)
-    KernelFn fn = nullptr;
+    // the kernel of the (first) launch and of the traceback launch of a two-launch class: split, fused, slots and the trace words are read off them
+    KernelForm form, formTrace;
+    KernelFn fn() const { return kernel_of(form); }
+    KernelFn fnTrace() const { return kernel_of(formTrace); }
     CpkGeometry geo{};   // what the kernel reads: the scalar fields describe this class
     int waves = 0;       // workgroups of the launch
     // A reserved batch (model slots, KArgs::slotModels): the SLOTS build of the kernel, and the workgroups of a run with
     // t models, 1 <= t <= the reserved count -- `waves` is the most of them, which the per-wave scratch is sized for
-    bool slots = false;
+    bool slots() const { return form.slots; }
     int wavesFor[CPECAN_MAX_MODEL_SLOTS + 1] = {};
-    int wavesWith(int nModels) const { return slots && wavesFor[nModels] < waves ? wavesFor[nModels] : waves; }
+    int wavesWith(int nModels) const { return slots() && wavesFor[nModels] < waves ? wavesFor[nModels] : waves; }
     int threads = CPK_WAVE;  // threads per workgroup: one wave, or the waves of a team
     int64_t subSlots = 0;  // scratch slots: one per wave (sweep) or one per region group of a wave (packed)
     size_t ldsBytes = 0;
@@ -25,67 +27,21 @@ struct LaunchClass {
     int regionBase = 0, regionCount = 0;
     // A SPLIT class (fewer regions than wave slots): launch 1 = forward sweeps of whole regions into per-REGION rings,
     // launch 2 = one queue item per (region, traceback segment); see kModeForward / kModeTrace in cpk_sweep.inl.
-    bool split = false;
-    bool dense = false;  // three-state match kernels allocated for three waves per SIMD (WPS = 3)
-    bool fused = false;  // split, as ONE launch (kModeFused): regions and their traceback items in one queue
-    bool abs = false;    // split, with the sweeps over absolute positions (cpk_sweep.inl "Absolute-position sweeps")
-    KernelFn fnTrace = nullptr;
+    bool split() const { return form.mode != kModeWhole; }
+    bool fused() const { return form.mode == kModeFused; }  // split, as ONE launch: regions and their traceback items in one queue
+    bool dense = false;  // the plan's decision: the three-state match kernels allocated for three waves per SIMD (WPS = 3)
+    bool abs = false;    // LDS rows for sweeps over absolute positions (set_row_form; cpk_sweep.inl "Absolute-position sweeps"): the ABS of a split class's kernels
     int wavesTrace = 0;
     int64_t itemBase = 0, itemCount = 0;  // its items in dItems
     int64_t ringTotal = 0;                // doubles of all its regions' rings (ringEl is 0 then: nothing per slot)
     int64_t ringEl = 0, candEl = 0, refEl = 0, totEl = 0, bringEl = 0, grollEl = 0;  // elements per scratch slot
     int64_t oRing = 0, oCand = 0, oRef = 0, oTot = 0, oBring = 0, oGroll = 0, oExpect = 0;  // element offsets of the class
     // LDS bytes of the first launch: the forward launch of a two-launch class has a size of its own where the plan set one
-    size_t firstLdsBytes() const { return (split && !fused && ldsBytesFwd) ? ldsBytesFwd : ldsBytes; }
+    size_t firstLdsBytes() const { return (split() && !fused() && ldsBytesFwd) ? ldsBytesFwd : ldsBytes; }
     double slotBytes() const {
         return 8.0 * ringEl + (double)sizeof(Candidate) * candEl + 16.0 * refEl + 8.0 * totEl + 8.0 * bringEl + 8.0 * grollEl;
     }
 };
-
-static KernelFn pick_packed_kernel(const CpkGeometry &g, int cls, bool dynamic, bool slots = false) {  // class k: groups of 8 << k lanes
-    const bool five = g.nStates == 5;
-    if (slots) {  // reserved batches: the expectation emitter alone reaches the packed kernel (a FORWARD batch has no narrow class)
-#define CPK_PICK_PACKED_SLOTS(D)                                                                                                          \
-    if (g.emit == CPECAN_EMIT_EXPECT && dynamic == (D)) switch (cls) {                                                                  \
-            case 0: return five ? cpecan_pairhmm_packed<5, 8, CPECAN_EMIT_EXPECT, (D), kModeWhole, true> : cpecan_pairhmm_packed<3, 8, CPECAN_EMIT_EXPECT, (D), kModeWhole, true>;    \
-            case 1: return five ? cpecan_pairhmm_packed<5, 16, CPECAN_EMIT_EXPECT, (D), kModeWhole, true> : cpecan_pairhmm_packed<3, 16, CPECAN_EMIT_EXPECT, (D), kModeWhole, true>;  \
-            case 2: return five ? cpecan_pairhmm_packed<5, 32, CPECAN_EMIT_EXPECT, (D), kModeWhole, true> : cpecan_pairhmm_packed<3, 32, CPECAN_EMIT_EXPECT, (D), kModeWhole, true>;  \
-        }
-        CPK_PICK_PACKED_SLOTS(false)
-        CPK_PICK_PACKED_SLOTS(true)
-#undef CPK_PICK_PACKED_SLOTS
-        return nullptr;
-    }
-#define CPK_PICK_PACKED(E, D)                                                                                               \
-    if (g.emit == (E) && dynamic == (D)) switch (cls) {                                                                     \
-            case 0: return five ? cpecan_pairhmm_packed<5, 8, (E), (D)> : cpecan_pairhmm_packed<3, 8, (E), (D)>;            \
-            case 1: return five ? cpecan_pairhmm_packed<5, 16, (E), (D)> : cpecan_pairhmm_packed<3, 16, (E), (D)>;          \
-            case 2: return five ? cpecan_pairhmm_packed<5, 32, (E), (D)> : cpecan_pairhmm_packed<3, 32, (E), (D)>;          \
-        }
-    CPK_PICK_PACKED(CPECAN_EMIT_MATCH, false)
-    CPK_PICK_PACKED(CPECAN_EMIT_INDEL, false)
-    CPK_PICK_PACKED(CPECAN_EMIT_EXPECT, false)
-    CPK_PICK_PACKED(CPECAN_EMIT_MATCH, true)  // per-anchor expansions
-    CPK_PICK_PACKED(CPECAN_EMIT_INDEL, true)
-    CPK_PICK_PACKED(CPECAN_EMIT_EXPECT, true)
-#undef CPK_PICK_PACKED
-    return nullptr;
-}
-// the two kernels of a split packed class (match emitter, fixed expansion; cpk_packed.inl, MODE)
-static void pick_packed_split_kernels(const CpkGeometry &g, int cls, KernelFn *fwd, KernelFn *trace) {
-    const bool five = g.nStates == 5;
-#define CPK_PICK_PACKED_SPLIT(GW)                                                                                                \
-    {                                                                                                                            \
-        *fwd = five ? cpecan_pairhmm_packed<5, GW, CPECAN_EMIT_MATCH, false, kModeForward> : cpecan_pairhmm_packed<3, GW, CPECAN_EMIT_MATCH, false, kModeForward>; \
-        *trace = five ? cpecan_pairhmm_packed<5, GW, CPECAN_EMIT_MATCH, false, kModeTrace> : cpecan_pairhmm_packed<3, GW, CPECAN_EMIT_MATCH, false, kModeTrace>;   \
-    }
-    switch (cls) {
-        case 0: CPK_PICK_PACKED_SPLIT(8) break;
-        case 1: CPK_PICK_PACKED_SPLIT(16) break;
-        default: CPK_PICK_PACKED_SPLIT(32) break;
-    }
-#undef CPK_PICK_PACKED_SPLIT
-}
 
 // Doubles of the ring a split region keeps its forward values in.  The match emitter stores the match row of every
 // diagonal and every state only where the traceback reads it back: diagonal 0, the refresh diagonals of the emitting
@@ -97,101 +53,6 @@ static int64_t split_ring_doubles(const CpkRegion &rg, int S) {
     const int64_t fullDiags = N / CPK_REFRESH_PERIOD + 3 * (int64_t)rg.nSeg + 4;  // refresh points + two resume diagonals per segment
     // + one double of padding per diagonal (match rows start and end on even doubles); an even total keeps the next region's ring aligned
     return ((int64_t)rg.cells + (N + 1) + (int64_t)(S - 1) * rg.maxWidth * fullDiags + S + 1) & ~(int64_t)1;
-}
-// dense: the three-state match kernels allocated for three waves per SIMD (cpk_sweep.inl, WPS)
-static KernelFn pick_fused_kernel(const CpkGeometry &g, bool dense, bool abs, bool three = false) {
-    const bool fast = !g.useGlobalRoll;
-    if (abs && fast) {
-        // three (round 4): built for three waves per SIMD, for classes whose LDS lets nine or more waves onto a CU
-        if (g.nStates == 5)
-            return three ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeFused, 3, true>
-                         : cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeFused, CPK_SWEEP_WAVES, true>;
-        return dense ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused, 3, true>
-                     : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused, CPK_SWEEP_WAVES, true>;
-    }
-    if (g.nStates == 5)
-        return fast ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeFused> : cpecan_pairhmm_sweep<5, false, CPECAN_EMIT_MATCH, kModeFused>;
-    if (dense)
-        return fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeFused, 3>;
-    return fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeFused> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeFused>;
-}
-// the two kernels of a split class (match emitter)
-static void pick_split_kernels(const CpkGeometry &g, bool dense, bool abs, KernelFn *fwd, KernelFn *trace, bool fwd3 = false,
-                               bool trace3 = false) {
-    const bool fast = !g.useGlobalRoll;
-    if (abs && fast) {
-        // fwd3: the forward launch has no candidate ring and 120 VGPRs or fewer; where its LDS lets nine or more waves
-        // onto a CU it runs the build for three waves per SIMD (profiles/r03_occupancy_3_waves_per_simd.txt)
-        if (g.nStates == 5) {
-            *fwd = fwd3 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeForward, 3, true>
-                        : cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeForward, CPK_SWEEP_WAVES, true>;
-            // trace3 (round 4): the traceback launch built for three waves per SIMD (168 VGPRs), for classes whose LDS lets
-            // nine or more waves onto a CU
-            *trace = trace3 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true>
-                            : cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeTrace, CPK_SWEEP_WAVES, true>;
-        } else {
-            *fwd = fwd3 ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeForward, 3, true>
-                        : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeForward, CPK_SWEEP_WAVES, true>;
-            *trace = dense ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true>
-                           : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace, CPK_SWEEP_WAVES, true>;
-        }
-        return;
-    }
-    if (g.nStates == 5) {
-        *fwd = fast ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeForward> : cpecan_pairhmm_sweep<5, false, CPECAN_EMIT_MATCH, kModeForward>;
-        *trace = fast ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_MATCH, kModeTrace> : cpecan_pairhmm_sweep<5, false, CPECAN_EMIT_MATCH, kModeTrace>;
-    } else {
-        // the forward-only kernel needs 70 VGPRs: one variant
-        *fwd = fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeForward> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeForward>;
-        if (dense)
-            *trace = fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeTrace, 3>;
-        else
-            *trace = fast ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeTrace> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeTrace>;
-    }
-}
-static KernelFn pick_dense_kernel(const CpkGeometry &g) {  // one wave per region, three-state match emitter
-    return !g.useGlobalRoll ? cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_MATCH, kModeWhole, 3> : cpecan_pairhmm_sweep<3, false, CPECAN_EMIT_MATCH, kModeWhole, 3>;
-}
-
-static KernelFn pick_kernel(const CpkGeometry &g, bool slots = false) {
-    const bool fast = !g.useGlobalRoll;  // second template argument = FAST (LDS rolling buffers + LDS symbol strings)
-    if (slots) {  // reserved batches (expectation and forward emitters): the same forms, the SLOTS builds
-        if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep == 1)
-            return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1, true>
-                                  : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1, true>;
-        if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep)
-            return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2, true>
-                                  : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2, true>;
-#define CPK_PICK_SLOTS(E)                                                                                                             \
-    if (g.emit == (E)) {                                                                                                              \
-        if (g.nStates == 5)                                                                                                           \
-            return fast ? cpecan_pairhmm_sweep<5, true, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>                           \
-                        : cpecan_pairhmm_sweep<5, false, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>;                          \
-        return fast ? cpecan_pairhmm_sweep<3, true, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>                               \
-                    : cpecan_pairhmm_sweep<3, false, (E), kModeWhole, CPK_SWEEP_WAVES, false, 0, true>;                              \
-    }
-        CPK_PICK_SLOTS(CPECAN_EMIT_EXPECT)
-        CPK_PICK_SLOTS(kEmitForward)
-#undef CPK_PICK_SLOTS
-        return nullptr;
-    }
-    if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep == 1)  // no diagonal wider than one 64-lane group
-        return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1>
-                              : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 1>;
-    if (g.emit == CPECAN_EMIT_EXPECT && fast && g.expInSweep)
-        return g.nStates == 5 ? cpecan_pairhmm_sweep<5, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2>
-                              : cpecan_pairhmm_sweep<3, true, CPECAN_EMIT_EXPECT, kModeWhole, CPK_SWEEP_WAVES, false, 2>;
-#define CPK_PICK(E)                                                                                          \
-    if (g.emit == (E)) {                                                                                     \
-        if (g.nStates == 5) return fast ? cpecan_pairhmm_sweep<5, true, (E)> : cpecan_pairhmm_sweep<5, false, (E)>; \
-        return fast ? cpecan_pairhmm_sweep<3, true, (E)> : cpecan_pairhmm_sweep<3, false, (E)>;              \
-    }
-    CPK_PICK(CPECAN_EMIT_MATCH)
-    CPK_PICK(CPECAN_EMIT_INDEL)
-    CPK_PICK(CPECAN_EMIT_EXPECT)
-    CPK_PICK(kEmitForward)
-#undef CPK_PICK
-    return nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -268,9 +129,9 @@ struct PlanInputs {
 // directly.  Over-estimating is harmless: surplus workgroups simply queue, every wave exits when the work queue is empty.
 // A team of four puts one wave on every SIMD, a team of eight two.  CPECAN_MAX_WAVES_PER_CU counts single waves and has
 // never applied to teams.
-static int waves_per_cu(KernelFn fn, size_t ldsBytes, int wavesPerWorkgroup, const PlanKnobs &knobs, int *out) {
+static int waves_per_cu(const KernelForm &form, size_t ldsBytes, int wavesPerWorkgroup, const PlanKnobs &knobs, int *out) {
     hipFuncAttributes attr;
-    HIP_TRY(hipFuncGetAttributes(&attr, (const void *)fn));
+    HIP_TRY(hipFuncGetAttributes(&attr, (const void *)kernel_of(form)));
     const int vgprAlloc = ((attr.numRegs > 0 ? attr.numRegs : 128) + kVgprGranule - 1) / kVgprGranule * kVgprGranule;
     int perSimd = kSimdVgprs / vgprAlloc;
     if (perSimd > kMaxWavesPerCU / kSimdsPerCU) perSimd = kMaxWavesPerCU / kSimdsPerCU;
@@ -304,9 +165,8 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
     LaunchClass c;
     c.packed = true;
     c.k = k;
-    c.slots = in.modelSlots > 0;
-    c.fn = pick_packed_kernel(geo, k, in.dynamic != 0, c.slots);
-    if (!c.fn) {
+    c.form = packed_form(geo, k, in.dynamic != 0, in.modelSlots > 0);
+    if (!c.fn()) {
         cpk_set_error("no packed kernel for emitter %d", geo.emit);
         return CPECAN_EINVAL;
     }
@@ -319,7 +179,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
     c.ldsBytes = sizeof(double) * (size_t)(kLdsCubics + kLdsEm + kLdsWeights + (expect ? kExpectCopies * 80 : 0)) +
                  (size_t)G * pack_group_bytes(S, GW);
     int perCU = 0;
-    if (int rc = waves_per_cu(c.fn, c.ldsBytes, 1, in.knobs, &perCU)) return rc;
+    if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in.knobs, &perCU)) return rc;
     const int64_t slots = (int64_t)perCU * in.dev.numCUs;
     c.ringEl = c.geo.ringCells * S;
     c.candEl = c.geo.fbCells;
@@ -372,7 +232,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
         cc.regionBase = (int)pBase;
         cc.regionCount = (int)pCount;
         int64_t waves = (pCount + G - 1) / G;
-        if (cc.slots) {  // t models: t times the groups, up to the wave slots of the chip
+        if (cc.slots()) {  // t models: t times the groups, up to the wave slots of the chip
             const int64_t groups = waves;
             for (int t = 1; t <= in.modelSlots; t++) {
                 cc.wavesFor[t] = (int)(groups * t < slots ? groups * t : slots);
@@ -385,8 +245,8 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
         if (part == 0) {
             int64_t nSegPart = 0;
             for (int64_t di = pBase; di < pBase + pCount; di++) nSegPart += regions[di].nSeg;
-            cc.split = true;
-            pick_packed_split_kernels(cc.geo, k, &cc.fn, &cc.fnTrace);
+            cc.form = with_mode(c.form, kModeForward, false);  // (match emitter, fixed expansion: `eligible` above)
+            cc.formTrace = with_mode(c.form, kModeTrace, false);
             int64_t wt = (nSegPart + G - 1) / G;
             if (wt > slots) wt = slots;
             cc.wavesTrace = (int)wt;
@@ -395,7 +255,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
         }
         if (in.knobs.traceHost)
             fprintf(stderr, "cpecan packed class %d: %d regions in groups of %d lanes, LDS %zu B, waves %d / %d, %s\n", k, cc.regionCount, GW,
-                    cc.ldsBytes, cc.waves, cc.wavesTrace, cc.split ? "two launches" : "whole regions");
+                    cc.ldsBytes, cc.waves, cc.wavesTrace, form_words(cc.form, false).c_str());
         (part == 0 ? packedSplit : packedWhole)->push_back(cc);
     }
     return CPECAN_OK;
@@ -414,8 +274,8 @@ static void share_packed_slots(const PlanInputs &in, std::vector<LaunchClass> *p
     for (const LaunchClass &cc : *packedSplit) total += cc.waves;
     for (const LaunchClass &cc : *packedWhole) total += cc.waves;
     int perCU0 = 0;  // (of the first class; a failed query leaves 0 and with it every class as it is)
-    for (const LaunchClass &cc : *packedSplit) if (!perCU0) (void)waves_per_cu(cc.fnTrace, cc.ldsBytes, 1, in.knobs, &perCU0);
-    for (const LaunchClass &cc : *packedWhole) if (!perCU0) (void)waves_per_cu(cc.fn, cc.ldsBytes, 1, in.knobs, &perCU0);
+    for (const LaunchClass &cc : *packedSplit) if (!perCU0) (void)waves_per_cu(cc.formTrace, cc.ldsBytes, 1, in.knobs, &perCU0);
+    for (const LaunchClass &cc : *packedWhole) if (!perCU0) (void)waves_per_cu(cc.form, cc.ldsBytes, 1, in.knobs, &perCU0);
     const int64_t room = (int64_t)perCU0 * in.dev.numCUs - in.dev.numCUs / 8;
     if (!(total > room && room > 0)) return;
     for (std::vector<LaunchClass> *part : {packedSplit, packedWhole})
@@ -423,7 +283,7 @@ static void share_packed_slots(const PlanInputs &in, std::vector<LaunchClass> *p
             const int G = CPK_WAVE / (8 << cc.k);
             int64_t w = (int64_t)cc.waves * room / total;
             cc.waves = (int)(w < 1 ? 1 : w);
-            if (cc.split) {
+            if (cc.split()) {
                 int64_t wt = (int64_t)cc.wavesTrace * room / total;
                 cc.wavesTrace = (int)(wt < cc.waves ? cc.waves : wt);
                 if (cc.wavesTrace > (int)((cc.itemCount + G - 1) / G)) cc.wavesTrace = (int)((cc.itemCount + G - 1) / G);
@@ -469,6 +329,16 @@ static void plan_expect_in_sweep(LaunchClass &c, const PlanKnobs &knobs) {
     }
 }
 
+// The build of *f for three waves per SIMD, taken where it puts more waves on a CU than *f's perCU: *p3 is its waves per CU then, else 0.
+static int take_three_waves(const PlanInputs &in, KernelForm *f, size_t ldsBytes, int perCU, int *p3) {
+    KernelForm f3 = *f;
+    f3.wps = 3;
+    if (int rc = waves_per_cu(f3, ldsBytes, 1, in.knobs, p3)) return rc;
+    if (*p3 > perCU) *f = f3;
+    else *p3 = 0;
+    return CPECAN_OK;
+}
+
 // A team of waves per region, or one wave per region -- then, maybe, the build for three waves per SIMD.  Sets the
 // class's kernel and *perCUOut, its resident workgroups per CU.
 static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut) {
@@ -489,25 +359,15 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
     // the global-memory variant.  CPECAN_TEAM=<cells> (tests, diagnostics): from that band width instead; 0: never.
     const Knob<int> &teamEnv = in.knobs.team;
     int soloPerCU = 0;
-    if (int rc = waves_per_cu(c.fn, c.ldsBytes, 1, in.knobs, &soloPerCU)) return rc;
+    if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in.knobs, &soloPerCU)) return rc;
     const bool wanted = teamEnv.set ? (teamEnv.v > 0 && c.geo.maxWidth >= teamEnv.v)
                                     : (c.geo.maxWidth > 256 && (soloPerCU <= 3 || c.geo.useGlobalRoll));
     // one workgroup per CU is all the LDS allows from ~660 cells: then eight waves share the region
     const bool big = 2 * teamLds > kCuLdsBytes;
     if (wanted && (geo.emit == CPECAN_EMIT_MATCH || geo.emit == CPECAN_EMIT_INDEL || expect) && !geo.debug &&
         c.geo.maxWidth <= CPK_WAVE * kTeamWaves * (big ? 2 : 1) * kTeamGroups && teamLds <= kCuLdsBytes) {
-        if (expect && c.slots)  // (reserved batches: the SLOTS build)
-            c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_EXPECT, true> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_EXPECT, true>)
-                          : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_EXPECT, true> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_EXPECT, true>);
-        else if (expect)  // (round 4: the expectation emitter -- its second pass shared by the team's waves)
-            c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_EXPECT> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_EXPECT>)
-                          : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_EXPECT> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_EXPECT>);
-        else if (geo.emit == CPECAN_EMIT_INDEL)  // (round 4: the three lists of the indel emitter from the team as well)
-            c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves, CPECAN_EMIT_INDEL> : cpecan_pairhmm_team<5, kTeamWaves, CPECAN_EMIT_INDEL>)
-                          : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves, CPECAN_EMIT_INDEL> : cpecan_pairhmm_team<3, kTeamWaves, CPECAN_EMIT_INDEL>);
-        else
-            c.fn = S == 5 ? (big ? cpecan_pairhmm_team<5, 2 * kTeamWaves> : cpecan_pairhmm_team<5, kTeamWaves>)
-                          : (big ? cpecan_pairhmm_team<3, 2 * kTeamWaves> : cpecan_pairhmm_team<3, kTeamWaves>);
+        // (round 4: the indel emitter's three lists and the expectation emitter -- its second pass shared by the team's waves)
+        c.form = team_form(c.form, kTeamWaves * (big ? 2 : 1));
         c.threads = CPK_WAVE * kTeamWaves * (big ? 2 : 1);
         c.geo.useGlobalRoll = 0;
         c.abs = false;
@@ -518,7 +378,7 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
         c.geo.rollDoubles = (int64_t)(2 * S + 1) * c.geo.rollStride;
         c.ldsBytes = teamLds;
         c.grollEl = 0;
-        if (int rc = waves_per_cu(c.fn, teamLds, c.threads / CPK_WAVE, in.knobs, &perCU)) return rc;
+        if (int rc = waves_per_cu(c.form, teamLds, c.threads / CPK_WAVE, in.knobs, &perCU)) return rc;
         if (perCU < 1) perCU = 1;
     } else {
         perCU = soloPerCU;
@@ -529,14 +389,10 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
         const Knob<int> &denseEnv = in.knobs.dense;
         if (S == 3 && geo.emit == CPECAN_EMIT_MATCH && !geo.debug &&
             (denseEnv.set ? denseEnv.v != 0 : geo.nWide[k] >= (int64_t)soloPerCU * in.dev.numCUs)) {
-            KernelFn f3 = pick_dense_kernel(c.geo);
             int p3 = 0;
-            if (int rc = waves_per_cu(f3, c.ldsBytes, 1, in.knobs, &p3)) return rc;
-            if (p3 > perCU) {
-                c.fn = f3;
-                c.dense = true;
-                perCU = p3;
-            }
+            if (int rc = take_three_waves(in, &c.form, c.ldsBytes, perCU, &p3)) return rc;
+            c.dense = p3 > 0;
+            if (c.dense) perCU = p3;
         }
     }
     *perCUOut = perCU;
@@ -582,26 +438,21 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
         }
         return CPECAN_OK;
     }
-    c.split = true;
+    c.form.abs = c.abs;  // the sweeps of the split modes follow the rows
     c.itemCount = nSegClass;
     // CPECAN_SPLIT=2 / 1: force the one-launch (kModeFused) / two-launch form
     // (the one-launch form addresses a region's ring with 32-bit byte offsets: Sweep::ringPut)
-    c.fused = (env.set ? env.v == 2 : oneLaunch) && maxRing < ((int64_t)1 << 28);
-    if (c.fused) {
+    if ((env.set ? env.v == 2 : oneLaunch) && maxRing < ((int64_t)1 << 28)) {
         // an item polls this often (s_sleep between polls: seconds in all) for its region's forward values; a
         // count that never comes is reported and the class re-run in two launches (cpk_device_download).
         // CPECAN_FUSED_SPIN: tests force that path with a bound of a few polls.
         c.geo.fusedSpin = in.knobs.fusedSpin.set ? in.knobs.fusedSpin.v : (1 << 24);
-        c.fn = pick_fused_kernel(c.geo, c.dense, c.abs);
+        c.form = with_mode(c.form, kModeFused, c.dense);
         int64_t slotsF = slots;
         if (c.abs && S == 5 && !in.knobs.fused3.off() && kCuLdsBytes / c.ldsBytes >= kThreeWpsLdsWaves) {
-            KernelFn f3 = pick_fused_kernel(c.geo, c.dense, c.abs, true);
             int p3 = 0;
-            if (int rc = waves_per_cu(f3, c.ldsBytes, 1, in.knobs, &p3)) return rc;
-            if (p3 > perCU) {
-                c.fn = f3;
-                slotsF = (int64_t)p3 * numCUs;
-            }
+            if (int rc = take_three_waves(in, &c.form, c.ldsBytes, perCU, &p3)) return rc;
+            if (p3) slotsF = (int64_t)p3 * numCUs;
         }
         // One CU in eight keeps a wave slot (and its 19 KB of LDS) free: a launch that fills every slot to its
         // end starves the small kernels of the batch before it -- the list consumers need a few KB of LDS --
@@ -615,7 +466,8 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
         c.subSlots = wt;
         return CPECAN_OK;
     }
-    pick_split_kernels(c.geo, c.dense, c.abs, &c.fn, &c.fnTrace);
+    c.formTrace = with_mode(c.form, kModeTrace, c.dense);
+    c.form = with_mode(c.form, kModeForward, c.dense);
     int64_t wt = slots < nSegClass ? slots : nSegClass;
     c.wavesTrace = (int)wt;
     if (wt > c.subSlots) c.subSlots = wt;
@@ -624,12 +476,9 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
     c.ldsBytesFwd = c.geo.useGlobalRoll ? c.ldsBytes : c.ldsBytes - sizeof(double) * lds_stage_doubles(geo.emit, c.abs);
     // ... and so does the traceback launch of a five-state class since round 4 (CPECAN_TRACE3=0: never)
     if (c.abs && S == 5 && !in.knobs.trace3.off() && kCuLdsBytes / c.ldsBytes >= kThreeWpsLdsWaves) {
-        KernelFn f2 = nullptr, tr3 = nullptr;
-        pick_split_kernels(c.geo, c.dense, c.abs, &f2, &tr3, false, true);
-        int p3 = 0;
-        if (int rc = waves_per_cu(tr3, c.ldsBytes, 1, in.knobs, &p3)) return rc;
-        if (p3 > perCU) {
-            c.fnTrace = tr3;
+        int p3 = 0;  // (168 VGPRs)
+        if (int rc = take_three_waves(in, &c.formTrace, c.ldsBytes, perCU, &p3)) return rc;
+        if (p3) {
             int64_t w3 = (int64_t)p3 * numCUs;
             if (w3 > nSegClass) w3 = nSegClass;
             c.wavesTrace = (int)w3;
@@ -637,12 +486,9 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
         }
     }
     if (c.abs && !in.knobs.fwd3.off() && kCuLdsBytes / c.ldsBytesFwd >= kThreeWpsLdsWaves) {
-        KernelFn f3 = nullptr, tr = nullptr;
-        pick_split_kernels(c.geo, c.dense, c.abs, &f3, &tr, true);
-        int p3 = 0;
-        if (int rc = waves_per_cu(f3, c.ldsBytesFwd, 1, in.knobs, &p3)) return rc;
-        if (p3 > perCU) {
-            c.fn = f3;
+        int p3 = 0;  // (no candidate ring and 120 VGPRs or fewer: profiles/r03_occupancy_3_waves_per_simd.txt)
+        if (int rc = take_three_waves(in, &c.form, c.ldsBytesFwd, perCU, &p3)) return rc;
+        if (p3) {
             int64_t wf = (int64_t)p3 * numCUs;
             if (wf > n) wf = n;
             c.waves = (int)even_rounds(n, wf);  // forward waves touch no per-slot scratch: subSlots stays as it is
@@ -688,9 +534,8 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     c.geo.useGlobalRoll = c.ldsBytes + 16 > kLdsPathMaxBytes;
     set_row_form(c, absWanted && !c.geo.useGlobalRoll, in.knobs);  // absolute positions are a form of the LDS rows
     plan_expect_in_sweep(c, in.knobs);
-    c.slots = in.modelSlots > 0;
-    c.fn = pick_kernel(c.geo, c.slots);
-    if (!c.fn) {
+    c.form = wide_form(c.geo, in.modelSlots > 0);
+    if (!c.fn()) {
         cpk_set_error("no kernel for emitter %d", geo.emit);
         return CPECAN_EINVAL;
     }
@@ -704,7 +549,7 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     int64_t waves = (int64_t)perCU * in.dev.numCUs;
     if (waves > n) waves = n;
     waves = even_rounds(n, waves);
-    if (c.slots) {
+    if (c.slots()) {
         // t models: t x n virtual regions -- an under-subscribed class gets more waves, a saturated one none.  (Rounds are
         // evened out per t, so the count is not monotone in t: the scratch is sized for the most.)
         const int64_t cap = (int64_t)perCU * in.dev.numCUs;
@@ -720,11 +565,8 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     c.regionCount = geo.nWide[k];
     if (int rc = plan_split_form(in, c, nSegClass, perCU)) return rc;
     if (in.knobs.traceHost)
-        fprintf(stderr, "cpecan class %d: %d regions, widest diagonal %d, LDS %zu B (forward launch %zu B), waves %d / %d, %s%s%s%s%s\n", k,
-                c.regionCount, c.geo.maxWidth, c.ldsBytes, c.ldsBytesFwd, c.waves, c.wavesTrace,
-                c.split ? (c.fused ? "one launch" : "two launches") : (c.threads > 4 * CPK_WAVE ? "a team of waves per region (eight)" : c.threads > CPK_WAVE ? "a team of waves per region (four)" : "one wave per region"),
-                c.geo.useGlobalRoll ? ", rolling rows in global memory" : "", c.abs ? ", absolute positions" : "",
-                c.dense ? ", three waves per SIMD" : "", c.geo.expInSweep ? ", expectation events inside the traceback" : "");
+        fprintf(stderr, "cpecan class %d: %d regions, widest diagonal %d, LDS %zu B (forward launch %zu B), waves %d / %d, %s\n", k,
+                c.regionCount, c.geo.maxWidth, c.ldsBytes, c.ldsBytesFwd, c.waves, c.wavesTrace, form_words(c.form, c.dense).c_str());
     c.ringEl = c.geo.ringCells * S;
     c.candEl = c.geo.fbCells * (geo.emit == CPECAN_EMIT_INDEL ? 3 : 1);  // candidate lists
     c.refEl = c.geo.refreshCells;
@@ -735,29 +577,22 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     return CPECAN_OK;
 }
 
-// back to one wave per region with a per-wave ring
+// back to one wave per region (a packed class: whole regions) with a per-wave ring
 static void unsplit(LaunchClass &c, const PlanKnobs &knobs) {
-    c.split = false;
-    c.fused = false;
-    c.fnTrace = nullptr;
+    c.form = with_mode(c.form, kModeWhole, c.dense);
+    c.formTrace = KernelForm{};
     c.itemCount = 0;
     c.ringTotal = 0;
     c.ringEl = c.geo.ringCells * c.geo.nStates;
-    if (c.packed) {
-        c.fn = pick_packed_kernel(c.geo, c.k, false);
-        c.subSlots = (int64_t)c.waves * (CPK_WAVE / (8 << c.k));
-        return;
-    }
     if (c.abs) set_row_form(c, false, knobs);
-    c.fn = c.dense ? pick_dense_kernel(c.geo) : pick_kernel(c.geo);
-    c.subSlots = c.waves;
+    c.subSlots = c.packed ? (int64_t)c.waves * (CPK_WAVE / (8 << c.k)) : c.waves;
 }
 // A fused class as two launches -- all forward sweeps, then all items -- which needs no hand-off inside a launch: what
 // a class runs as after an item of its one launch gave up waiting (cpk_device_download).  The plain two-launch kernels,
 // without the builds for three waves per SIMD, and the launch's waves for both.
 static void unfuse(LaunchClass &c) {
-    c.fused = false;
-    pick_split_kernels(c.geo, c.dense, c.abs, &c.fn, &c.fnTrace);
+    c.formTrace = with_mode(c.form, kModeTrace, c.dense);
+    c.form = with_mode(c.form, kModeForward, c.dense);
     c.wavesTrace = c.waves;
     if (c.waves > c.regionCount) c.waves = c.regionCount;
 }
@@ -782,7 +617,7 @@ static int fit_to_memory(const PlanInputs &in, const PlanFixedSizes &sz, std::ve
     if (in.knobs.memBudgetMb.set) budget = 1048576.0 * in.knobs.memBudgetMb.v;
     // split classes keep one ring per REGION (it holds every segment of the region), nothing per slot
     for (LaunchClass &c : classes) {
-        if (!c.split) continue;
+        if (!c.split()) continue;
         c.ringTotal = 0;
         for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) c.ringTotal += split_ring_doubles(in.regions[di], geo.nStates);
         c.ringEl = 0;
@@ -795,7 +630,7 @@ static int fit_to_memory(const PlanInputs &in, const PlanFixedSizes &sz, std::ve
     tally(classes, fixed, &need, &floorNeed);
     if (need > budget || need > splitBudget) {  // whole-region rings are a luxury: give them up before giving up resident waves
         for (LaunchClass &c : classes)
-            if (c.split) unsplit(c, in.knobs);
+            if (c.split()) unsplit(c, in.knobs);
         tally(classes, fixed, &need, &floorNeed);
     }
     if (floorNeed > budget) {
