@@ -143,6 +143,16 @@ class Stats(C.Structure):
     ]
 
 
+class TableInfo(C.Structure):
+    """cpecan_table_info: what Batch.table() reports of a region beside its table."""
+    _fields_ = [
+        ("x1", C.c_int64), ("y1", C.c_int64), ("cells", C.c_int64), ("ringDoubles", C.c_int64),
+        ("lX", C.c_int32), ("lY", C.c_int32), ("maxWidth", C.c_int32), ("ringCap", C.c_int32),
+        ("split", C.c_int32), ("absOk", C.c_int32), ("nSeg", C.c_int32), ("hasPos", C.c_int32),
+        ("nStates", C.c_int32), ("nRegions", C.c_int32),
+    ]
+
+
 # Every symbol include/cpecan_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "cpecan_model_default", "cpecan_model_from_hmm", "cpecan_hmm_init", "cpecan_hmm_normalise", "cpecan_hmm_write",
@@ -165,6 +175,7 @@ EXPORTS = [
     "cpecan_anchor_options_default", "cpecan_find_anchor_runs_many_with_options", "cpecan_find_anchor_runs_once_with_options",
     "cpecan_batch_reserve_models", "cpecan_batch_set_models", "cpecan_batch_expectations_slot",
     "cpecan_batch_forward_prob_slot",
+    "cpecan_batch_table_fetch",
 ]
 MAX_MODEL_SLOTS = 8  # CPECAN_MAX_MODEL_SLOTS
 OP_MATCH, OP_INDEL_X, OP_INDEL_Y = 0, 1, 2
@@ -215,6 +226,7 @@ def lib():
     L.cpecan_batch_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cpecan_batch_set_debug.argtypes = [vp, C.c_int]
     L.cpecan_batch_debug_fetch.argtypes = [vp, C.c_int64, dp, C.c_int64, dp, C.c_int64]
+    L.cpecan_batch_table_fetch.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(TableInfo), i32p, i32p, C.c_int64, i32p, C.c_int64]
     L.cpecan_get_aligned_pairs_using_anchors.argtypes = [
         C.POINTER(StateMachine), C.c_char_p, C.c_char_p, i64p, C.c_int64, C.POINTER(PairwiseAlignmentParameters),
         C.c_int, C.c_int, C.POINTER(i32p), i64p]
@@ -757,6 +769,27 @@ class Batch:
         _check(lib().cpecan_batch_debug_fetch(self._h, problem, fb.ctypes.data_as(dp), cells, tot.ctypes.data_as(dp),
                                               diagonals), "cpecan_batch_debug_fetch")
         return fb, tot
+
+    def table(self, problem, region=0):
+        """cpecan_batch_table_fetch: the band table the device built for one region of the uploaded plan (after upload(),
+        with or without run(), debug or not).  A dict: the region's facts (x1, y1, lX, lY, cells, maxWidth, ringCap,
+        ringDoubles, split, absOk, nSeg, nStates, nRegions), "diags" int32[lX+lY+1, 4] of (xmyL, width, ringOff, cellOff),
+        "dpos" int32[lX+lY+1] or None where the batch has no position words, "segs" int32[nSeg, 3] of (tbPrev, dTop,
+        tbFrom)."""
+        info = TableInfo()
+        i32p = C.POINTER(C.c_int32)
+        _check(lib().cpecan_batch_table_fetch(self._h, problem, region, C.byref(info), None, None, 0, None, 0),
+               "cpecan_batch_table_fetch")
+        n = info.lX + info.lY + 1
+        diags = np.zeros((n, 4), dtype=np.int32)
+        dpos = np.zeros(n, dtype=np.int32)
+        segs = np.zeros((max(info.nSeg, 1), 3), dtype=np.int32)
+        _check(lib().cpecan_batch_table_fetch(self._h, problem, region, C.byref(info), diags.ctypes.data_as(i32p),
+                                              dpos.ctypes.data_as(i32p), n, segs.ctypes.data_as(i32p), info.nSeg),
+               "cpecan_batch_table_fetch")
+        out = {name: int(getattr(info, name)) for name, _ in TableInfo._fields_ if name != "hasPos"}
+        out.update(diags=diags, dpos=dpos if info.hasPos else None, segs=segs[:info.nSeg])
+        return out
 
 
 def getAlignedPairsUsingAnchors(sM, sX, sY, anchorPairs, p, alignmentHasRaggedLeftEnd=False,

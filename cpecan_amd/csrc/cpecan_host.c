@@ -2195,6 +2195,49 @@ int cpecan_batch_debug_fetch(const cpecan_batch *b, int64_t problem, double *fbM
     return rc;
 }
 
+/* The band table of one region as the device built it for the plan that runs (tests/test_gpu_table.py): the region's
+ * facts come from the host's copies of the plan, the entries and position words from the device.  Needs no debug mode. */
+int cpecan_batch_table_fetch(const cpecan_batch *b, int64_t problem, int64_t regionInProblem, cpecan_table_info *info,
+                             int32_t *diags, int32_t *dpos, int64_t nDiags, int32_t *segs, int64_t nSegs) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !b->frozen) return CPECAN_ESTATE;
+    if (!info || problem < 0 || problem >= b->nProblems || regionInProblem < 0 ||
+        regionInProblem >= b->problems[problem].nRegions)
+        return CPECAN_EINVAL;
+    if (!b->dev || !b->devRegions) return CPECAN_ESTATE;
+    const HostRegion *r = &b->regions[b->problems[problem].firstRegion + regionInProblem];
+    const CpkRegion *g = &b->devRegions[r->devIndex];
+    const int dynamic = b->emit == CPECAN_EMIT_FORWARD ? 0 : b->params.dynamicAnchorExpansion; /* host_plan_init */
+    int hasPos = 0;
+    int64_t ringDoubles = 0;
+    int rc = cpk_device_table_fetch(b->dev, g, dynamic, NULL, NULL, &hasPos, &ringDoubles);
+    if (rc != CPECAN_OK) return rc;
+    memset(info, 0, sizeof *info);
+    info->x1 = r->x1;
+    info->y1 = r->y1;
+    info->cells = g->cells;
+    info->ringDoubles = ringDoubles;
+    info->lX = g->lX;
+    info->lY = g->lY;
+    info->maxWidth = g->maxWidth;
+    info->ringCap = g->ringCap;
+    info->split = g->split;
+    info->absOk = g->absOk;
+    info->nSeg = g->nSeg;
+    info->hasPos = hasPos;
+    info->nStates = is_five(b->model.type) ? 5 : 3;
+    info->nRegions = (int32_t)b->problems[problem].nRegions;
+    if (!diags) return CPECAN_OK;
+    if (nDiags != (int64_t)g->lX + g->lY + 1 || (segs && nSegs != g->nSeg)) return CPECAN_EINVAL;
+    for (int64_t s = 0; segs && s < g->nSeg; s++) {
+        const CpkSegment *sg = &b->segs[g->segOff + s];
+        segs[3 * s] = sg->tbPrev;
+        segs[3 * s + 1] = sg->dTop;
+        segs[3 * s + 2] = sg->tbFrom;
+    }
+    return cpk_device_table_fetch(b->dev, g, dynamic, (CpkDiag *)diags, dpos, &hasPos, &ringDoubles);
+}
+
 /* ------------------------------------------------------------------------------------------------
  * single-problem convenience
  * ---------------------------------------------------------------------------------------------- */

@@ -225,6 +225,11 @@ int cpk_device_post(CpkDevice *dev, const CpkPostJob *job);
 /* Runs the job on lists given by the host: `triples` (total*3 int32) is uploaded, processed and copied back. */
 int cpk_post_lists(int device, int32_t *triples, int64_t total, const CpkPostJob *job);
 int cpk_device_debug_fetch(CpkDevice *dev, double *fb, int64_t cells, double *totals, int64_t diags);
+/* The table the device built for one region of the uploaded plan (rg: its entry as cpk_device_upload left it): waits for the
+ * batch's own stream and copies the region's lX + lY + 1 entries, and its position words where the batch has them and
+ * `dynamic` is 0 (*hasPos).  diags NULL: only *hasPos and *ringDoubles (what a split region's ring was given).  No launch. */
+int cpk_device_table_fetch(CpkDevice *dev, const CpkRegion *rg, int dynamic, CpkDiag *diags, int32_t *dpos, int *hasPos,
+                           int64_t *ringDoubles);
 int64_t cpk_device_bytes(const CpkDevice *dev);
 int cpk_device_waves(const CpkDevice *dev);
 void cpk_set_error(const char *fmt, ...);

@@ -1624,6 +1624,29 @@ extern "C" int cpk_device_debug_fetch(CpkDevice *d, double *fb, int64_t cells, d
     return CPECAN_OK;
 }
 
+// The table of one region as the builders of cpk_table_gather.inl left it, for tests: read-only, no launch.  The build is
+// ordered on the batch's own stream (cpk_device_upload), so waiting for that stream is enough whether the batch has run.
+extern "C" int cpk_device_table_fetch(CpkDevice *d, const CpkRegion *rg, int dynamic, CpkDiag *diags, int32_t *dpos, int *hasPos,
+                                      int64_t *ringDoubles) {
+    CPK_ON_DEVICE(d->device);
+    if (!d->dDiags) {
+        cpk_set_error("table fetch before upload");
+        return CPECAN_ESTATE;
+    }
+    const int64_t n = (int64_t)rg->lX + rg->lY + 1;
+    if (rg->diagOff < 0 || rg->diagOff + n > d->nDiags) {
+        cpk_set_error("table fetch: region outside the batch's table");
+        return CPECAN_EINVAL;
+    }
+    *hasPos = d->dDiagPos && !dynamic;  // (the builders return in front of the position chains otherwise)
+    *ringDoubles = rg->split ? split_ring_doubles(*rg, d->geo.nStates) : 0;
+    if (!diags) return CPECAN_OK;
+    HIP_TRY(hipStreamSynchronize(d->io));
+    HIP_TRY(hipMemcpy(diags, d->dDiags + rg->diagOff, sizeof(CpkDiag) * (size_t)n, hipMemcpyDeviceToHost));
+    if (*hasPos && dpos) HIP_TRY(hipMemcpy(dpos, d->dDiagPos + rg->diagOff, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return CPECAN_OK;
+}
+
 // The reference's unit-test primitives (cpk_cells.inl): a few hundred cells at most, one lane, blocking copies.
 extern "C" int cpk_ref_cells(int device, const CpkModel *model, int mode, const CpkCellOp *ops, int64_t n, double *buf,
                              int64_t nDoubles, double total) {

@@ -459,6 +459,31 @@ int cpecan_batch_set_debug(cpecan_batch *b, int on);
 int cpecan_batch_debug_fetch(const cpecan_batch *b, int64_t problem, double *fbMatch, int64_t cells,
                              double *totalUsed, int64_t diagonals);
 
+/* Test hook: the per-diagonal band table the device built for region `regionInProblem` of problem `problem`, as the
+ * sweeps of the uploaded plan read it.  Works on any batch after cpecan_batch_upload, run or not, debug or not
+ * (CPECAN_ESTATE before upload, CPECAN_EINVAL for indices out of range); read-only, launches nothing: it waits for the
+ * batch's own stream, on which the table build is ordered, and copies the region's slice.
+ * info is always filled.  With diags != NULL the call also copies, and the counts must then be the region's own
+ * (nDiags == lX + lY + 1, nSegs == info->nSeg): diags[d] = {xmyL, width, ringOff, cellOff}; dpos[d] = the position word
+ * of the absolute-position sweeps (posF | flagF << 15 | posB << 16 | flagB << 31), written only when info->hasPos;
+ * segs[s] = {tbPrev, dTop, tbFrom} of the region's traceback segments.  dpos and segs may be NULL. */
+typedef struct {
+    int64_t x1, y1;        /* origin of the region inside its problem */
+    int64_t cells;         /* band cells, as the host planned them */
+    int64_t ringDoubles;   /* split regions: doubles reserved for the region's own forward ring; otherwise 0 */
+    int32_t lX, lY;
+    int32_t maxWidth;      /* widest diagonal, as the host planned it */
+    int32_t ringCap;       /* cells of the forward ring before it wraps (split regions: never) */
+    int32_t split;         /* the region's tracebacks run as separate items: ringOff counts doubles */
+    int32_t absOk;         /* planning: both band edges move by one x-y step per diagonal */
+    int32_t nSeg;
+    int32_t hasPos;        /* the batch has position words and this region's were written (fixed expansion) */
+    int32_t nStates;
+    int32_t nRegions;      /* regions of the problem */
+} cpecan_table_info;
+int cpecan_batch_table_fetch(const cpecan_batch *b, int64_t problem, int64_t regionInProblem, cpecan_table_info *info,
+                             int32_t *diags, int32_t *dpos, int64_t nDiags, int32_t *segs, int64_t nSegs);
+
 /* ---- single-problem convenience (a batch of one) ---- */
 /* getAlignedPairsUsingAnchors (pairwiseAligner.c:1431): *triples is malloc'd (free with cpecan_free). */
 int cpecan_get_aligned_pairs_using_anchors(const cpecan_model *m, const char *sX, const char *sY,
