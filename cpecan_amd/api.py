@@ -153,6 +153,14 @@ class TableInfo(C.Structure):
     ]
 
 
+class BandEdge(C.Structure):
+    """cpecan_band_edge: posterior mass on the band's edge of one problem (include/cpecan_hip.h)."""
+    _fields_ = [("edgePairs", C.c_int64), ("edgeScoreSum", C.c_int64), ("edgeScoreMax", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {"edgePairs": int(self.edgePairs), "edgeScoreSum": int(self.edgeScoreSum), "edgeScoreMax": int(self.edgeScoreMax)}
+
+
 # Every symbol include/cpecan_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "cpecan_model_default", "cpecan_model_from_hmm", "cpecan_hmm_init", "cpecan_hmm_normalise", "cpecan_hmm_write",
@@ -176,6 +184,7 @@ EXPORTS = [
     "cpecan_batch_reserve_models", "cpecan_batch_set_models", "cpecan_batch_expectations_slot",
     "cpecan_batch_forward_prob_slot",
     "cpecan_batch_table_fetch",
+    "cpecan_batch_set_band_edge", "cpecan_batch_band_edge", "cpecan_band_edge_of_pairs",
 ]
 MAX_MODEL_SLOTS = 8  # CPECAN_MAX_MODEL_SLOTS
 OP_MATCH, OP_INDEL_X, OP_INDEL_Y = 0, 1, 2
@@ -289,6 +298,10 @@ def lib():
     L.cpecan_batch_set_models.argtypes = [vp, C.POINTER(StateMachine), C.c_int]
     L.cpecan_batch_expectations_slot.argtypes = [vp, C.c_int, C.POINTER(Hmm)]
     L.cpecan_batch_forward_prob_slot.argtypes = [vp, C.c_int, C.c_int64, dp]
+    L.cpecan_batch_set_band_edge.argtypes = [vp, C.c_int]
+    L.cpecan_batch_band_edge.argtypes = [vp, C.c_int64, C.POINTER(BandEdge)]
+    L.cpecan_band_edge_of_pairs.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(PairwiseAlignmentParameters), C.c_int,
+                                            C.c_int, i32p, C.c_int64, C.POINTER(BandEdge)]
     _lib = L
     return L
 
@@ -770,6 +783,16 @@ class Batch:
                                               diagonals), "cpecan_batch_debug_fetch")
         return fb, tot
 
+    def set_band_edge(self, on=True):
+        """cpecan_batch_set_band_edge: the next download() also computes the posterior mass on the band's edge."""
+        _check(lib().cpecan_batch_set_band_edge(self._h, int(bool(on))), "cpecan_batch_set_band_edge")
+
+    def band_edge(self, problem):
+        """cpecan_batch_band_edge: {"edgePairs", "edgeScoreSum", "edgeScoreMax"} of a problem of the downloaded run."""
+        e = BandEdge()
+        _check(lib().cpecan_batch_band_edge(self._h, problem, C.byref(e)), "cpecan_batch_band_edge")
+        return e.as_dict()
+
     def table(self, problem, region=0):
         """cpecan_batch_table_fetch: the band table the device built for one region of the uploaded plan (after upload(),
         with or without run(), debug or not).  A dict: the region's facts (x1, y1, lX, lY, cells, maxWidth, ringCap,
@@ -790,6 +813,17 @@ class Batch:
         out = {name: int(getattr(info, name)) for name, _ in TableInfo._fields_ if name != "hasPos"}
         out.update(diags=diags, dpos=dpos if info.hasPos else None, segs=segs[:info.nSeg])
         return out
+
+
+def band_edge_of_pairs(anchorPairs, lX, lY, p, alignedPairs, raggedLeft=False, raggedRight=False):
+    """cpecan_band_edge_of_pairs: the band-edge statistic of a problem's aligned pairs (score, x, y), on the host."""
+    a, ptr, n = _anchor_array(anchorPairs)
+    t = np.ascontiguousarray(np.asarray(alignedPairs, dtype=np.int32).reshape(-1, 3))
+    e = BandEdge()
+    _check(lib().cpecan_band_edge_of_pairs(ptr, n, lX, lY, C.byref(p), int(raggedLeft), int(raggedRight),
+                                           t.ctypes.data_as(C.POINTER(C.c_int32)) if len(t) else None, len(t), C.byref(e)),
+           "cpecan_band_edge_of_pairs")
+    return e.as_dict()
 
 
 def getAlignedPairsUsingAnchors(sM, sX, sY, anchorPairs, p, alignmentHasRaggedLeftEnd=False,

@@ -10,6 +10,11 @@
  * --transitionHspThreshold N asks N of an HSP that only such hits extend to (cpecan_anchor_options); it needs --seedTransitions.
  * --gapped extends the chained HSPs of the anchor finder across indels (cpecan_anchor_options.gappedExtension); --yDrop N
  * sets what ends such an extension and needs --gapped.
+ * --diagonalExpansion N replaces the expansion of pairwiseAlignmentBandingParameters_construct (20) for the anchors and the band.
+ * --adaptiveBand N --minEdgeScore S (each needs the other): the DP batch also computes the posterior mass on the band's edge
+ * (cpecan_band_edge); a pair whose edgeScoreSum reaches S runs again, up to N = 1..4 times, in a batch of the flagged pairs
+ * with the expansion of their runs and of the parameters doubled per round.  Anchors are not searched again.  A pair's cigar
+ * is that of its last run, and stderr names the round and the expansion every pair ended on.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -36,7 +41,10 @@ static void usage(void) {
                     "-t --seedTransitions (anchor seed hits may carry one transition)  -h --help\n"
                     "-T --transitionHspThreshold N (with --seedTransitions: an HSP that no exact seed hit extends to must score N;\n"
                     "   at least the HSP threshold, 800)\n"
-                    "-G --gapped (gapped extension of the chained HSPs)  -Y --yDrop N (with --gapped; default 9400)\n");
+                    "-G --gapped (gapped extension of the chained HSPs)  -Y --yDrop N (with --gapped; default 9400)\n"
+                    "-r --diagonalExpansion N (even; default 20)\n"
+                    "--adaptiveBand N --minEdgeScore S (each needs the other): pairs whose posterior mass on the band's edge sums to S\n"
+                    "   or more (score units, 10000000 = probability 1) run again, up to N = 1..4 times, each with the expansion doubled\n");
 }
 
 static int fail(const char *what) {
@@ -105,12 +113,84 @@ static int by_x(const void *a, const void *b) {
     return p[0] < q[0] ? -1 : p[0] > q[0];
 }
 
+/* One DP batch over the m pairs idx[0 .. m): getAlignedPairs with both ends ragged, reweightAlignedPairs2, the ordered
+ * filter at 0.9 (cPecanAlign.c:125-139).  texts[i] receives pair i's cigar (the text it held is released); edgeSum, when
+ * given, its edgeScoreSum. */
+static int align_pairs(const cpecan_model *model, const cpecan_params *params, double gapGamma, int device,
+                       const cpecan_problem_runs *pr, const int32_t *yMinus, const Records *targets, const Records *queries,
+                       const int64_t *idx, int64_t m, char **texts, int64_t *edgeSum) {
+    int status = 0;
+    cpecan_batch *b = NULL;
+    cpecan_problem_runs *sub = malloc(sizeof *sub * (size_t)m);
+    int32_t *subMinus = malloc(sizeof *subMinus * (size_t)m);
+    if (!sub || !subMinus) status = 1;
+    for (int64_t j = 0; status == 0 && j < m; j++) {
+        sub[j] = pr[idx[j]];
+        subMinus[j] = yMinus[idx[j]];
+    }
+    if (status != 0) status = 1;
+    else if (cpecan_batch_create(&b, model, params, CPECAN_EMIT_MATCH, device) != CPECAN_OK) status = fail("batch");
+    else if (cpecan_batch_set_post(b, CPECAN_POST_REWEIGHT | CPECAN_POST_ORDERED, gapGamma) != CPECAN_OK ||
+             cpecan_batch_set_match_gamma(b, 0.9f) != CPECAN_OK) /* :129-139 */
+        status = fail("consumers");
+    else if (edgeSum && cpecan_batch_set_band_edge(b, 1) != CPECAN_OK) status = fail("band edge");
+    else if (cpecan_batch_add_many_runs_stranded(b, sub, subMinus, m) < 0) status = fail("add");
+    else if (cpecan_batch_upload(b) != CPECAN_OK) status = fail("upload");
+    else if (cpecan_batch_run(b, NULL) != CPECAN_OK) status = fail("run");
+    else if (cpecan_batch_download(b) != CPECAN_OK) status = fail("download");
+    for (int64_t j = 0; status == 0 && j < m; j++) {
+        const int64_t i = idx[j];
+        const int32_t *tr = NULL;
+        int64_t cnt = 0;
+        cpecan_band_edge e;
+        if (cpecan_batch_result(b, j, 3, &tr, &cnt) != CPECAN_OK || (edgeSum && cpecan_batch_band_edge(b, j, &e) != CPECAN_OK)) {
+            status = fail("result");
+            break;
+        }
+        if (edgeSum) edgeSum[i] = e.edgeScoreSum;
+        int64_t *xy = malloc(sizeof *xy * 2 * (size_t)(cnt ? cnt : 1));
+        if (!xy) {
+            status = 1;
+            break;
+        }
+        for (int64_t k = 0; k < cnt; k++) { /* :144-145 */
+            xy[2 * k] = tr[3 * k + 1];
+            xy[2 * k + 1] = tr[3 * k + 2];
+        }
+        qsort(xy, (size_t)cnt, sizeof *xy * 2, by_x);
+        cpecan_cigar c;
+        memset(&c, 0, sizeof c);
+        if (cpecan_cigar_from_aligned_pairs_stranded(targets->r[i % targets->n].name, queries->r[i / targets->n].name, 0.0, pr[i].lX,
+                                                     pr[i].lY, !yMinus[i], xy, cnt, &c) != CPECAN_OK) {
+            status = fail("cigar");
+        } else {
+            const int64_t need = cpecan_cigar_format(&c, NULL, 0) + 1;
+            char *text = malloc((size_t)need);
+            if (text) {
+                cpecan_cigar_format(&c, text, need);
+                free(texts[i]);
+                texts[i] = text;
+            } else {
+                status = 1;
+            }
+            cpecan_cigar_clear(&c);
+        }
+        free(xy);
+    }
+    if (b) cpecan_batch_destroy(b);
+    free(sub);
+    free(subMinus);
+    return status;
+}
+
 int main(int argc, char **argv) {
     const char *hmmFile = NULL;
     long long device = 0;
     int strandMode = CPECAN_STRAND_PLUS, seedTransitions = 0, haveThreshold = 0;
     long long transitionHspThreshold = 0, yDrop = 0;
     int gapped = 0, haveYDrop = 0;
+    long long expansion = -1, adaptiveBand = 0, minEdgeScore = 0;
+    int haveAdaptive = 0, haveMinEdge = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
@@ -119,8 +199,11 @@ int main(int argc, char **argv) {
                                        {"transitionHspThreshold", required_argument, 0, 'T'},
                                        {"gapped", no_argument, 0, 'G'},
                                        {"yDrop", required_argument, 0, 'Y'},
+                                       {"diagonalExpansion", required_argument, 0, 'r'},
+                                       {"adaptiveBand", required_argument, 0, 1000},
+                                       {"minEdgeScore", required_argument, 0, 1001},
                                        {0, 0, 0, 0}};
-    for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:GY:", longOpts, NULL)) != -1;) {
+    for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:GY:r:", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
         case 'y': hmmFile = optarg; break;
@@ -147,6 +230,9 @@ int main(int argc, char **argv) {
             }
             haveYDrop = 1;
             break;
+        case 'r': if (sscanf(optarg, "%lld", &expansion) != 1 || expansion < 0 || expansion % 2 != 0 || expansion > (1 << 20)) { usage(); return 1; } break;
+        case 1000: if (sscanf(optarg, "%lld", &adaptiveBand) != 1 || adaptiveBand < 1 || adaptiveBand > 4) { usage(); return 1; } haveAdaptive = 1; break;
+        case 1001: if (sscanf(optarg, "%lld", &minEdgeScore) != 1 || minEdgeScore < 1) { usage(); return 1; } haveMinEdge = 1; break;
         default: usage(); return 1;
         }
     }
@@ -156,6 +242,10 @@ int main(int argc, char **argv) {
     }
     if (haveYDrop && !gapped) {
         fprintf(stderr, "cpecan_align: --yDrop needs --gapped\n");
+        return 1;
+    }
+    if (haveAdaptive != haveMinEdge) {
+        fprintf(stderr, "cpecan_align: --adaptiveBand and --minEdgeScore need each other\n");
         return 1;
     }
     if (argc - optind != 2) { /* cPecanAlign.c:93-96 */
@@ -171,6 +261,7 @@ int main(int argc, char **argv) {
     }
     cpecan_params params;
     cpecan_params_default(&params); /* :102 */
+    if (expansion >= 0) params.diagonalExpansion = expansion;
     cpecan_anchor_params anchorParams;
     cpecan_anchor_params_default(&anchorParams);
     anchorParams.seedTransitions = seedTransitions;
@@ -197,8 +288,10 @@ int main(int argc, char **argv) {
     int64_t **runs = calloc((size_t)(n ? n : 1), sizeof *runs), *nRuns = calloc((size_t)(n ? n : 1), sizeof *nRuns);
     cpecan_strand_result *strands = calloc((size_t)(n ? n : 1), sizeof *strands);
     int32_t *yMinus = calloc((size_t)(n ? n : 1), sizeof *yMinus);
-    cpecan_batch *b = NULL;
-    if (!ap || !pr || !runs || !nRuns || !strands || !yMinus) status = 1;
+    char **texts = calloc((size_t)(n ? n : 1), sizeof *texts);
+    int64_t *idx = calloc((size_t)(n ? n : 1), sizeof *idx), *edgeSum = calloc((size_t)(n ? n : 1), sizeof *edgeSum);
+    int32_t *rounds = calloc((size_t)(n ? n : 1), sizeof *rounds);
+    if (!ap || !pr || !runs || !nRuns || !strands || !yMinus || !texts || !idx || !edgeSum || !rounds) status = 1;
     for (int64_t q = 0, i = 0; status == 0 && q < queries.n; q++) /* :110-114 */
         for (int64_t t = 0; t < targets.n; t++, i++) {
             ap[i].sX = targets.r[t].seq; /* :123: the target is X */
@@ -222,61 +315,35 @@ int main(int argc, char **argv) {
             pr[i].nRuns = nRuns[i];
             pr[i].raggedLeft = pr[i].raggedRight = 1; /* :125 */
             yMinus[i] = strands[i].strand == CPECAN_STRAND_MINUS;
+            idx[i] = i;
         }
-        if (cpecan_batch_create(&b, &model, &params, CPECAN_EMIT_MATCH, (int)device) != CPECAN_OK) status = fail("batch");
-        else if (cpecan_batch_set_post(b, CPECAN_POST_REWEIGHT | CPECAN_POST_ORDERED, gapGamma) != CPECAN_OK ||
-                 cpecan_batch_set_match_gamma(b, 0.9f) != CPECAN_OK) /* :129-139 */
-            status = fail("consumers");
-        else if (cpecan_batch_add_many_runs_stranded(b, pr, yMinus, n) < 0) status = fail("add");
-        else if (cpecan_batch_upload(b) != CPECAN_OK) status = fail("upload");
-        else if (cpecan_batch_run(b, NULL) != CPECAN_OK) status = fail("run");
-        else if (cpecan_batch_download(b) != CPECAN_OK) status = fail("download");
+        status = align_pairs(&model, &params, gapGamma, (int)device, pr, yMinus, &targets, &queries, idx, n, texts,
+                             haveAdaptive ? edgeSum : NULL);
     }
-    char *text = NULL;
-    int64_t textCap = 0;
+    for (long long k = 1; status == 0 && k <= adaptiveBand; k++) { /* the pairs flagged in round k - 1, the expansion doubled */
+        int64_t m = 0;
+        for (int64_t i = 0; i < n; i++)
+            if (rounds[i] == k - 1 && edgeSum[i] >= minEdgeScore) idx[m++] = i;
+        if (m == 0) break;
+        cpecan_params wider = params;
+        wider.diagonalExpansion = params.diagonalExpansion << k;
+        for (int64_t j = 0; j < m; j++) {
+            for (int64_t q = 0; q < nRuns[idx[j]]; q++) runs[idx[j]][4 * q + 3] *= 2;
+            rounds[idx[j]] = (int32_t)k;
+        }
+        status = align_pairs(&model, &wider, gapGamma, (int)device, pr, yMinus, &targets, &queries, idx, m, texts, edgeSum);
+    }
     for (int64_t i = 0; status == 0 && i < n; i++) {
-        const int32_t *tr = NULL;
-        int64_t cnt = 0;
-        if (cpecan_batch_result(b, i, 3, &tr, &cnt) != CPECAN_OK) {
-            status = fail("result");
-            break;
-        }
-        int64_t *xy = malloc(sizeof *xy * 2 * (size_t)(cnt ? cnt : 1));
-        if (!xy) {
-            status = 1;
-            break;
-        }
-        for (int64_t k = 0; k < cnt; k++) { /* :144-145 */
-            xy[2 * k] = tr[3 * k + 1];
-            xy[2 * k + 1] = tr[3 * k + 2];
-        }
-        qsort(xy, (size_t)cnt, sizeof *xy * 2, by_x);
-        cpecan_cigar c;
-        memset(&c, 0, sizeof c);
-        if (cpecan_cigar_from_aligned_pairs_stranded(targets.r[i % targets.n].name, queries.r[i / targets.n].name, 0.0, ap[i].lX,
-                                                     ap[i].lY, !yMinus[i], xy, cnt, &c) != CPECAN_OK) {
-            status = fail("cigar");
-        } else {
-            const int64_t need = cpecan_cigar_format(&c, NULL, 0) + 1;
-            if (need > textCap) {
-                char *g = realloc(text, (size_t)(2 * need));
-                if (g) {
-                    text = g;
-                    textCap = 2 * need;
-                } else {
-                    status = 1;
-                }
-            }
-            if (status == 0) {
-                cpecan_cigar_format(&c, text, textCap);
-                puts(text); /* :149 */
-            }
-            cpecan_cigar_clear(&c);
-        }
-        free(xy);
+        puts(texts[i]); /* :149 */
+        if (haveAdaptive)
+            fprintf(stderr, "cpecan_align: %s %s: round %d, expansion %lld\n", targets.r[i % targets.n].name,
+                    queries.r[i / targets.n].name, (int)rounds[i], (long long)(params.diagonalExpansion << rounds[i]));
     }
-    free(text);
-    if (b) cpecan_batch_destroy(b);
+    for (int64_t i = 0; texts && i < n; i++) free(texts[i]);
+    free(texts);
+    free(idx);
+    free(edgeSum);
+    free(rounds);
     for (int64_t i = 0; runs && i < n; i++) cpecan_free(runs[i]);
     free(runs);
     free(nRuns);

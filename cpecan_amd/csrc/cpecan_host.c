@@ -449,6 +449,8 @@ struct cpecan_batch {
     double postGapGamma;
     float postMatchGamma; /* ORDERED: matchGamma of cPecanRealign.c:355 */
     int32_t *postMea, *postShift;
+    int bandEdge;            /* cpecan_batch_set_band_edge: downloads also compute the statistic */
+    cpecan_band_edge *edges; /* [nProblems] of the downloaded run, or NULL: it was not asked for */
     cpecan_stats stats;
     /* cpecan_batch_download_begin / _end */
     pthread_t dlThread;
@@ -669,7 +671,9 @@ static void free_results(cpecan_batch *b) {
     cpk_host_free(b->results);
     cpk_host_free(b->postMea);
     cpk_host_free(b->postShift);
+    free(b->edges);
     b->results = b->postMea = b->postShift = NULL;
+    b->edges = NULL;
 }
 
 void cpecan_batch_destroy(cpecan_batch *b) {
@@ -1797,17 +1801,27 @@ int cpecan_batch_set_model(cpecan_batch *b, const cpecan_model *m) {
  * segments in DEScending order (each traceback's pairs are prepended, pairwiseAligner.c:1415-1417), every triple shifted
  * by its region's offset (:1411-1418).  Sets the per-problem result pointers into b->results. */
 static int plan_results(cpecan_batch *b, const int32_t *counts, const int32_t *segStarts, const int32_t *segCounts,
-                        CpkChunk **chunksOut, int64_t *nChunksOut, int64_t *totalOut) {
+                        CpkChunk **chunksOut, int64_t *nChunksOut, int64_t *totalOut, int32_t **chunkRegionOut,
+                        int32_t **chunkProblemOut, int64_t *nChunks0Out) {
     int64_t total = 0;
     for (int l = 0; l < b->nLists; l++)
         for (int64_t di = 0; di < b->nRegions; di++) total += counts[(size_t)l * b->nRegions + di];
     CpkChunk *chunks = cpk_host_alloc(sizeof(CpkChunk) * (size_t)(b->nLists * (b->nSegs ? b->nSegs : 1)));
     b->results = cpk_host_alloc(sizeof(int32_t) * 3 * (size_t)(total ? total : 1));
-    if (!chunks || !b->results) {
+    /* the band-edge statistic (cpk_device_band_edge): device region and problem of every list-0 chunk, beside the list */
+    int32_t *chunkRegion = NULL, *chunkProblem = NULL;
+    if (b->bandEdge) {
+        chunkRegion = malloc(sizeof(int32_t) * (size_t)(b->nSegs ? b->nSegs : 1));
+        chunkProblem = malloc(sizeof(int32_t) * (size_t)(b->nSegs ? b->nSegs : 1));
+    }
+    if (!chunks || !b->results || (b->bandEdge && (!chunkRegion || !chunkProblem))) {
         cpk_host_free(chunks);
+        free(chunkRegion);
+        free(chunkProblem);
         return CPECAN_ENOMEM;
     }
     int64_t nChunks = 0, at = 0;
+    *nChunks0Out = 0;
     for (int l = 0; l < b->nLists; l++) {
         const int32_t *cnt = counts + (size_t)l * b->nRegions;
         const int32_t *ss = segStarts + (size_t)l * b->nSegs;
@@ -1825,6 +1839,10 @@ static int plan_results(cpecan_batch *b, const int32_t *counts, const int32_t *s
                     /* a split region's segments were written apart, each with its own count */
                     const int32_t to = g->split ? from + sc[g->segOff + sgi] : (sgi + 1 < g->nSeg ? ss[g->segOff + sgi + 1] : n);
                     if (to <= from) continue;
+                    if (l == 0 && chunkRegion) {
+                        chunkRegion[nChunks] = (int32_t)r->devIndex;
+                        chunkProblem[nChunks] = (int32_t)pi;
+                    }
                     CpkChunk *c = &chunks[nChunks++];
                     c->src = (int64_t)l * b->outTriples + g->outOff + from;
                     c->dst = at;
@@ -1837,7 +1855,10 @@ static int plan_results(cpecan_batch *b, const int32_t *counts, const int32_t *s
             }
             pr->nTriples[l] = at - first;
         }
+        if (l == 0) *nChunks0Out = nChunks;
     }
+    *chunkRegionOut = chunkRegion;
+    *chunkProblemOut = chunkProblem;
     *chunksOut = chunks;
     *nChunksOut = nChunks;
     *totalOut = at;
@@ -1940,6 +1961,111 @@ int cpecan_batch_set_post(cpecan_batch *b, int flags, double gapGamma) {
     return CPECAN_OK;
 }
 
+int cpecan_batch_set_band_edge(cpecan_batch *b, int on) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b) return CPECAN_EINVAL;
+    if (b->emit == CPECAN_EMIT_FORWARD || b->emit == CPECAN_EMIT_EXPECT) {
+        cpk_set_error("the band edge statistic is a function of the pair lists: EXPECT and FORWARD batches have none");
+        return CPECAN_EINVAL;
+    }
+    b->bandEdge = on != 0;
+    return CPECAN_OK;
+}
+
+int cpecan_batch_band_edge(const cpecan_batch *b, int64_t problem, cpecan_band_edge *out) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !b->downloaded) return CPECAN_ESTATE;
+    if (!b->edges) {
+        cpk_set_error("the band edge statistic was not asked for: cpecan_batch_set_band_edge before the download");
+        return CPECAN_ESTATE;
+    }
+    if (problem < 0 || problem >= b->nProblems || !out) return CPECAN_EINVAL;
+    *out = b->edges[problem];
+    return CPECAN_OK;
+}
+
+/* The definition of cpecan_band_edge on the host: regions as cpecan_batch_add cuts them, each region's band, every pair
+ * against its own anti-diagonal. */
+int cpecan_band_edge_of_pairs(const int64_t *anchors, int64_t nAnchors, int64_t lX, int64_t lY, const cpecan_params *p,
+                              int raggedLeft, int raggedRight, const int32_t *triples, int64_t n, cpecan_band_edge *out) {
+    if (!p || !out || lX < 0 || lY < 0 || nAnchors < 0 || n < 0 || (nAnchors > 0 && !anchors) || (n > 0 && !triples))
+        return CPECAN_EINVAL;
+    memset(out, 0, sizeof *out);
+    int64_t *rects = malloc(sizeof(int64_t) * 4 * (size_t)(nAnchors + 2));
+    if (!rects) return CPECAN_ENOMEM;
+    const int64_t nRects = cpecan_split_points(anchors, nAnchors, lX, lY, p->splitMatrixBiggerThanThis, raggedLeft, raggedRight, rects);
+    int rc = nRects < 0 ? (int)nRects : CPECAN_OK;
+    int64_t *own = NULL, *band = NULL, *regionOf = NULL, *first = NULL, *order = NULL;
+    if (rc == CPECAN_OK) {
+        own = malloc(sizeof(int64_t) * 3 * (size_t)(nAnchors ? nAnchors : 1));
+        regionOf = malloc(sizeof(int64_t) * (size_t)(n ? n : 1));
+        order = malloc(sizeof(int64_t) * (size_t)(n ? n : 1));
+        first = calloc((size_t)nRects + 2, sizeof(int64_t));
+        if (!own || !regionOf || !order || !first) rc = CPECAN_ENOMEM;
+    }
+    /* the rectangles are disjoint and ascend in x and in y: a pair's region is the last one that starts at or left of it */
+    for (int64_t i = 0; rc == CPECAN_OK && i < n; i++) {
+        const int64_t x = triples[3 * i + 1], y = triples[3 * i + 2];
+        int64_t lo = 0, hi = nRects - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            if (rects[4 * mid] <= x) lo = mid;
+            else hi = mid - 1;
+        }
+        if (nRects == 0 || x < rects[4 * lo] || x >= rects[4 * lo + 2] || y < rects[4 * lo + 1] || y >= rects[4 * lo + 3]) {
+            cpk_set_error("cpecan_band_edge_of_pairs: pair %lld (%lld, %lld) lies in no region of the problem", (long long)i,
+                          (long long)x, (long long)y);
+            rc = CPECAN_EINVAL;
+            break;
+        }
+        regionOf[i] = lo;
+        first[lo + 2]++;
+    }
+    if (rc == CPECAN_OK) { /* the pairs by region: first[k + 1] .. of region k after the scatter */
+        for (int64_t k = 0; k < nRects; k++) first[k + 2] += first[k + 1];
+        for (int64_t i = 0; i < n; i++) order[first[regionOf[i] + 1]++] = i;
+    }
+    int64_t next = 0;
+    for (int64_t k = 0; rc == CPECAN_OK && k < nRects; k++) {
+        const int64_t x1 = rects[4 * k], y1 = rects[4 * k + 1], x2 = rects[4 * k + 2], y2 = rects[4 * k + 3];
+        const int64_t rX = x2 - x1, rY = y2 - y1;
+        int64_t nOwn = 0; /* anchors go to regions in order (pairwiseAligner.c:1296-1308) */
+        for (; next < nAnchors && anchors[3 * next] + anchors[3 * next + 1] < x2 + y2; next++, nOwn++) {
+            own[3 * nOwn] = anchors[3 * next] - x1;
+            own[3 * nOwn + 1] = anchors[3 * next + 1] - y1;
+            own[3 * nOwn + 2] = anchors[3 * next + 2];
+        }
+        if (first[k] == first[k + 1]) continue; /* no pair in this region */
+        int64_t *grown = realloc(band, sizeof(int64_t) * 3 * (size_t)(rX + rY + 1));
+        if (!grown) {
+            rc = CPECAN_ENOMEM;
+            break;
+        }
+        band = grown;
+        rc = cpecan_band(own, nOwn, rX, rY, p->diagonalExpansion, p->dynamicAnchorExpansion != 0, band);
+        for (int64_t q = first[k]; rc == CPECAN_OK && q < first[k + 1]; q++) {
+            const int64_t i = order[q];
+            const int64_t xs = (int64_t)triples[3 * i + 1] - x1, ys = (int64_t)triples[3 * i + 2] - y1;
+            const int64_t d = xs + ys + 2, xmy = xs - ys; /* cell (xs + 1, ys + 1) */
+            const int left = xmy == band[3 * d + 1] && ys + 2 <= rY;  /* (x - 1, y + 1) is in the matrix; x - 1 >= 0 always */
+            const int right = xmy == band[3 * d + 2] && xs + 2 <= rX; /* (x + 1, y - 1) */
+            if (left || right) {
+                out->edgePairs++;
+                out->edgeScoreSum += triples[3 * i];
+                if (triples[3 * i] > out->edgeScoreMax) out->edgeScoreMax = triples[3 * i];
+            }
+        }
+    }
+    if (rc != CPECAN_OK) memset(out, 0, sizeof *out);
+    free(rects);
+    free(own);
+    free(band);
+    free(regionOf);
+    free(first);
+    free(order);
+    return rc;
+}
+
 int cpecan_batch_set_match_gamma(cpecan_batch *b, float matchGamma) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || !(matchGamma >= 0.0f)) return CPECAN_EINVAL;
@@ -1979,6 +2105,8 @@ int cpecan_batch_download(cpecan_batch *b) {
     free_results(b);
     b->stats.pairs = 0;
     if (b->nRegions == 0) {
+        if (b->bandEdge) b->edges = calloc((size_t)(b->nProblems ? b->nProblems : 1), sizeof(cpecan_band_edge));
+        if (b->bandEdge && !b->edges) return CPECAN_ENOMEM;
         b->downloaded = 1;
         return CPECAN_OK;
     }
@@ -2065,10 +2193,18 @@ int cpecan_batch_download(cpecan_batch *b) {
         CpkChunk *chunks = NULL;
         int64_t nChunks = 0, total = 0;
         const double tD2 = now_ms();
-        rc = plan_results(b, counts, segStarts, segCounts, &chunks, &nChunks, &total);
+        int32_t *chunkRegion = NULL, *chunkProblem = NULL;
+        int64_t nChunks0 = 0;
+        rc = plan_results(b, counts, segStarts, segCounts, &chunks, &nChunks, &total, &chunkRegion, &chunkProblem, &nChunks0);
         const double tD3 = now_ms();
         if (rc == CPECAN_OK) rc = cpk_device_gather(b->dev, chunks, nChunks, total);
         cpk_host_free(chunks);
+        if (rc == CPECAN_OK && b->bandEdge) { /* on the sweep's own scores: in front of the consumers (REWEIGHT rewrites them) */
+            b->edges = malloc(sizeof(cpecan_band_edge) * (size_t)(b->nProblems ? b->nProblems : 1));
+            rc = b->edges ? cpk_device_band_edge(b->dev, nChunks0, chunkRegion, chunkProblem, b->nProblems, b->edges) : CPECAN_ENOMEM;
+        }
+        free(chunkRegion);
+        free(chunkProblem);
         const double tD4 = now_ms();
         if (rc == CPECAN_OK) rc = run_post(b); /* consumers of the lists, on the device, before they leave it */
         const double tD5 = now_ms();

@@ -186,6 +186,11 @@ int cpk_device_download(CpkDevice *dev, int32_t *counts /* [nLists][nRegions] */
                         double *expect /* [106] */, double *kernelMs, double *d2hMs);
 /* Moves the chunks into one compact buffer on the device (reference list order, region offsets applied). */
 int cpk_device_gather(CpkDevice *dev, const CpkChunk *chunks, int64_t nChunks, int64_t total);
+/* Posterior mass on the band's edge (cpecan_band_edge, cpecan_hip.h), behind cpk_device_gather and in front of
+ * cpk_device_post: the first nChunks0 chunks of the gather -- those of list 0 -- each with its device region and its
+ * problem; out receives nProblems records.  Counters and the two index arrays live for the duration of the call. */
+int cpk_device_band_edge(CpkDevice *dev, int64_t nChunks0, const int32_t *chunkRegion, const int32_t *chunkProblem,
+                         int64_t nProblems, cpecan_band_edge *out);
 /* Copies the compact buffer -- `total` triples, nothing else -- to hostOut. */
 int cpk_device_fetch(CpkDevice *dev, int32_t *hostOut, int64_t total, double *d2hMs);
 

@@ -1584,6 +1584,33 @@ extern "C" int cpk_device_post(CpkDevice *d, const CpkPostJob *job) {
     return post_core(sc, d->dCompact, job);
 }
 
+extern "C" int cpk_device_band_edge(CpkDevice *d, int64_t nChunks0, const int32_t *chunkRegion, const int32_t *chunkProblem,
+                                    int64_t nProblems, cpecan_band_edge *out) {
+    CPK_ON_DEVICE(d->device);
+    memset(out, 0, sizeof(cpecan_band_edge) * (size_t)nProblems);
+    if (nChunks0 <= 0 || nProblems <= 0) return CPECAN_OK;  // no pair was emitted
+    if (nChunks0 > d->chunkCap || !d->dChunks || !d->dCompact || !d->dDiags) {
+        cpk_set_error("band edge statistic without a gathered list");
+        return CPECAN_ESTATE;
+    }
+    PostScratch sc(d->io);
+    int32_t *dRegion = nullptr, *dProblem = nullptr;
+    cpecan_band_edge *dOut = nullptr;
+    if (int rc = sc.alloc(&dRegion, (size_t)nChunks0)) return rc;
+    if (int rc = sc.alloc(&dProblem, (size_t)nChunks0)) return rc;
+    if (int rc = sc.alloc(&dOut, (size_t)nProblems)) return rc;
+    HIP_TRY(hipMemcpyAsync(dRegion, chunkRegion, sizeof(int32_t) * (size_t)nChunks0, hipMemcpyHostToDevice, d->io));
+    HIP_TRY(hipMemcpyAsync(dProblem, chunkProblem, sizeof(int32_t) * (size_t)nChunks0, hipMemcpyHostToDevice, d->io));
+    HIP_TRY(hipMemsetAsync(dOut, 0, sizeof(cpecan_band_edge) * (size_t)nProblems, d->io));
+    const int64_t blocks = nChunks0 < 65536 ? nChunks0 : 65536;
+    hipLaunchKernelGGL(cpecan_post_band_edge, dim3((unsigned)blocks), dim3(CPK_WAVE), 0, d->io, d->dChunks, dRegion, dProblem,
+                       nChunks0, d->dRegions, d->dDiags, d->dCompact, dOut);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dOut, sizeof(cpecan_band_edge) * (size_t)nProblems, hipMemcpyDeviceToHost, d->io));
+    HIP_TRY(hipStreamSynchronize(d->io));
+    return CPECAN_OK;
+}
+
 extern "C" int cpk_post_lists(int device, int32_t *triples, int64_t total, const CpkPostJob *job) {
     const int nDev = cpk_device_count();
     if (nDev <= 0 || device < 0 || device >= nDev) {

@@ -402,6 +402,12 @@ struct cpecan_realigner {
     SeqEntry *seqs; /* open addressing, capacity a power of two */
     int64_t nSeqs, capSeqs;
     char *finalPairsPath, *allPairsPath;
+    /* cpecan_realigner_set_adaptive_band: rounds of re-runs at a doubled expansion (0: off) for the cigars whose
+     * edgeScoreSum reaches minEdgeScore; lastRounds: the round every cigar of the last realign call ended on */
+    int adaptiveRounds;
+    int64_t minEdgeScore;
+    int32_t *lastRounds;
+    int64_t nLastRounds;
 };
 
 void cpecan_realign_options_default(cpecan_realign_options *o) {
@@ -442,6 +448,7 @@ void cpecan_realigner_destroy(cpecan_realigner *r) {
     free(r->seqs);
     free(r->finalPairsPath);
     free(r->allPairsPath);
+    free(r->lastRounds);
     free(r);
 }
 
@@ -867,16 +874,15 @@ static int build_output(const cpecan_realigner *r, const cpecan_batch *b, const 
     return rc;
 }
 
-static int realign_on_device(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_cigar **out, int64_t *nOut) {
-    *out = NULL;
-    *nOut = 0;
+/* One batch: the realign loop (cPecanRealign.c:509-600) over n cigars under r's options.  slots[i] receives the pieces of
+ * cigar i; edgeSum (or NULL: the batch is not asked for the statistic) the edgeScoreSum of its problem; files: the
+ * posterior files of the realigner are the last cigar's of this batch. */
+static int realign_batch(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, OutSlot *slots, int64_t *edgeSum,
+                         int files) {
     const cpecan_realign_options *o = &r->opt;
     Item *items = calloc((size_t)(n ? n : 1), sizeof(Item));
-    OutSlot *slots = calloc((size_t)(n ? n : 1), sizeof(OutSlot));
-    cpecan_cigar *res = NULL;
-    int64_t nRes = 0;
     cpecan_batch *b = NULL;
-    int rc = items && slots ? CPECAN_OK : CPECAN_ENOMEM;
+    int rc = items ? CPECAN_OK : CPECAN_ENOMEM;
     const int timing = getenv("CPECAN_REALIGN_TIMING") != NULL; /* stage times of this call on stderr */
     const double t0 = now_ms();
     if (rc == CPECAN_OK) rc = cpecan_batch_create(&b, &r->model, &o->params, CPECAN_EMIT_MATCH, r->device);
@@ -884,10 +890,16 @@ static int realign_on_device(const cpecan_realigner *r, const cpecan_cigar *in, 
         rc = cpecan_batch_set_post(b, CPECAN_POST_REWEIGHT | CPECAN_POST_ORDERED, (double)o->gapGamma);
         if (rc == CPECAN_OK) rc = cpecan_batch_set_match_gamma(b, o->matchGamma);
     }
+    if (rc == CPECAN_OK && edgeSum) rc = cpecan_batch_set_band_edge(b, 1);
     if (rc == CPECAN_OK) rc = prepare_and_add(r, in, n, items, b);
     const double t1 = now_ms();
     if (rc == CPECAN_OK && n > 0) rc = run_batch(b);
     const double t2 = now_ms();
+    for (int64_t i = 0; rc == CPECAN_OK && edgeSum && i < n; i++) {
+        cpecan_band_edge e;
+        rc = cpecan_batch_band_edge(b, i, &e);
+        edgeSum[i] = e.edgeScoreSum;
+    }
     if (rc == CPECAN_OK) {
         int64_t firstBad = n;
 #pragma omp parallel for schedule(dynamic, 64) num_threads(cpk_host_threads())
@@ -903,18 +915,7 @@ static int realign_on_device(const cpecan_realigner *r, const cpecan_cigar *in, 
             if (rc == CPECAN_OK) rc = CPECAN_ESTATE;
         }
     }
-    if (rc == CPECAN_OK) {
-        for (int64_t i = 0; i < n; i++) nRes += slots[i].n;
-        res = malloc(sizeof(cpecan_cigar) * (size_t)(nRes ? nRes : 1));
-        if (!res) rc = CPECAN_ENOMEM;
-        for (int64_t i = 0, at = 0; rc == CPECAN_OK && i < n; i++) { /* ownership of the pieces moves to res */
-            if (slots[i].n) memcpy(res + at, slots[i].pieces, sizeof(cpecan_cigar) * (size_t)slots[i].n);
-            at += slots[i].n;
-            free(slots[i].pieces);
-            memset(&slots[i], 0, sizeof(OutSlot));
-        }
-    }
-    if (rc == CPECAN_OK && n > 0 && r->finalPairsPath) { /* the last cigar's final pairs (:566-570) */
+    if (rc == CPECAN_OK && n > 0 && files && r->finalPairsPath) { /* the last cigar's final pairs (:566-570) */
         const int32_t *list = NULL;
         int32_t *owned = NULL;
         int64_t nList = 0;
@@ -923,7 +924,7 @@ static int realign_on_device(const cpecan_realigner *r, const cpecan_cigar *in, 
         if (rc == CPECAN_OK) rc = write_pairs(r->finalPairsPath, list, nList, &items[n - 1]);
         free(owned);
     }
-    if (rc == CPECAN_OK && n > 0 && r->allPairsPath) { /* every pair of the last alignment, before reweighting (:541-545) */
+    if (rc == CPECAN_OK && n > 0 && files && r->allPairsPath) { /* every pair of the last alignment, before reweighting (:541-545) */
         cpecan_batch *raw = NULL;
         Item *it = &items[n - 1];
         item_clear(it);
@@ -953,10 +954,79 @@ static int realign_on_device(const cpecan_realigner *r, const cpecan_cigar *in, 
     cpecan_batch_destroy(b);
     for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
     free(items);
+    return rc;
+}
+
+/* Round k = 1 .. adaptiveRounds of cpecan_realigner_set_adaptive_band: the cigars whose last run left edgeScoreSum >=
+ * minEdgeScore run again, as a batch of their own, under the realigner's options with diagonalExpansion * 2^k -- the run
+ * expansions and the parameter -- and take that run's output.  rounds[i]: the round cigar i ended on. */
+static int adaptive_rounds(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, OutSlot *slots, int64_t *edgeSum,
+                           int32_t *rounds) {
+    int64_t *idx = malloc(sizeof(int64_t) * (size_t)(n ? n : 1));
+    int rc = idx ? CPECAN_OK : CPECAN_ENOMEM;
+    for (int k = 1; rc == CPECAN_OK && k <= r->adaptiveRounds; k++) {
+        int64_t m = 0;
+        for (int64_t i = 0; i < n; i++)
+            if (rounds[i] == k - 1 && edgeSum[i] >= r->minEdgeScore) idx[m++] = i;
+        if (m == 0) break;
+        cpecan_cigar *sub = malloc(sizeof(cpecan_cigar) * (size_t)m); /* shallow: the texts and operations stay the caller's */
+        OutSlot *subSlots = calloc((size_t)m, sizeof(OutSlot));
+        int64_t *subEdge = calloc((size_t)m, sizeof(int64_t));
+        rc = sub && subSlots && subEdge ? CPECAN_OK : CPECAN_ENOMEM;
+        if (rc == CPECAN_OK) {
+            for (int64_t j = 0; j < m; j++) sub[j] = in[idx[j]];
+            cpecan_realigner wider = *r;
+            wider.opt.params.diagonalExpansion = r->opt.params.diagonalExpansion << k;
+            rc = realign_batch(&wider, sub, m, subSlots, subEdge, idx[m - 1] == n - 1);
+        }
+        for (int64_t j = 0; j < m; j++) {
+            if (rc == CPECAN_OK) { /* the cigar's output is that of its last run */
+                cpecan_cigars_free(slots[idx[j]].pieces, slots[idx[j]].n);
+                slots[idx[j]] = subSlots[j];
+                edgeSum[idx[j]] = subEdge[j];
+                rounds[idx[j]] = k;
+            } else if (subSlots) {
+                cpecan_cigars_free(subSlots[j].pieces, subSlots[j].n);
+            }
+        }
+        free(sub);
+        free(subSlots);
+        free(subEdge);
+    }
+    free(idx);
+    return rc;
+}
+
+/* rounds: n entries that receive the round every cigar ended on (0 without the adaptive band), or NULL */
+static int realign_on_device(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_cigar **out, int64_t *nOut,
+                             int32_t *rounds) {
+    *out = NULL;
+    *nOut = 0;
+    const int adaptive = r->adaptiveRounds > 0 && rounds;
+    OutSlot *slots = calloc((size_t)(n ? n : 1), sizeof(OutSlot));
+    int64_t *edgeSum = adaptive ? calloc((size_t)(n ? n : 1), sizeof(int64_t)) : NULL;
+    cpecan_cigar *res = NULL;
+    int64_t nRes = 0;
+    int rc = slots && (!adaptive || edgeSum) ? CPECAN_OK : CPECAN_ENOMEM;
+    for (int64_t i = 0; rounds && i < n; i++) rounds[i] = 0;
+    if (rc == CPECAN_OK) rc = realign_batch(r, in, n, slots, edgeSum, 1);
+    if (rc == CPECAN_OK && adaptive) rc = adaptive_rounds(r, in, n, slots, edgeSum, rounds);
+    if (rc == CPECAN_OK) {
+        for (int64_t i = 0; i < n; i++) nRes += slots[i].n;
+        res = malloc(sizeof(cpecan_cigar) * (size_t)(nRes ? nRes : 1));
+        if (!res) rc = CPECAN_ENOMEM;
+        for (int64_t i = 0, at = 0; rc == CPECAN_OK && i < n; i++) { /* ownership of the pieces moves to res */
+            if (slots[i].n) memcpy(res + at, slots[i].pieces, sizeof(cpecan_cigar) * (size_t)slots[i].n);
+            at += slots[i].n;
+            free(slots[i].pieces);
+            memset(&slots[i], 0, sizeof(OutSlot));
+        }
+    }
     for (int64_t i = 0; slots && i < n; i++) cpecan_cigars_free(slots[i].pieces, slots[i].n);
     free(slots);
+    free(edgeSum);
     if (rc != CPECAN_OK) {
-        cpecan_cigars_free(res, nRes);
+        free(res); /* (no piece has moved into it) */
         return rc;
     }
     *out = res;
@@ -1014,6 +1084,35 @@ int cpecan_realign_shard_bounds(const cpecan_cigar *in, int64_t n, int64_t diago
     return CPECAN_OK;
 }
 
+int cpecan_realigner_set_adaptive_band(cpecan_realigner *r, int maxRounds, int64_t minEdgeScore) {
+    if (!r || maxRounds < 0 || maxRounds > 4) return CPECAN_EINVAL;
+    if (maxRounds > 0 && minEdgeScore < 1) {
+        cpk_set_error("the adaptive band needs minEdgeScore >= 1: it has no default");
+        return CPECAN_EINVAL;
+    }
+    if (maxRounds > 0 && r->opt.rescoreOriginalAlignment) {
+        cpk_set_error("rescoreOriginalAlignment returns the input alignment: a wider band cannot change it");
+        return CPECAN_EINVAL;
+    }
+    r->adaptiveRounds = maxRounds;
+    r->minEdgeScore = maxRounds > 0 ? minEdgeScore : 0;
+    return CPECAN_OK;
+}
+
+int cpecan_realigner_adaptive_rounds(const cpecan_realigner *r, int32_t *rounds, int64_t n) {
+    if (!r || (!rounds && n > 0)) return CPECAN_EINVAL;
+    if (!r->lastRounds) {
+        cpk_set_error("no realign call yet");
+        return CPECAN_ESTATE;
+    }
+    if (n != r->nLastRounds) {
+        cpk_set_error("the last realign call had %lld cigars, not %lld", (long long)r->nLastRounds, (long long)n);
+        return CPECAN_EINVAL;
+    }
+    for (int64_t i = 0; i < n; i++) rounds[i] = r->lastRounds[i];
+    return CPECAN_OK;
+}
+
 int cpecan_realigner_set_devices(cpecan_realigner *r, const int *devices, int nDevices) {
     if (!r || nDevices < 0 || nDevices > CPK_REALIGN_MAX_DEVICES || (nDevices > 0 && !devices)) return CPECAN_EINVAL;
     for (int k = 0; k < nDevices; k++)
@@ -1030,6 +1129,7 @@ typedef struct {
     int64_t n;
     int expect;
     int threads;
+    int32_t *rounds; /* the shard's part of the realigner's lastRounds */
     cpecan_cigar *out;
     int64_t nOut;
     cpecan_hmm acc;
@@ -1041,7 +1141,7 @@ static void *shard_main(void *arg) {
     ShardJob *j = arg;
     omp_set_num_threads(j->threads); /* this thread's parallel loops: its share of the host's cores */
     j->rc = j->expect ? expectations_on_device(&j->shard, j->in, j->n, &j->acc)
-                      : realign_on_device(&j->shard, j->in, j->n, &j->out, &j->nOut);
+                      : realign_on_device(&j->shard, j->in, j->n, &j->out, &j->nOut, j->rounds);
     if (j->rc != CPECAN_OK) {
         strncpy(j->err, cpk_last_error(), sizeof j->err - 1);
         j->err[sizeof j->err - 1] = 0;
@@ -1069,6 +1169,7 @@ static int run_shards(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, in
             j->shard.finalPairsPath = j->shard.allPairsPath = NULL;
         j->in = in + bounds[k];
         j->n = bounds[k + 1] - bounds[k];
+        j->rounds = !expect && r->lastRounds ? r->lastRounds + bounds[k] : NULL; /* every shard adapts on its own */
         j->expect = expect;
         j->threads = threads;
         if (expect && (rc = cpecan_hmm_init(&j->acc, hmmType, 0.0)) != CPECAN_OK) break;
@@ -1096,7 +1197,12 @@ static int run_shards(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, in
 
 int cpecan_realigner_realign(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_cigar **out, int64_t *nOut) {
     if (!r || (!in && n > 0) || n < 0 || !out || !nOut) return CPECAN_EINVAL;
-    if (r->nDevices <= 1 || n < 2) return realign_on_device(r, in, n, out, nOut);
+    free(r->lastRounds);
+    r->nLastRounds = 0;
+    r->lastRounds = calloc((size_t)(n ? n : 1), sizeof(int32_t));
+    if (!r->lastRounds) return CPECAN_ENOMEM;
+    r->nLastRounds = n;
+    if (r->nDevices <= 1 || n < 2) return realign_on_device(r, in, n, out, nOut, r->lastRounds);
     *out = NULL;
     *nOut = 0;
     ShardJob *jobs = malloc(sizeof(ShardJob) * (size_t)r->nDevices);

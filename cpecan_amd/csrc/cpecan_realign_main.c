@@ -23,6 +23,8 @@ static void usage(void) {
             "a batch also closes at 64 Mbp of aligned sequence)\n"
             "-g --device N  -G --devices LIST (e.g. 0-7 or 0,2,3: the cigars of every batch are cut into one shard per\n"
             "listed device, run side by side from this process and joined in input order; a device may be listed twice)\n"
+            "--adaptiveBand N --minEdgeScore S (each needs the other): cigars whose posterior mass on the band's edge sums to S\n"
+            "or more (score units, 10000000 = probability 1) run again, up to N = 1..4 times, each with the expansion doubled\n"
             "-h --help\n");
 }
 
@@ -60,7 +62,8 @@ int main(int argc, char **argv) {
     cpecan_realign_options o;
     cpecan_realign_options_default(&o);
     const char *posteriorFile = NULL, *allPosteriorFile = NULL, *expectationsFile = NULL, *hmmFile = NULL;
-    long long batch = 32768, device = 0, v;
+    long long batch = 32768, device = 0, v, adaptiveBand = 0, minEdgeScore = 0;
+    int haveAdaptive = 0, haveMinEdge = 0;
     int devices[64], nDevices = 0;
     const long long batchBases = 64ll << 20; /* a batch also closes here: ~1.5 GB of anchors on the host */
     static struct option longOpts[] = {{"logLevel", required_argument, 0, 'a'},
@@ -84,6 +87,8 @@ int main(int argc, char **argv) {
                                        {"batch", required_argument, 0, 'b'},
                                        {"device", required_argument, 0, 'g'},
                                        {"devices", required_argument, 0, 'G'},
+                                       {"adaptiveBand", required_argument, 0, 1000},
+                                       {"minEdgeScore", required_argument, 0, 1001},
                                        {0, 0, 0, 0}};
     for (int key; (key = getopt_long(argc, argv, "a:hl:o:r:t:s:wxijkmu:v:y:z:L:b:g:G:", longOpts, NULL)) != -1;) {
         switch (key) {
@@ -108,8 +113,14 @@ int main(int argc, char **argv) {
         case 'b': if (sscanf(optarg, "%lld", &batch) != 1 || batch < 1) return 1; break;
         case 'g': if (sscanf(optarg, "%lld", &device) != 1) return 1; break;
         case 'G': if ((nDevices = parse_devices(optarg, devices, 64)) < 1) { usage(); return 1; } device = devices[0]; break;
+        case 1000: if (sscanf(optarg, "%lld", &adaptiveBand) != 1 || adaptiveBand < 1 || adaptiveBand > 4) { usage(); return 1; } haveAdaptive = 1; break;
+        case 1001: if (sscanf(optarg, "%lld", &minEdgeScore) != 1 || minEdgeScore < 1) { usage(); return 1; } haveMinEdge = 1; break;
         default: usage(); return 1;
         }
+    }
+    if (haveAdaptive != haveMinEdge) {
+        fprintf(stderr, "cpecan_realign: --adaptiveBand and --minEdgeScore need each other\n");
+        return 1;
     }
     cpecan_model model;
     cpecan_hmm expectations;
@@ -123,6 +134,7 @@ int main(int argc, char **argv) {
     cpecan_realigner *r = NULL;
     if (cpecan_realigner_create(&r, &model, &o, (int)device) != CPECAN_OK) return fail("options");
     if (nDevices > 1 && cpecan_realigner_set_devices(r, devices, nDevices) != CPECAN_OK) return fail("devices");
+    if (haveAdaptive && cpecan_realigner_set_adaptive_band(r, (int)adaptiveBand, minEdgeScore) != CPECAN_OK) return fail("adaptiveBand");
     if (optind >= argc) {
         usage();
         return 1;

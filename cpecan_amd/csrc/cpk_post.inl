@@ -883,3 +883,56 @@ __global__ void __launch_bounds__(256) cpecan_post_list_scores(const CpkPostProb
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Posterior mass on the band's edge (cpecan_band_edge_of_pairs is the host's statement of it).
+// Runs on the compact buffer behind cpecan_gather_lists and in front of every consumer, so the scores are the sweep's.
+// One wave per list-0 chunk -- the triples of one traceback segment of one region -- lanes over its triples: a triple
+// (score, xs + dx, ys + dy) is cell (xs + 1, ys + 1) of its region, on anti-diagonal d = xs + ys + 2 with x - y = xs - ys.
+// The cell is left-cut when it is the band's first cell of d and its neighbour (x - 1, y + 1) is still in the matrix
+// (y + 1 <= lY; x - 1 >= 0 always holds for an emitted pair), right-cut likewise with the last cell and (x + 1, y - 1).
+// Count, sum and maximum are reduced across the wave and leave as one set of atomics of lane 0 into the problem's
+// counters: integers, so the result does not depend on the order of the waves.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) cpecan_post_band_edge(const CpkChunk *chunks, const int32_t *chunkRegion,
+                                                            const int32_t *chunkProblem, int64_t nChunks,
+                                                            const CpkRegion *regions, const CpkDiag *diags,
+                                                            const int32_t *triples, cpecan_band_edge *out) {
+    const int lane = threadIdx.x;
+    for (int64_t c = blockIdx.x; c < nChunks; c += gridDim.x) {
+        const CpkChunk ch = chunks[c];
+        const CpkRegion *rg = regions + chunkRegion[c];
+        const int lX = rg->lX, lY = rg->lY;
+        const CpkDiag *table = diags + rg->diagOff;
+        const int32_t *t = triples + 3 * ch.dst;
+        long long sum = 0;
+        int count = 0, top = 0;
+        for (int i = lane; i < ch.len; i += CPK_WAVE) {
+            const int s = t[3 * i], xs = t[3 * i + 1] - ch.dx, ys = t[3 * i + 2] - ch.dy;
+            const int d = xs + ys + 2;
+            if (xs < 0 || ys < 0 || xs >= lX || ys >= lY) continue;  // (never for a list the sweep wrote: d stays inside the table)
+            const CpkDiag dg = table[d];
+            const int xmy = xs - ys;
+            const bool left = xmy == dg.xmyL && ys + 2 <= lY;
+            const bool right = xmy == dg.xmyL + 2 * (dg.width - 1) && xs + 2 <= lX;
+            if (left || right) {
+                count++;
+                sum += s;
+                top = s > top ? s : top;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            count += __shfl_xor(count, off);
+            sum += __shfl_xor(sum, off);
+            const int o = __shfl_xor(top, off);
+            top = o > top ? o : top;
+        }
+        if (lane == 0 && count > 0) {
+            cpecan_band_edge *e = out + chunkProblem[c];
+            atomicAdd(reinterpret_cast<unsigned long long *>(&e->edgePairs), (unsigned long long)count);
+            atomicAdd(reinterpret_cast<unsigned long long *>(&e->edgeScoreSum), (unsigned long long)sum);
+            atomicMax(&e->edgeScoreMax, top);
+        }
+    }
+}

@@ -16,6 +16,7 @@ EXPORTS = [
     "cpecan_realigner_set_devices", "cpecan_realign_shard_bounds",
     "cpecan_expect_set_create", "cpecan_expect_set_run", "cpecan_expect_set_shards", "cpecan_expect_set_stats",
     "cpecan_expect_set_destroy", "cpecan_expect_set_reserve_models", "cpecan_expect_set_run_models",
+    "cpecan_realigner_set_adaptive_band", "cpecan_realigner_adaptive_rounds",
 ]
 
 
@@ -69,6 +70,8 @@ def _lib():
         L.cpecan_realigner_expectations.argtypes = [vp, C.POINTER(_Cigar), C.c_int64, C.POINTER(api.Hmm)]
         L.cpecan_realigner_set_devices.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
         L.cpecan_realign_shard_bounds.argtypes = [C.POINTER(_Cigar), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+        L.cpecan_realigner_set_adaptive_band.argtypes = [vp, C.c_int, C.c_int64]
+        L.cpecan_realigner_adaptive_rounds.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64]
         _bound = True
     return L
 
@@ -206,6 +209,20 @@ class Realigner:
         arr = (C.c_int * max(1, len(devices)))(*devices)
         api._check(_lib().cpecan_realigner_set_devices(self._h, arr, len(devices)), "cpecan_realigner_set_devices")
 
+    def set_adaptive_band(self, rounds, min_edge_score=0):
+        """cpecan_realigner_set_adaptive_band: cigars whose band-edge score sum reaches min_edge_score run again, up to
+        `rounds` times (0: off), each time with the expansion doubled."""
+        api._check(_lib().cpecan_realigner_set_adaptive_band(self._h, int(rounds), int(min_edge_score)),
+                   "cpecan_realigner_set_adaptive_band")
+
+    def adaptive_rounds(self):
+        """The round every input cigar of the last realign() ended on."""
+        n = getattr(self, "_last_n", None)
+        out = (C.c_int32 * max(1, n or 0))()
+        api._check(_lib().cpecan_realigner_adaptive_rounds(self._h, out, -1 if n is None else n),
+                   "cpecan_realigner_adaptive_rounds")
+        return list(out[:n])
+
     def _pack(self, cigars):
         keep = []
         arr = (_Cigar * max(1, len(cigars)))(*[c._to_c(keep) for c in cigars])
@@ -214,6 +231,7 @@ class Realigner:
     def realign(self, cigars):
         arr, keep = self._pack(cigars)
         out, n = C.POINTER(_Cigar)(), C.c_int64()
+        self._last_n = len(cigars)
         api._check(_lib().cpecan_realigner_realign(self._h, arr, len(cigars), C.byref(out), C.byref(n)),
                    "cpecan_realigner_realign")
         try:

@@ -451,6 +451,36 @@ int cpecan_batch_scores(const cpecan_batch *b, int64_t problem, double *byPoster
  * have been selected (any flag). */
 int cpecan_batch_identity_scores(const cpecan_batch *b, int64_t problem, double *byIdentity, double *byIdentityIgnoringGaps);
 
+/* ---- posterior mass on the band's edge ----
+ * Every kernel computes posteriors inside the band its anchors dictate; this is the per-problem sign that the alignment
+ * wanted to leave it.  A region is what the batch cuts a problem into (the whole problem, or one rectangle of
+ * cpecan_split_points), with lengths lX, lY; its band on anti-diagonal d is xmyL(d) .. xmyR(d) as cpecan_band gives it for
+ * the region's anchors.  Cell (d, xmy) has x = (d + xmy) / 2, y = (d - xmy) / 2 in matrix coordinates.  A cell is LEFT-CUT
+ * iff xmy == xmyL(d), x - 1 >= 0 and y + 1 <= lY -- the next cell along the anti-diagonal lies in the matrix but not in the
+ * band -- and RIGHT-CUT iff xmy == xmyR(d), x + 1 <= lX and y - 1 >= 0.  An edge the matrix itself cuts is no band edge, so
+ * an unanchored region has no cut cell.  An EDGE PAIR is a triple (score, xs, ys) of list 0 of a region whose cell
+ * (xs + 1, ys + 1) is left- or right-cut (both: counted once), taken as the sweep emitted it, before any consumer stage.
+ * Per problem, over all its regions: edgePairs is their count, edgeScoreSum the sum of their scores, edgeScoreMax the
+ * largest (0 without an edge pair).  Only emitted pairs count: mass under `threshold` is not seen.  A pure integer
+ * function of the lists and the band. */
+typedef struct cpecan_band_edge {
+    int64_t edgePairs, edgeScoreSum;
+    int32_t edgeScoreMax, reserved;
+} cpecan_band_edge; /* 24 bytes */
+/* Before download: the next downloads also compute the statistic, with one more kernel between the list gather and the
+ * consumers (0: off, the default -- nothing is allocated and nothing is launched for it).  CPECAN_EINVAL on
+ * CPECAN_EMIT_EXPECT / CPECAN_EMIT_FORWARD batches, which have no lists. */
+int cpecan_batch_set_band_edge(cpecan_batch *b, int on);
+/* After download: the statistic of problem i.  CPECAN_ESTATE if the downloaded run was not asked for it. */
+int cpecan_batch_band_edge(const cpecan_batch *b, int64_t problem, cpecan_band_edge *out);
+/* The definition on the host, no device needed: cuts the problem into regions as cpecan_batch_add does
+ * (cpecan_split_points with p->splitMatrixBiggerThanThis), builds each region's band (cpecan_band with
+ * p->diagonalExpansion, per-anchor expansions when p->dynamicAnchorExpansion) and applies the definition to n triples
+ * (score, x, y) in PROBLEM coordinates, in any order; the regions' rectangles are disjoint, so a pair lies in one region or
+ * in none, which is CPECAN_EINVAL.  This is what the kernel must equal. */
+int cpecan_band_edge_of_pairs(const int64_t *anchors, int64_t nAnchors, int64_t lX, int64_t lY, const cpecan_params *p,
+                              int raggedLeft, int raggedRight, const int32_t *triples, int64_t n, cpecan_band_edge *out);
+
 /* Debug / test hook: for single-region problem i, copies the per-cell forward+backward match sums
  * (fb[cell] = F.match + B.match at emit time) and the total log-probability used for each diagonal.
  * Buffers must hold `cells` and `diagonals` doubles; needs the batch to have been created with

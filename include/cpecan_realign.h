@@ -94,6 +94,23 @@ int cpecan_realign_shard_bounds(const cpecan_cigar *in, int64_t n, int64_t diago
 /* The realign loop (cPecanRealign.c:509-600) over n cigars as one batch.  *out: malloc'd array of *nOut cigars in input
  * order (more than n when splitIndelsLongerThanThis cuts some), to be released with cpecan_cigars_free. */
 int cpecan_realigner_realign(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_cigar **out, int64_t *nOut);
+/* The adaptive band.  The band of a realignment is diagonalExpansion / 2 diagonals either side of
+ * whatever the input cigar says, so a misplaced indel in the input cannot be repaired, and the output looks like any other
+ * cigar.  With maxRounds 1 .. 4 every realign call asks its batch for the band-edge statistic (cpecan_band_edge,
+ * cpecan_hip.h); a cigar is FLAGGED iff its edgeScoreSum >= minEdgeScore.  Round 0 is the call as it is without this
+ * option; round k = 1 .. maxRounds runs the cigars flagged in round k - 1 as a batch of their own with
+ * params.diagonalExpansion * 2^k for the run expansions and the parameter, everything else -- exact-match filter, trim,
+ * consumers -- as before.  A cigar's output (cigar, score, split pieces) is that of its last run: byte for byte what a
+ * realigner without this option returns for it at that expansion.  The posterior files are those of the last cigar's last
+ * run.  maxRounds 0 is off and the default: the calls and launches of a realigner that never heard of it.  minEdgeScore
+ * >= 1 is required when on; it has no default (DESIGN.md section 9 says what the quality record suggests).
+ * CPECAN_EINVAL: maxRounds outside 0 .. 4, minEdgeScore < 1 when on, or a realigner with rescoreOriginalAlignment, which
+ * returns its input.  Expectations calls are unaffected.  With several devices every shard adapts on its own; the result is
+ * per cigar, so it is the same. */
+int cpecan_realigner_set_adaptive_band(cpecan_realigner *r, int maxRounds, int64_t minEdgeScore);
+/* The round each of the n input cigars of the last realign call ended on (all 0 without the option).  CPECAN_ESTATE before
+ * the first realign call, CPECAN_EINVAL when n is not that call's count. */
+int cpecan_realigner_adaptive_rounds(const cpecan_realigner *r, int32_t *rounds, int64_t n);
 /* --outputExpectations (cPecanRealign.c:530-534): adds the expectation counts of the n alignments to *acc, which the
  * caller made with cpecan_hmm_init(acc, type, 0.000000000001) (:497) and writes with cpecan_hmm_write (:612). */
 int cpecan_realigner_expectations(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, cpecan_hmm *acc);
