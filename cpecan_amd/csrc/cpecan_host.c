@@ -1680,6 +1680,24 @@ int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]) {
     return rc;
 }
 
+/* For tests, no device needed: the launches cpecan_batch_upload would plan on a device of numCUs compute units.
+ * (The launch plan lives in the device layer; a program that links this file against a stand-in for that layer need not
+ * have it: a weak reference, CPECAN_ESTATE without it.) */
+extern __typeof__(cpk_plan_describe) cpk_plan_describe __attribute__((weak));
+int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *out, int maxClasses) {
+    if (!b || !out || b->frozen || dl_busy(b) || !cpk_plan_describe) return CPECAN_ESTATE;
+    if (b->nRegions == 0) return 0;
+    HostPlan hp;
+    CpkGeometry geo;
+    CpkModel km;
+    int rc = batch_plan(b, &hp, &geo, &km);
+    if (rc == CPECAN_OK)
+        rc = cpk_plan_describe(&geo, hp.devRegions, hp.dynamic, hp.totalDiags, hp.nSegs, b->nSymbols, b->nAnchorVals / b->anchorStride,
+                               hp.outTriples, b->nLists, b->modelSlots, numCUs, memBytes, out, maxClasses);
+    host_plan_free(&hp);
+    return rc;
+}
+
 int cpecan_batch_upload(cpecan_batch *b) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || b->frozen) return CPECAN_ESTATE;

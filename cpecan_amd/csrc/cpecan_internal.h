@@ -243,6 +243,15 @@ int cpk_host_threads(void); /* threads of the host's parallel loops (cpecan_host
  * CpkRegion array in device order, devToHost, the CpkSegment slots, CpkGeometry with the output and debug totals.  For
  * tests: the plan is dropped again (cpecan_host.c). */
 int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]);
+/* Plans an unfrozen batch as cpecan_batch_upload would and then its launches (cpk_plan.inl, plan_batch) for a device of
+ * numCUs compute units and memBytes of free memory that is not there: a kernel is taken to use the registers its build
+ * allows.  out receives CPK_LAUNCH_PLAN_FIELDS numbers per launch class, in launch order (cpk_plan_describe); returns
+ * the number of classes, or an error code (< 0).  For tests: the plan is dropped again. */
+#define CPK_LAUNCH_PLAN_FIELDS 24
+int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *out, int maxClasses);
+int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, int dynamic, int64_t nDiags, int64_t nSegs, int64_t nSymbolBytes,
+                      int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs, int64_t memBytes,
+                      int64_t *out, int maxClasses);
 
 /* ---- the anchor finder (cpk_anchor.inl; host side in cpecan_anchor.c) ---- */
 /* One problem of an anchor pass: two substrings of the context's symbol buffer.  The host fills the first block, the

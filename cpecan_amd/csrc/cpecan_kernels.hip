@@ -931,6 +931,31 @@ static void count_waves(CpkDevice *d) {
         d->totalWaves += (c.split() && c.wavesTrace > c.waves ? c.wavesTrace : c.wavesWith(d->activeModels)) * (c.threads / CPK_WAVE);
 }
 
+// The launches of a batch on a device that is not there (tests of the plan): CPK_LAUNCH_PLAN_FIELDS numbers per class.
+extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, int dynamic, int64_t nDiags, int64_t nSegs,
+                                 int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
+                                 int64_t memBytes, int64_t *out, int maxClasses) {
+    const PlanKnobs knobs;  // (reads the environment)
+    PlanDevice dev;
+    dev.numCUs = numCUs;
+    dev.freeBytes = dev.totalBytes = (size_t)memBytes;
+    dev.queryKernels = false;
+    const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
+    std::vector<LaunchClass> classes;
+    if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, modelSlots, &classes)) return rc;
+    if ((int)classes.size() > maxClasses) return CPECAN_EINVAL;
+    for (size_t i = 0; i < classes.size(); i++) {
+        const LaunchClass &c = classes[i];
+        const int64_t f[CPK_LAUNCH_PLAN_FIELDS] = {
+            c.packed, c.k, c.regionCount, c.geo.maxWidth, c.geo.nStates, c.form.family, c.form.mode, c.form.wps, c.form.abs, c.form.gang,
+            c.split() && !c.fused() ? c.formTrace.wps : 0, c.split() && !c.fused() ? c.formTrace.gang : 0, c.waves, c.wavesTrace, c.gang,
+            c.gangTrace, (int64_t)c.ldsBytes, (int64_t)c.ldsBytesFwd, (int64_t)c.firstLdsBytes(), (int64_t)c.traceLdsBytes(), c.subSlots,
+            c.threads, c.itemCount, c.firstGrid(1)};
+        for (int j = 0; j < CPK_LAUNCH_PLAN_FIELDS; j++) out[i * CPK_LAUNCH_PLAN_FIELDS + j] = f[j];
+    }
+    return (int)classes.size();
+}
+
 // Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch).
 extern "C" int cpk_device_reserve_models(CpkDevice *d, int nSlots) {
     if (nSlots < 0 || nSlots > CPECAN_MAX_MODEL_SLOTS) return CPECAN_EINVAL;
@@ -996,6 +1021,9 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
                 if (c.fnTrace())
                     HIP_TRY(hipFuncSetAttribute((const void *)c.fnTrace(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.ldsBytes));
             }
+            // a gang may declare the whole LDS of a CU (the same bound for every batch that launches the kernel)
+            if (c.gang > 1) HIP_TRY(hipFuncSetAttribute((const void *)c.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCuLdsBytes));
+            if (c.gangTrace > 1) HIP_TRY(hipFuncSetAttribute((const void *)c.fnTrace(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCuLdsBytes));
         }
         if (int rc = dev_alloc(d, &d->dRing, (size_t)oRing + 256)) return rc;
         if (int rc = dev_alloc(d, &d->dCand, (size_t)oCand)) return rc;
@@ -1288,14 +1316,14 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
         }
         hipStream_t cs = onCaller ? st : d->sideStream[i];
         if (!onCaller) HIP_TRY(hipStreamWaitEvent(cs, d->evStart, 0));
-        hipLaunchKernelGGL(c.fn(), dim3((unsigned)c.wavesWith(d->activeModels)), dim3((unsigned)c.threads), c.firstLdsBytes(), cs, p);
+        hipLaunchKernelGGL(c.fn(), dim3(c.firstGrid(d->activeModels)), dim3(c.firstThreads()), c.firstLdsBytes(), cs, p);
         HIP_TRY(hipGetLastError());
         if (c.split() && !c.fused()) {  // the tracebacks of the class's regions, one queue item each, behind the forward launch
             KArgs t = p;
             t.items = d->dItems + c.itemBase;
             t.regionCount = (int32_t)c.itemCount;
             t.queue = d->dQueue + kMaxClasses + i;
-            hipLaunchKernelGGL(c.fnTrace(), dim3((unsigned)c.wavesTrace), dim3((unsigned)c.threads), c.ldsBytes, cs, t);
+            hipLaunchKernelGGL(c.fnTrace(), dim3(c.traceGrid()), dim3(c.traceThreads()), c.traceLdsBytes(), cs, t);
             HIP_TRY(hipGetLastError());
         }
         if (!onCaller) HIP_TRY(hipEventRecord(d->sideDone[i], cs));

@@ -362,6 +362,13 @@ __device__ __forceinline__ void roll_fence() {
     }
 }
 
+// What roll_fence<true> is to a single-wave workgroup, for one wave of a gang (cpk_sweep.inl "GANG"): the same release /
+// acquire of global memory at workgroup scope without the barrier -- the wave's siblings are elsewhere in their own work.
+__device__ __forceinline__ void gang_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // data this wave wrote earlier in the same launch: always a vector load, never the scalar cache
 __device__ __forceinline__ double ld_self(const double *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -455,6 +462,13 @@ constexpr int kStage = 128;  // LDS staging slots per candidate list (two waves'
 constexpr int kStageAbs = 32;
 __host__ __device__ constexpr int lds_stage_doubles(int emit, bool abs = false) {
     return emit == CPECAN_EMIT_MATCH ? 2 * (abs ? kStageAbs : kStage) : (emit == CPECAN_EMIT_INDEL ? 3 * 2 * kStage : 0);
+}
+// A gang (cpk_sweep.inl "GANG"): up to three waves per SIMD in one workgroup, and the doubles of LDS each of them has to
+// itself behind the shared tables -- rolling rows, candidate stage, symbols padded to 16 bytes.  The plan sizes the
+// workgroup's LDS with the same expression (cpk_plan.inl, gang_lds_bytes).
+constexpr int kGangMaxWaves = 12;
+__host__ __device__ constexpr int64_t lds_gang_private_doubles(int64_t rollDoubles, int stageDoubles, int seqLdsBytes) {
+    return rollDoubles + stageDoubles + (seqLdsBytes + 15) / 16 * 2;
 }
 constexpr int kPrefetch = 3;  // passes (of 64 cells) of F.match prefetched one diagonal ahead in the traceback
 constexpr float kCandMargin = 3.0f;  // log-space slack of the candidate filter (see DESIGN.md "candidate filter")

@@ -15,16 +15,18 @@ struct KernelForm {
     int inSweep = 0;    // sweep: expectation events inside the traceback, for one / two groups per diagonal (INSWEEP)
     bool slots = false, dynamic = false;  // dynamic: packed, per-anchor expansions (DYN)
     int width = 0;      // packed: lanes of a group (GW); team: waves (T)
+    bool gang = false;  // sweep: workgroups of several waves that share the LDS tables (GANG)
 };
 constexpr bool operator==(const KernelForm &a, const KernelForm &b) {
     return a.family == b.family && a.S == b.S && a.emit == b.emit && a.mode == b.mode && a.fast == b.fast && a.wps == b.wps && a.abs == b.abs &&
-           a.inSweep == b.inSweep && a.slots == b.slots && a.dynamic == b.dynamic && a.width == b.width;
+           a.inSweep == b.inSweep && a.slots == b.slots && a.dynamic == b.dynamic && a.width == b.width && a.gang == b.gang;
 }
 struct KernelEntry { KernelForm form; KernelFn fn; };
 // One macro per family builds the key and the pointer of an entry from the same argument list; _F repeats it for LDS and
 // global rows, _G / _T for the three group widths / the two team sizes, CPK_BOTH(row macro, ...) for both state counts.
-#define CPK_SWEEP(S, FAST, EMIT, MODE, WPS, ABS, INSWEEP, SLOTS) \
-    {KernelForm{kFamilySweep, S, EMIT, MODE, FAST, WPS, ABS, INSWEEP, SLOTS, false, 0}, cpecan_pairhmm_sweep<S, FAST, EMIT, MODE, WPS, ABS, INSWEEP, SLOTS>},
+#define CPK_SWEEP_GANG(S, FAST, EMIT, MODE, WPS, ABS, INSWEEP, SLOTS, GANG) \
+    {KernelForm{kFamilySweep, S, EMIT, MODE, FAST, WPS, ABS, INSWEEP, SLOTS, false, 0, GANG}, cpecan_pairhmm_sweep<S, FAST, EMIT, MODE, WPS, ABS, INSWEEP, SLOTS, GANG>},
+#define CPK_SWEEP(...) CPK_SWEEP_GANG(__VA_ARGS__, false)
 #define CPK_PACKED(S, GW, EMIT, DYN, MODE, SLOTS) \
     {KernelForm{kFamilyPacked, S, EMIT, MODE, false, 0, false, 0, SLOTS, DYN, GW}, cpecan_pairhmm_packed<S, GW, EMIT, DYN, MODE, SLOTS>},
 #define CPK_TEAM(S, T, EMIT, SLOTS) \
@@ -57,6 +59,9 @@ constexpr KernelEntry kKernelTable[] = {
     CPK_BOTH(CPK_SWEEP, true, CPECAN_EMIT_MATCH, kModeForward, 3, true, 0, false)
     CPK_BOTH(CPK_SWEEP, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true, 0, false)
     CPK_BOTH(CPK_SWEEP, true, CPECAN_EMIT_MATCH, kModeFused, 3, true, 0, false)
+    // ... the two launches at three waves per SIMD as gangs: workgroups of several waves, one copy of the tables
+    CPK_BOTH(CPK_SWEEP_GANG, true, CPECAN_EMIT_MATCH, kModeForward, 3, true, 0, false, true)
+    CPK_BOTH(CPK_SWEEP_GANG, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true, 0, false, true)
     // dense classes: the three-state match kernels for three waves per SIMD (the forward launch needs 70 VGPRs: one variant)
     CPK_SWEEP_F(3, CPECAN_EMIT_MATCH, kModeWhole, 3, false, 0, false)
     CPK_SWEEP_F(3, CPECAN_EMIT_MATCH, kModeTrace, 3, false, 0, false)
@@ -79,6 +84,7 @@ constexpr KernelEntry kKernelTable[] = {
     CPK_BOTH(CPK_TEAM_T, CPECAN_EMIT_EXPECT, true)
 };
 #undef CPK_SWEEP
+#undef CPK_SWEEP_GANG
 #undef CPK_PACKED
 #undef CPK_TEAM
 #undef CPK_SWEEP_F
@@ -130,6 +136,8 @@ constexpr bool split_forms_have_kernels(const KernelForm &whole, bool dense) {  
             if (!has_kernel(s)) return false;
             s.wps = 3;  // the requests for three waves per SIMD: the forward launch; a five-state traceback or one launch
             if (abs && (mode == kModeForward || s.S == 5) && !has_kernel(s)) return false;
+            s.gang = true;  // ... and their gangs: the two launches (take_gang)
+            if (abs && mode != kModeFused && !has_kernel(s)) return false;
         }
     return true;
 }

@@ -14,7 +14,7 @@ struct LaunchClass {
     KernelFn fn() const { return kernel_of(form); }
     KernelFn fnTrace() const { return kernel_of(formTrace); }
     CpkGeometry geo{};   // what the kernel reads: the scalar fields describe this class
-    int waves = 0;       // workgroups of the launch
+    int waves = 0;       // workgroups of the launch (a gang: its waves, `gang` to a workgroup)
     // A reserved batch (model slots, KArgs::slotModels): the SLOTS build of the kernel, and the workgroups of a run with
     // t models, 1 <= t <= the reserved count -- `waves` is the most of them, which the per-wave scratch is sized for
     bool slots() const { return form.slots; }
@@ -32,12 +32,26 @@ struct LaunchClass {
     bool dense = false;  // the plan's decision: the three-state match kernels allocated for three waves per SIMD (WPS = 3)
     bool abs = false;    // LDS rows for sweeps over absolute positions (set_row_form; cpk_sweep.inl "Absolute-position sweeps"): the ABS of a split class's kernels
     int wavesTrace = 0;
+    // Gangs (cpk_sweep.inl "GANG"): waves per workgroup of the forward and of the traceback launch of a two-launch class, 0: one
+    // wave per workgroup.  `waves` / `wavesTrace` stay counts of WAVES -- whole gangs --, ldsBytes / ldsBytesFwd the LDS of one.
+    int gang = 0, gangTrace = 0;
     int64_t itemBase = 0, itemCount = 0;  // its items in dItems
     int64_t ringTotal = 0;                // doubles of all its regions' rings (ringEl is 0 then: nothing per slot)
     int64_t ringEl = 0, candEl = 0, refEl = 0, totEl = 0, bringEl = 0, grollEl = 0;  // elements per scratch slot
     int64_t oRing = 0, oCand = 0, oRef = 0, oTot = 0, oBring = 0, oGroll = 0, oExpect = 0;  // element offsets of the class
     // LDS bytes of the first launch: the forward launch of a two-launch class has a size of its own where the plan set one
-    size_t firstLdsBytes() const { return (split() && !fused() && ldsBytesFwd) ? ldsBytesFwd : ldsBytes; }
+    size_t firstLdsBytes() const { return gang_lds_bytes((split() && !fused() && ldsBytesFwd) ? ldsBytesFwd : ldsBytes, gang); }
+    size_t traceLdsBytes() const { return gang_lds_bytes(ldsBytes, gangTrace); }
+    // the LDS of a workgroup of n waves whose single wave takes waveLds: the tables once, the rest n times
+    size_t gang_lds_bytes(size_t waveLds, int n) const {
+        const size_t shared = sizeof(double) * lds_header_doubles(geo.emit);
+        return n > 1 ? shared + (size_t)n * (waveLds - shared) : waveLds;
+    }
+    // workgroups and threads per workgroup of the two launches
+    unsigned firstGrid(int nModels) const { return (unsigned)(gang > 1 ? (wavesWith(nModels) + gang - 1) / gang : wavesWith(nModels)); }
+    unsigned firstThreads() const { return (unsigned)(gang > 1 ? gang * CPK_WAVE : threads); }
+    unsigned traceGrid() const { return (unsigned)(gangTrace > 1 ? (wavesTrace + gangTrace - 1) / gangTrace : wavesTrace); }
+    unsigned traceThreads() const { return (unsigned)(gangTrace > 1 ? gangTrace * CPK_WAVE : threads); }
     double slotBytes() const {
         return 8.0 * ringEl + (double)sizeof(Candidate) * candEl + 16.0 * refEl + 8.0 * totEl + 8.0 * bringEl + 8.0 * grollEl;
     }
@@ -99,6 +113,7 @@ struct PlanKnobs {
     Knob<int> fused3{"CPECAN_FUSED3"};  // =0: never the three-waves-per-SIMD build of the one-launch form
     Knob<int> trace3{"CPECAN_TRACE3"};  // =0: never the three-waves-per-SIMD build of the traceback launch
     Knob<int> fwd3{"CPECAN_FWD3"};  // =0: never the three-waves-per-SIMD build of the forward launch
+    Knob<int> gang{"CPECAN_GANG"};  // =0: never workgroups of several waves (gangs); n in 2..12: n waves per workgroup wherever the form allows it and n fit
     Knob<double> memBudgetMb{"CPECAN_MEM_BUDGET_MB"};  // the device memory the batch may plan with (test / diagnostic knob)
     Knob<double> splitBudgetFrac{"CPECAN_SPLIT_BUDGET_FRAC"};  // the share of the device the rings of whole regions may take (default 0.45)
     bool traceHost = getenv("CPECAN_TRACE_HOST") != nullptr;  // one line per planned class on stderr
@@ -109,6 +124,9 @@ struct PlanDevice {
     size_t freeBytes = 0, totalBytes = 0;  // hipMemGetInfo
     size_t idleCachedBytes = 0;            // idle blocks of the block cache: ours to reuse or drop
     bool othersAlive = false;              // another batch of this process has run on the device and is not destroyed yet
+    // false (planning without a device: the tests of the plan): a kernel is taken to use the registers its build allows
+    // it -- 512 / WPS, in granules -- and no static LDS, instead of what the loaded code object reports
+    bool queryKernels = true;
 };
 // The sizes of a batch that no plan changes: what its tables, strings and results take on the device.
 struct PlanFixedSizes {
@@ -129,15 +147,30 @@ struct PlanInputs {
 // directly.  Over-estimating is harmless: surplus workgroups simply queue, every wave exits when the work queue is empty.
 // A team of four puts one wave on every SIMD, a team of eight two.  CPECAN_MAX_WAVES_PER_CU counts single waves and has
 // never applied to teams.
-static int waves_per_cu(const KernelForm &form, size_t ldsBytes, int wavesPerWorkgroup, const PlanKnobs &knobs, int *out) {
-    hipFuncAttributes attr;
-    HIP_TRY(hipFuncGetAttributes(&attr, (const void *)kernel_of(form)));
-    const int vgprAlloc = ((attr.numRegs > 0 ? attr.numRegs : 128) + kVgprGranule - 1) / kVgprGranule * kVgprGranule;
+// Waves per SIMD the registers of a form's kernel allow, and its static LDS.
+static int kernel_resources(const PlanDevice &dev, const KernelForm &form, int *perSimdOut, size_t *staticLds) {
+    int numRegs = 0;
+    *staticLds = 0;
+    if (dev.queryKernels) {
+        hipFuncAttributes attr;
+        HIP_TRY(hipFuncGetAttributes(&attr, (const void *)kernel_of(form)));
+        numRegs = attr.numRegs;
+        *staticLds = (size_t)attr.sharedSizeBytes;
+    } else if (form.family == kFamilySweep && form.wps > 0) numRegs = kSimdVgprs / form.wps / kVgprGranule * kVgprGranule;
+    const int vgprAlloc = ((numRegs > 0 ? numRegs : 128) + kVgprGranule - 1) / kVgprGranule * kVgprGranule;
     int perSimd = kSimdVgprs / vgprAlloc;
     if (perSimd > kMaxWavesPerCU / kSimdsPerCU) perSimd = kMaxWavesPerCU / kSimdsPerCU;
     if (perSimd < 1) perSimd = 1;
+    *perSimdOut = perSimd;
+    return CPECAN_OK;
+}
+static int waves_per_cu(const KernelForm &form, size_t ldsBytes, int wavesPerWorkgroup, const PlanInputs &in, int *out) {
+    const PlanKnobs &knobs = in.knobs;
+    int perSimd = 0;
+    size_t staticLds = 0;
+    if (int rc = kernel_resources(in.dev, form, &perSimd, &staticLds)) return rc;
     int perCU = kSimdsPerCU * perSimd / wavesPerWorkgroup;
-    const size_t ldsTotal = ldsBytes + (size_t)attr.sharedSizeBytes;
+    const size_t ldsTotal = ldsBytes + staticLds;
     const int byLds = (int)(kCuLdsBytes / (ldsTotal ? ldsTotal : 1));
     if (byLds < perCU) perCU = byLds;
     if (perCU > kMaxWavesPerCU / wavesPerWorkgroup) perCU = kMaxWavesPerCU / wavesPerWorkgroup;
@@ -179,7 +212,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
     c.ldsBytes = sizeof(double) * (size_t)(kLdsCubics + kLdsEm + kLdsWeights + (expect ? kExpectCopies * 80 : 0)) +
                  (size_t)G * pack_group_bytes(S, GW);
     int perCU = 0;
-    if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in.knobs, &perCU)) return rc;
+    if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in, &perCU)) return rc;
     const int64_t slots = (int64_t)perCU * in.dev.numCUs;
     c.ringEl = c.geo.ringCells * S;
     c.candEl = c.geo.fbCells;
@@ -274,8 +307,8 @@ static void share_packed_slots(const PlanInputs &in, std::vector<LaunchClass> *p
     for (const LaunchClass &cc : *packedSplit) total += cc.waves;
     for (const LaunchClass &cc : *packedWhole) total += cc.waves;
     int perCU0 = 0;  // (of the first class; a failed query leaves 0 and with it every class as it is)
-    for (const LaunchClass &cc : *packedSplit) if (!perCU0) (void)waves_per_cu(cc.formTrace, cc.ldsBytes, 1, in.knobs, &perCU0);
-    for (const LaunchClass &cc : *packedWhole) if (!perCU0) (void)waves_per_cu(cc.form, cc.ldsBytes, 1, in.knobs, &perCU0);
+    for (const LaunchClass &cc : *packedSplit) if (!perCU0) (void)waves_per_cu(cc.formTrace, cc.ldsBytes, 1, in, &perCU0);
+    for (const LaunchClass &cc : *packedWhole) if (!perCU0) (void)waves_per_cu(cc.form, cc.ldsBytes, 1, in, &perCU0);
     const int64_t room = (int64_t)perCU0 * in.dev.numCUs - in.dev.numCUs / 8;
     if (!(total > room && room > 0)) return;
     for (std::vector<LaunchClass> *part : {packedSplit, packedWhole})
@@ -333,9 +366,37 @@ static void plan_expect_in_sweep(LaunchClass &c, const PlanKnobs &knobs) {
 static int take_three_waves(const PlanInputs &in, KernelForm *f, size_t ldsBytes, int perCU, int *p3) {
     KernelForm f3 = *f;
     f3.wps = 3;
-    if (int rc = waves_per_cu(f3, ldsBytes, 1, in.knobs, p3)) return rc;
+    if (int rc = waves_per_cu(f3, ldsBytes, 1, in, p3)) return rc;
     if (*p3 > perCU) *f = f3;
     else *p3 = 0;
+    return CPECAN_OK;
+}
+
+// The gang a launch of class `c` could run as (`f`: its kernel, waveLds: the LDS of one wave of it): *g waves per workgroup
+// and *perCU resident waves per CU, or 0 where the form has no gang build, its registers do not allow three waves per SIMD
+// or fewer than two waves fit.  forced: CPECAN_GANG=n, that many waves per workgroup -- as many workgroups per CU as fit --,
+// else one workgroup per CU of as many waves as fit, twelve at most.
+static int gang_waves(const PlanInputs &in, const LaunchClass &c, KernelForm f, size_t waveLds, int forced, int *g, int *perCU) {
+    *g = *perCU = 0;
+    f.wps = 3;
+    f.gang = true;
+    if (!has_kernel(f)) return CPECAN_OK;
+    int perSimd = 0;
+    size_t staticLds = 0;
+    if (int rc = kernel_resources(in.dev, f, &perSimd, &staticLds)) return rc;
+    const size_t shared = sizeof(double) * lds_header_doubles(c.geo.emit) + staticLds, own = c.gang_lds_bytes(waveLds, 2) - c.gang_lds_bytes(waveLds, 1);
+    if (perSimd < 3 || own == 0 || shared + 2 * own > kCuLdsBytes) return CPECAN_OK;
+    int n = (int)((kCuLdsBytes - shared) / own);
+    if (n > kGangMaxWaves) n = kGangMaxWaves;
+    int groups = 1;
+    if (forced) {
+        if (forced < 2 || forced > n) return CPECAN_OK;
+        n = forced;
+        groups = (int)(kCuLdsBytes / (shared + (size_t)n * own));
+        if (groups > kGangMaxWaves / n) groups = kGangMaxWaves / n;
+    }
+    *g = n;
+    *perCU = groups * n;
     return CPECAN_OK;
 }
 
@@ -359,7 +420,7 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
     // the global-memory variant.  CPECAN_TEAM=<cells> (tests, diagnostics): from that band width instead; 0: never.
     const Knob<int> &teamEnv = in.knobs.team;
     int soloPerCU = 0;
-    if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in.knobs, &soloPerCU)) return rc;
+    if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in, &soloPerCU)) return rc;
     const bool wanted = teamEnv.set ? (teamEnv.v > 0 && c.geo.maxWidth >= teamEnv.v)
                                     : (c.geo.maxWidth > 256 && (soloPerCU <= 3 || c.geo.useGlobalRoll));
     // one workgroup per CU is all the LDS allows from ~660 cells: then eight waves share the region
@@ -378,7 +439,7 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
         c.geo.rollDoubles = (int64_t)(2 * S + 1) * c.geo.rollStride;
         c.ldsBytes = teamLds;
         c.grollEl = 0;
-        if (int rc = waves_per_cu(c.form, teamLds, c.threads / CPK_WAVE, in.knobs, &perCU)) return rc;
+        if (int rc = waves_per_cu(c.form, teamLds, c.threads / CPK_WAVE, in, &perCU)) return rc;
         if (perCU < 1) perCU = 1;
     } else {
         perCU = soloPerCU;
@@ -471,6 +532,7 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
     int64_t wt = slots < nSegClass ? slots : nSegClass;
     c.wavesTrace = (int)wt;
     if (wt > c.subSlots) c.subSlots = wt;
+    int perCUTrace = perCU, perCUFwd = perCU;  // resident waves per CU of either launch
     // the forward launch: no candidate ring in its LDS, and with absolute positions few enough registers
     // for three waves per SIMD -- more waves per CU where that LDS allows them (CPECAN_FWD3=0: never)
     c.ldsBytesFwd = c.geo.useGlobalRoll ? c.ldsBytes : c.ldsBytes - sizeof(double) * lds_stage_doubles(geo.emit, c.abs);
@@ -483,6 +545,7 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
             if (w3 > nSegClass) w3 = nSegClass;
             c.wavesTrace = (int)w3;
             if (w3 > c.subSlots) c.subSlots = w3;
+            perCUTrace = p3;
         }
     }
     if (c.abs && !in.knobs.fwd3.off() && kCuLdsBytes / c.ldsBytesFwd >= kThreeWpsLdsWaves) {
@@ -492,9 +555,56 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
             int64_t wf = (int64_t)p3 * numCUs;
             if (wf > n) wf = n;
             c.waves = (int)even_rounds(n, wf);  // forward waves touch no per-slot scratch: subSlots stays as it is
+            perCUFwd = p3;
+        }
+    }
+    // Gangs: either launch as workgroups of several waves with one copy of the tables (cpk_sweep.inl "GANG").  One workgroup
+    // may declare the whole LDS of a CU, so what the tables took in every wave becomes room for one wave more: config B,
+    // ten single waves per CU -> one gang of eleven.  Taken (CPECAN_GANG unset) by a launch that already runs the build for
+    // three waves per SIMD and whose queue fills every wave of every gang -- with less work than that, gangs would crowd
+    // onto few CUs the waves that single-wave workgroups spread over all of them (config A keeps its plan).  Measured at
+    // config B (profiles/gang_workgroups_ab.txt): the traceback launch alone 83.3 -> 79.2 ms per step, both launches 76.4.
+    if (c.abs && !c.geo.useGlobalRoll && !in.knobs.gang.off()) {
+        const int forced = in.knobs.gang.set ? in.knobs.gang.v : 0;
+        // The traceback launch: items are handed out longest first to whoever is free, so every wave more per CU counts --
+        // a gang where it puts more waves on a CU than single-wave workgroups do.
+        int g = 0, perCUGang = 0;
+        if (int rc = gang_waves(in, c, c.formTrace, c.ldsBytes, forced, &g, &perCUGang)) return rc;
+        if (g > 1 && (forced || (c.formTrace.wps == 3 && perCUGang > perCUTrace && nSegClass >= (int64_t)perCUGang * numCUs))) {
+            c.formTrace.wps = 3;
+            c.formTrace.gang = true;
+            c.gangTrace = g;
+            int64_t w = (int64_t)perCUGang * numCUs;
+            if (w > nSegClass) w = nSegClass;
+            c.wavesTrace = (int)((w + g - 1) / g * g);  // whole gangs: a wave without an item leaves at once
+            if (c.wavesTrace > c.subSlots) c.subSlots = c.wavesTrace;
+        }
+        // The forward launch is quantised -- equal regions run in rounds -- so the rounds, evened out, keep deciding its
+        // wave count: the waves a round fewer asks for where the gangs' waves per CU take one off, else the count it has,
+        // laid out as whole gangs -- all of them resident at once, or a round would be added.
+        if (int rc = gang_waves(in, c, c.form, c.ldsBytesFwd, forced, &g, &perCUGang)) return rc;
+        const int64_t cap = (int64_t)perCUGang * numCUs;
+        if (g > 1 && (forced || (c.form.wps == 3 && perCUGang > perCUFwd && n >= cap))) {
+            int64_t w = c.waves;
+            if (!forced && (n + cap - 1) / cap < (n + w - 1) / w) w = even_rounds(n, cap);
+            const int64_t groups = (w + g - 1) / g;
+            if (forced || groups * g <= cap) {
+                c.form.wps = 3;
+                c.form.gang = true;
+                c.gang = g;
+                c.waves = (int)(groups * g);
+            }
         }
     }
     return CPECAN_OK;
+}
+
+// ", gang of n ..." for a class's CPECAN_TRACE_HOST line: the launches that run as gangs, with the LDS of a workgroup
+static std::string gang_words(const LaunchClass &c) {
+    std::string w;
+    if (c.gang > 1) w += ", forward launch: gang of " + std::to_string(c.gang) + " (LDS " + std::to_string(c.firstLdsBytes()) + " B)";
+    if (c.gangTrace > 1) w += ", traceback launch: gang of " + std::to_string(c.gangTrace) + " (LDS " + std::to_string(c.traceLdsBytes()) + " B)";
+    return w;
 }
 
 // The wide class k (the sweep kernel, one region per wave or team at a time), its regions from `base` in the device order.
@@ -565,8 +675,9 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     c.regionCount = geo.nWide[k];
     if (int rc = plan_split_form(in, c, nSegClass, perCU)) return rc;
     if (in.knobs.traceHost)
-        fprintf(stderr, "cpecan class %d: %d regions, widest diagonal %d, LDS %zu B (forward launch %zu B), waves %d / %d, %s\n", k,
-                c.regionCount, c.geo.maxWidth, c.ldsBytes, c.ldsBytesFwd, c.waves, c.wavesTrace, form_words(c.form, c.dense).c_str());
+        fprintf(stderr, "cpecan class %d: %d regions, widest diagonal %d, LDS %zu B (forward launch %zu B), waves %d / %d, %s%s\n", k,
+                c.regionCount, c.geo.maxWidth, c.ldsBytes, c.ldsBytesFwd, c.waves, c.wavesTrace, form_words(c.form, c.dense).c_str(),
+                gang_words(c).c_str());
     c.ringEl = c.geo.ringCells * S;
     c.candEl = c.geo.fbCells * (geo.emit == CPECAN_EMIT_INDEL ? 3 : 1);  // candidate lists
     c.refEl = c.geo.refreshCells;
@@ -581,6 +692,8 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
 static void unsplit(LaunchClass &c, const PlanKnobs &knobs) {
     c.form = with_mode(c.form, kModeWhole, c.dense);
     c.formTrace = KernelForm{};
+    c.form.gang = false;
+    c.gang = c.gangTrace = 0;
     c.itemCount = 0;
     c.ringTotal = 0;
     c.ringEl = c.geo.ringCells * c.geo.nStates;

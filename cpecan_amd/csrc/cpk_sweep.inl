@@ -2158,14 +2158,24 @@ constexpr int kModeWhole = 0, kModeForward = 1, kModeTrace = 2, kModeFused = 3;
 // holds to the old slot's partial result, starts them again from zero and refills its weight table -- at most nModels
 // times, outside the diagonal loops.  A template parameter, not a test at ticket time: the builds of plain batches are
 // the code they were (the five-state expectation kernels have no register to give away).
-template <int S, bool FAST, int EMIT, int MODE = kModeWhole, int WPS = CPK_SWEEP_WAVES, bool ABS = false, int INSWEEP = 0, bool SLOTS = false>
-__global__ void __launch_bounds__(CPK_WAVE) __attribute__((amdgpu_waves_per_eu(WPS, WPS)))
+// GANG: the two launches of a split class over absolute positions as workgroups of SEVERAL waves (blockDim.x / 64 of them, up
+// to kGangMaxWaves: three per SIMD) that share ONE copy of the read-only tables -- logAdd cubics and weights, the same in
+// every wave of a plain launch -- at the base of the workgroup's LDS; behind it every wave has a private block of rows,
+// candidate stage and symbol window (lds_gang_private_doubles), and a scratch slot of its own.  One workgroup may declare
+// the whole LDS of a CU, so the tables are paid for once per CU instead of once per wave.  The waves meet at ONE barrier,
+// behind the fill of the tables and of their rows; from there on each is on its own -- its fences are wave-scope, it draws
+// its own tickets and leaves at an empty queue while its siblings work on.  The other builds are the code they were.
+template <int S, bool FAST, int EMIT, int MODE = kModeWhole, int WPS = CPK_SWEEP_WAVES, bool ABS = false, int INSWEEP = 0, bool SLOTS = false,
+          bool GANG = false>
+__global__ void __launch_bounds__(GANG ? kGangMaxWaves * CPK_WAVE : CPK_WAVE) __attribute__((amdgpu_waves_per_eu(WPS, WPS)))
 cpecan_pairhmm_sweep(const KArgs a) {
+    static_assert(!GANG || (ABS && WPS == 3 && (MODE == kModeForward || MODE == kModeTrace)), "gangs: the two launches of a split class over absolute positions, three waves per SIMD");
     static_assert(!SLOTS || (MODE == kModeWhole && (EMIT == CPECAN_EMIT_EXPECT || EMIT == kEmitForward)), "model slots: expectation and forward emitters, whole regions");
     static_assert(!ABS || (FAST && MODE != kModeWhole && EMIT == CPECAN_EMIT_MATCH), "absolute positions: split classes of the match emitter");
     static_assert(!INSWEEP || (FAST && MODE == kModeWhole && EMIT == CPECAN_EMIT_EXPECT), "in-sweep events: expectation emitter, LDS rows");
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int lane = threadIdx.x;
+    const int lane = GANG ? (int)(threadIdx.x & (CPK_WAVE - 1)) : (int)threadIdx.x;
+    const int wave = GANG ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / CPK_WAVE)) : 0;  // of the workgroup
     const CpkModel *mp = SLOTS ? &a.slotModels[0].m : a.model;  // (SLOTS: the model of the slot this wave holds)
     int curSlot = 0;
     const int stride = a.geo.rollStride;
@@ -2173,12 +2183,13 @@ cpecan_pairhmm_sweep(const KArgs a) {
     const int rollDoubles = (ABS ? 2 * S : 2 * S + 1) * stride;
 
     // LDS (doubles): logAdd cubics | emission tables | expectation sums | rolling buffers (FAST) | symbol strings (FAST)
+    // (GANG: the tables once, filled by wave 0 -- fill_cubics strides over threadIdx.x --, then rows, stage and symbols per wave)
     fill_cubics(lds);
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
     double *em = lds + kLdsCubics;  // (no plain emission table any more: kLdsEm == 0, every term reads `wt`)
     double *wt = lds + kLdsCubics + kLdsEm;
     if constexpr (SLOTS) fill_weights<S>(wt, *mp, a.slotModels[0].kc, lane);
-    else fill_weights<S>(wt, *mp, a.kc, lane);
+    else if (!GANG || wave == 0) fill_weights<S>(wt, *mp, a.kc, lane);
     double *eLds = lds + kLdsCubics + kLdsEm + kLdsWeights;  // emission-expectation sums of this wave (expectation emitter)
     constexpr int kECopies = lds_expect_copies(INSWEEP != 0);
     if (EMIT == CPECAN_EMIT_EXPECT)
@@ -2189,10 +2200,12 @@ cpecan_pairhmm_sweep(const KArgs a) {
     for (int i = 0; i < kNT; i++) tAcc[i] = 0.0;
     double likelihood = 0.0;
     constexpr int kHeader = lds_header_doubles(EMIT, INSWEEP != 0);
-    double *roll = FAST ? (lds + kHeader) : (a.groll + (size_t)blockIdx.x * a.geo.rollDoubles);
-    Candidate *stageLds = reinterpret_cast<Candidate *>(lds + kHeader + (FAST ? (size_t)rollDoubles : 0));
     constexpr int kStageDoubles = MODE == kModeForward ? 0 : lds_stage_doubles(EMIT, ABS);  // a forward launch stages no candidates
-    uint8_t *seqLds = reinterpret_cast<uint8_t *>(lds + kHeader + (size_t)rollDoubles + kStageDoubles);
+    double *mine = lds + kHeader;  // what follows the tables: this wave's own
+    if constexpr (GANG) mine += (size_t)wave * lds_gang_private_doubles(rollDoubles, kStageDoubles, a.geo.seqLdsBytes);
+    double *roll = FAST ? mine : (a.groll + (size_t)blockIdx.x * a.geo.rollDoubles);
+    Candidate *stageLds = reinterpret_cast<Candidate *>(mine + (FAST ? (size_t)rollDoubles : 0));
+    uint8_t *seqLds = reinterpret_cast<uint8_t *>(mine + (size_t)rollDoubles + kStageDoubles);
     // every rolling cell starts as -inf; position 0 of each row is never written again (the guard)
     for (int i = lane; i < rollDoubles; i += CPK_WAVE) roll[i] = NEG_INF;
     // expectation step inside the traceback (Sweep::tracebackExpect): three F slots and the window's emission sums behind the strings
@@ -2203,7 +2216,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
         for (int i = lane; i < 3 * (a.geo.maxWidth + 1) * S; i += CPK_WAVE) frowLds[i] = NEG_INF;
         for (int i = lane; i < kExpectWinCopies * 80; i += CPK_WAVE) eWinLds[i] = 0;
     }
-    __syncthreads();
+    __syncthreads();  // (GANG: the only barrier of the workgroup -- nothing below waits for another wave)
 
     // one partial result per resident wave (SLOTS: per slot and wave): [0,25) transitions [from*S+to], [25,105) emissions, [105] likelihood
     auto flushExpect = [&](int vs) __attribute__((always_inline)) {
@@ -2233,7 +2246,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
             if (lane == 0) dst[105] = v;
         }
     };
-    const size_t slot = blockIdx.x;
+    const size_t slot = GANG ? (size_t)blockIdx.x * (blockDim.x / CPK_WAVE) + wave : (size_t)blockIdx.x;  // the scratch slot of this wave
     for (;;) {
         // Every lane takes part in the ticket fetch (lane 0 adds 1, the others add 0; hipcc folds this into one
         // atomic per wave).  Do NOT write this as `if (lane == 0) ticket = atomicAdd(..)`: hipcc 7.2 jump-threads
@@ -2469,8 +2482,15 @@ cpecan_pairhmm_sweep(const KArgs a) {
                 if constexpr (ABS) sw.template tracebackAbs<NL, true>(sg, endPrior, (a.geo.debug & 1) ? a.dbgFb + rg.dbgCellOff : nullptr, nCand);
                 else if constexpr (INSWEEP != 0) sw.tracebackExpect(sg, endPrior, (a.geo.debug & 1) ? a.dbgFb + rg.dbgCellOff : nullptr);
                 else sw.template traceback<NL, EMIT != CPECAN_EMIT_EXPECT>(sg, endPrior, (a.geo.debug & 1) ? a.dbgFb + rg.dbgCellOff : nullptr, nCand);
-                roll_fence<true>();  // candidate / cbuf / mbuf stores of all lanes are complete before they are re-read
-                sw.foldTotals(sg, table);
+                // candidate / cbuf / mbuf stores of all lanes are complete before they are re-read, and so are the totals
+                if constexpr (GANG) {
+                    gang_fence();
+                    sw.template foldTotals<true>(sg, table);  // (the form without a barrier at its end)
+                    gang_fence();
+                } else {
+                    roll_fence<true>();
+                    sw.foldTotals(sg, table);
+                }
                 if (a.geo.debug & 1) {
                     for (int d2 = sg.tbPrev + 1 + lane; d2 <= sg.tbFrom; d2 += CPK_WAVE)
                         a.dbgTotals[rg.dbgDiagOff + d2] = ld_self(sw.totals + (sg.tbFrom - d2) / CPK_REFRESH_PERIOD);
