@@ -329,10 +329,30 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return v;
 }
 
+// Largest v of the 64 lanes, in every lane (wave-uniform: it comes back through an SGPR).  The scheme of wave_sum_f32 below
+// with v_max_f32 taking its first operand over DPP: row_shr:1/2/4/8 leave a row's maximum in its lane 15, row_bcast:15 / :31
+// join the rows, lane 63 holds the result -- six v_max_f32 and one v_readlane, no LDS (six rounds of __shfl_xor are six
+// ds_bpermute_b32, each with its wait and five instructions around it).  A lane whose DPP source does not exist, or whose
+// row the row mask leaves out, is not written: it keeps its own value, so the destination IS the old value.  v_max_f32
+// returns its other operand when one is a quiet NaN, as fmaxf does; a maximum does not depend on the order.
+// Written as assembly: from v = fmaxf(v, update_dpp(v, v, ...)) hipcc makes a copy, a v_mov_b32_dpp and two canonicalising
+// v_max_f32 in front of every maximum (25 instructions).  s_nop 1: a DPP operand written by the previous vector
+// instruction needs two wait states, and nothing schedules the inside of an asm block.
 __device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
+    asm("s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+        : "+v"(v));
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
 // Sum of v over the 64 lanes, in every lane: an inclusive scan inside the rows of 16 lanes (row_shr), the rows joined with

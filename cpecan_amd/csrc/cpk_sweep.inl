@@ -945,42 +945,38 @@ struct Sweep {
                 //     bound, this diagonal's largest F.m + B.m: renewed every 10th diagonal as
                 //     max(this diagonal's maximum, old bound - 1); the reference itself asserts that consecutive totals
                 //     differ by less than 1.0 (:834), so the decayed bound stays below the current total.
-                float diagMax = -__builtin_huge_valf();
+                //     The maximum is kept per lane and reduced over the wave ONCE per refresh point.  (The groups do not advance in
+                //     lock-step here as they do in tracebackAbs: these builds have no registers to spare for it -- the three-wave
+                //     ones went from 36-60 to 60-76 bytes of scratch, the indel emitter began to spill.)
+                float laneMax = -__builtin_huge_valf();
                 auto dotCell = [&](int k, int kR, const double (&fRow)[S]) {
                     double t = fRow[0] + curM[kR];
                     const int x = xlo + k, y = d2 - x;
-                    const float fbf = (x > 0 && y > 0) ? (float)t : -__builtin_huge_valf();
+                    if (CANDS && x > 0 && y > 0) laneMax = fmaxf(laneMax, (float)t);
 #pragma unroll
                     for (int s2 = 1; s2 < S; s2++) t = logadd(lg, t, fRow[s2] + curG[s2 + kR]);
                     cbuf[(size_t)k * J + jr] = t;
-                    return fbf;
                 };
 #pragma unroll
                 for (int q = 0; q < kPrefetch; q++) {
                     const int k = q * CPK_WAVE + lane;
-                    float fbf = -__builtin_huge_valf();
-                    if (q * CPK_WAVE < W) {  // wave-uniform
-                        if (k < W) {
-                            double fRow[S];
+                    if (k < W) {
+                        double fRow[S];
 #pragma unroll
-                            for (int s2 = 0; s2 < S; s2++) fRow[s2] = s2 < NL ? fmCur[s2][q] : rfC[s2][q];
-                            fbf = dotCell(k, q * CPK_WAVE * R + laneR, fRow);
-                        }
-                        if (CANDS) diagMax = fmaxf(diagMax, wave_max_f32(fbf));
+                        for (int s2 = 0; s2 < S; s2++) fRow[s2] = s2 < NL ? fmCur[s2][q] : rfC[s2][q];
+                        dotCell(k, q * CPK_WAVE * R + laneR, fRow);
                     }
                 }
                 for (int kb = kPrefetch * CPK_WAVE; kb < W; kb += CPK_WAVE) {  // diagonals wider than the prefetch
                     const int k = kb + lane;
-                    float fbf = -__builtin_huge_valf();
                     if (k < W) {
                         double fRow[S];
 #pragma unroll
                         for (int s2 = 0; s2 < S; s2++) fRow[s2] = ringLd(fsrc + ringIdx(W, s2, k));
-                        fbf = dotCell(k, kb * R + laneR, fRow);
+                        dotCell(k, kb * R + laneR, fRow);
                     }
-                    if (CANDS) diagMax = fmaxf(diagMax, wave_max_f32(fbf));
                 }
-                if (CANDS) lastMax = fmaxf(diagMax, lastMax - 1.0f);
+                if (CANDS) lastMax = fmaxf(wave_max_f32(laneMax), lastMax - 1.0f);
             }
             // slide the window of table entries and prefetched F rows down one diagonal
             ga = gb;
@@ -1118,52 +1114,86 @@ struct Sweep {
             for (int l = 0; l < (CANDS ? NL : 0); l++)
                 if (pend[l] >= kStageAbs / 2) flush(l);
         };
-        auto dotCell = [&](const AbsDiag &cx, int k, const double (&fRow)[S], double &t) {
-            const int kR = cx.ownR + k * R;
-            t = fRow[0] + cx.cur[kR];
-            const int x = cx.xlo + k, y = cx.d - x;
-            const float fbf = (x > 0 && y > 0) ? (float)t : -__builtin_huge_valf();
+        // The n groups of a refresh diagonal that the prefetch covers (n wave-uniform, 1..kPrefetch) advance TOGETHER: F and the
+        // S backward states of all of them are gathered first -- B through lds1(): plain loads pair up into ds_read2_b64, four
+        // times the LDS cycles per byte --, then the fold goes state by state with the n table fetches of a step in flight
+        // at once (logadd_n).  Per cell the sequence is what it was, t = F0 + B0; t = logAdd(t, Fs + Bs) for s = 1..S-1.  A
+        // lane without a cell computes cell 0 of the diagonal, as the lanes of a cell group that are not `on` compute a
+        // cell in the band: no divergent branch, and its value is never stored.  (One group after another, each behind its own
+        // branch, was four dependent logAdds with nothing else in flight, three times per refresh point.)
+        // laneMax: running maximum of the lane's F.m + B.m, reduced over the wave ONCE per refresh point by the caller.
+        auto dotGroups = [&](auto nTag, const AbsDiag &cx, int W, int off, const double (&fm)[NL][kPrefetch],
+                             const double (&rfC)[S][kPrefetch], float &laneMax) {
+            constexpr int n = decltype(nTag)::value;
+            double acc[n], b[S][n];
+            bool cell[n];
 #pragma unroll
-            for (int s2 = 1; s2 < S; s2++) t = logadd(lg, t, fRow[s2] + cx.cur[s2 + kR]);
-            return fbf;
+            for (int q = 0; q < n; q++) {
+                const int k = q * CPK_WAVE - off + lane;
+                const bool in = (unsigned)k < (unsigned)W;
+                // (lane * R is a member; k * R would be a multiply per lane that hipcc computes once per kernel and keeps)
+                const double *row = cx.cur + cx.ownR + (in ? (q * CPK_WAVE - off) * R + laneR : 0);
+#ifdef CPK_TIMING_NO_PASSES  // timing experiment: of the pass only the candidate bound is left -- results invalid
+                constexpr int nS = 1;
+#else
+                constexpr int nS = S;
+#endif
+#pragma unroll
+                for (int s2 = 0; s2 < nS; s2++) b[s2][q] = lds1(row + s2);
+                const int x = cx.xlo + k, y = cx.d - x;
+                cell[q] = in && x > 0 && y > 0;
+            }
+#pragma unroll
+            for (int q = 0; q < n; q++) {
+                acc[q] = fm[0][q] + b[0][q];
+                if (CANDS) laneMax = fmaxf(laneMax, cell[q] ? (float)acc[q] : -__builtin_huge_valf());
+            }
+#ifndef CPK_TIMING_NO_PASSES
+#pragma unroll
+            for (int s2 = 1; s2 < S; s2++) {
+                double t[n];
+#pragma unroll
+                for (int q = 0; q < n; q++) t[q] = (s2 < NL ? fm[s2 < NL ? s2 : 0][q] : rfC[s2][q]) + b[s2][q];
+                logadd_n<n>(lg, acc, t);
+            }
+#pragma unroll
+            for (int q = 0; q < n; q++) pendC[q] = acc[q];
+#endif
         };
         auto refreshDots = [&](const AbsDiag &cx, const CpkDiag &g, int off, int jr, const double (&fm)[NL][kPrefetch],
                                const double (&rfC)[S][kPrefetch]) {
+            static_assert(kPrefetch == 3, "one lock-step form per number of prefetched groups");
             const int W = g.width;
             const double *fsrc = ringAt(g);
-            float diagMax = -__builtin_huge_valf();
-#pragma unroll
-            for (int q = 0; q < kPrefetch; q++) {
-                const int k = q * CPK_WAVE - off + lane;
-                float fbf = -__builtin_huge_valf();
-                if (q * CPK_WAVE - off < W) {  // wave-uniform
-                    if ((unsigned)k < (unsigned)W) {
-                        double fRow[S];
-#pragma unroll
-                        for (int s2 = 0; s2 < S; s2++) fRow[s2] = s2 < NL ? fm[s2][q] : rfC[s2][q];
-                        fbf = dotCell(cx, k, fRow, pendC[q]);
-                    }
-                    if (CANDS) diagMax = fmaxf(diagMax, wave_max_f32(fbf));
-                }
-            }
+            float laneMax = -__builtin_huge_valf();
+            const int nG = (off + W + CPK_WAVE - 1) >> 6;  // groups the diagonal's cells lie in (wave-uniform, >= 1)
+            if (nG >= 3) dotGroups(std::integral_constant<int, 3>{}, cx, W, off, fm, rfC, laneMax);
+            else if (nG == 2) dotGroups(std::integral_constant<int, 2>{}, cx, W, off, fm, rfC, laneMax);
+            else dotGroups(std::integral_constant<int, 1>{}, cx, W, off, fm, rfC, laneMax);
             for (int kb = kPrefetch * CPK_WAVE - off; kb < W; kb += CPK_WAVE) {  // diagonals wider than the prefetch
                 const int k = kb + lane;
-                float fbf = -__builtin_huge_valf();
                 if (k < W) {
-                    double fRow[S];
+                    const double *row = cx.cur + cx.ownR + k * R;
+                    double fRow[S], b[S];
 #pragma unroll
                     for (int s2 = 0; s2 < S; s2++) fRow[s2] = ringLd(fsrc + ringIdx(W, s2, k));
-                    double tk;
-                    fbf = dotCell(cx, k, fRow, tk);
-                    cbuf[(size_t)k * J + jr] = tk;
+#pragma unroll
+                    for (int s2 = 0; s2 < S; s2++) b[s2] = lds1(row + s2);
+                    double t = fRow[0] + b[0];
+                    const int x = cx.xlo + k, y = cx.d - x;
+                    if (CANDS && x > 0 && y > 0) laneMax = fmaxf(laneMax, (float)t);
+#pragma unroll
+                    for (int s2 = 1; s2 < S; s2++) t = logadd(lg, t, fRow[s2] + b[s2]);
+                    cbuf[(size_t)k * J + jr] = t;
                 }
-                if (CANDS) diagMax = fmaxf(diagMax, wave_max_f32(fbf));
             }
+#ifndef CPK_TIMING_NO_PASSES
             pendCW = W;
             pendCOff = off;
             pendCj = jr;
+#endif
             if (CANDS) {
-                lastMax = fmaxf(diagMax, lastMax - 1.0f);
+                lastMax = fmaxf(wave_max_f32(laneMax), lastMax - 1.0f);
                 keepFrom = (double)(lastMax + logThr - kCandMargin);
             }
         };
@@ -1215,8 +1245,12 @@ struct Sweep {
 #pragma unroll
                     for (int l = 0; l < NL; l++) fm[l][q] = ringLd(fsrc + ringIdx(W, l, k < W ? k : W - 1));
                 }
-                loadRefreshRows(g, 0, rfC);
-                refreshDots(cx, g, 0, jr, fm, rfC);
+                // (the first lane is 0 here, and hipcc must not know: with a constant it computes the per-lane byte offsets of
+                // the rows once per KERNEL and keeps them -- in scratch, these kernels have no register to spare)
+                int off0 = 0;
+                asm volatile("" : "+s"(off0));
+                loadRefreshRows(g, off0, rfC);
+                refreshDots(cx, g, off0, jr, fm, rfC);
                 issueStores();
                 untilRefresh = CPK_REFRESH_PERIOD - 1;
                 jr++;
@@ -1356,8 +1390,9 @@ struct Sweep {
                 for (int l = 0; l < NL; l++) f0[l] = ringLd(ringAt(g) + ringIdx(W, l, on ? k0 : W - 1));
                 group(cx, on ? k0 : W - 1, on ? cx.ownR + kb * R + laneR : cx.ownR + (W - 1) * R, on, f0, g.cellOff);
             }
-#ifdef CPK_TIMING_NO_PASSES  // timing experiment: neither the straddle series nor the dot products
-            if ((feeds || refresh) && a.geo.maxWidth < 0) {
+#ifdef CPK_TIMING_NO_PASSES  // timing experiment: neither the straddle series nor the dot products; the candidate bound of a
+                             // refresh point stays (dotGroups) -- without it every cell of the segment is a candidate
+            if (refresh || (feeds && a.geo.maxWidth < 0)) {
 #else
             if (feeds || refresh) {  // one diagonal in five: all its cells are done (no tail waits), a pass of its own follows
 #endif
