@@ -2471,11 +2471,43 @@ static int take_list(const int32_t *src, int64_t n, int32_t **out, int64_t *nOut
     return CPECAN_OK;
 }
 
+/* The reweighting kernel keeps PROB_1 minus the listed mass of a base in an int32 (cpecan_post_reweight), the reference in
+ * an int64 (impl/pairwiseAligner.c:1519-1534).  The two agree while that difference fits: the listed mass of every row
+ * and every column must lie in [PROB_1 - INT32_MAX, PROB_1 - INT32_MIN] = [-2137483647, 2157483648], about 215 pairs of
+ * probability one on one base.  A posterior list stays below 1 x PROB_1 (+ rounding); a list beyond the bound is refused
+ * here, before a device is looked for ("The list consumers"). */
+static int reweight_mass_fits(const int32_t *triples, int64_t n, int64_t lX, int64_t lY) {
+    if (n < 0 || lX < 0 || lY < 0 || lX + lY >= (int64_t)1 << 30 || (n > 0 && !triples)) return CPECAN_EINVAL;
+    int64_t *mass = calloc((size_t)(lX + lY ? lX + lY : 1), sizeof(int64_t));
+    if (!mass) return CPECAN_ENOMEM;
+    int rc = CPECAN_OK;
+    for (int64_t i = 0; i < n && rc == CPECAN_OK; i++) {
+        const int64_t x = triples[3 * i + 1], y = triples[3 * i + 2];
+        if (x < 0 || x >= lX || y < 0 || y >= lY) {
+            rc = CPECAN_EINVAL;
+        } else {
+            mass[x] += triples[3 * i];
+            mass[lX + y] += triples[3 * i];
+        }
+    }
+    for (int64_t i = 0; i < lX + lY && rc == CPECAN_OK; i++)
+        if (mass[i] < (int64_t)CPECAN_PROB_1 - INT32_MAX || mass[i] > (int64_t)CPECAN_PROB_1 - INT32_MIN) {
+            cpk_set_error("reweightAlignedPairs2: base %lld of %s lists a mass of %lld, outside [%lld, %lld]",
+                          (long long)(i < lX ? i : i - lX), i < lX ? "X" : "Y", (long long)mass[i],
+                          (long long)CPECAN_PROB_1 - INT32_MAX, (long long)CPECAN_PROB_1 - INT32_MIN);
+            rc = CPECAN_EINVAL;
+        }
+    free(mass);
+    return rc;
+}
+
 int cpecan_reweight_aligned_pairs(int32_t *triples, int64_t n, int64_t lX, int64_t lY, double gapGamma) {
     const int32_t *lists[3] = {triples, NULL, NULL};
     const int64_t ns[3] = {n, 0, 0};
     PostSingle ps;
-    int rc = post_single_run(&ps, CPECAN_POST_REWEIGHT, gapGamma, 0.0, lists, ns, lX, lY, NULL, NULL);
+    int rc = gapGamma > 0.0 ? reweight_mass_fits(triples, n, lX, lY) : CPECAN_OK; /* (:1551: no mass is formed otherwise) */
+    if (rc != CPECAN_OK) return rc;
+    rc = post_single_run(&ps, CPECAN_POST_REWEIGHT, gapGamma, 0.0, lists, ns, lX, lY, NULL, NULL);
     if (rc == CPECAN_OK && n) memcpy(triples, ps.buf, sizeof(int32_t) * 3 * (size_t)n);
     post_single_free(&ps);
     return rc;
@@ -2510,9 +2542,41 @@ int cpecan_identity_scores(const int32_t *triples, int64_t n, const char *sX, co
     return rc;
 }
 
+static int cmp_cell(const void *a, const void *b) {
+    const int64_t u = *(const int64_t *)a, v = *(const int64_t *)b;
+    return u < v ? -1 : (u > v ? 1 : 0);
+}
+
+/* A list that names one cell (x, y) twice is refused.  The reference keeps the weights of an X column in a set sorted by
+ * Y position (impl/multipleAligner.c:121-131), so which copy's weight the chain sees is the set's insertion rule, and
+ * filterMultipleAlignedPairs (:569-601) then keeps EVERY listed pair of a chosen cell, the copies under matchGamma
+ * included; the oracle keeps the copy with the lower index and the kernels the one with the higher.  No emitter lists a
+ * cell twice.  Checked here, before a device is looked for ("The list consumers"). */
+static int cells_are_distinct(const int32_t *pairs, int64_t n) {
+    if (n < 2) return CPECAN_OK;
+    int64_t *cells = malloc(sizeof(int64_t) * (size_t)n);
+    if (!cells) return CPECAN_ENOMEM;
+    for (int64_t i = 0; i < n; i++) cells[i] = (int64_t)pairs[3 * i + 1] * ((int64_t)1 << 32) + (uint32_t)pairs[3 * i + 2];
+    qsort(cells, (size_t)n, sizeof(int64_t), cmp_cell);
+    int rc = CPECAN_OK;
+    for (int64_t i = 1; i < n && rc == CPECAN_OK; i++)
+        if (cells[i] == cells[i - 1]) {
+            cpk_set_error("filterPairwiseAlignmentToMakePairsOrdered: cell (%lld, %lld) is listed more than once",
+                          (long long)(cells[i] >> 32), (long long)(int32_t)(uint32_t)cells[i]);
+            rc = CPECAN_EINVAL;
+        }
+    free(cells);
+    return rc;
+}
+
 int cpecan_filter_pairs_ordered(const int32_t *pairs, int64_t n, int64_t lX, int64_t lY, float matchGamma, int32_t **out,
                                 int64_t *nOut) {
     if (!out || !nOut || !(matchGamma >= 0.0f)) return CPECAN_EINVAL;
+    if (n < 0 || n >= (int64_t)1 << 30 || (n > 0 && !pairs)) return CPECAN_EINVAL;
+    {
+        const int distinct = cells_are_distinct(pairs, n);
+        if (distinct != CPECAN_OK) return distinct;
+    }
     const int32_t *lists[3] = {pairs, NULL, NULL};
     const int64_t ns[3] = {n, 0, 0};
     PostSingle ps;

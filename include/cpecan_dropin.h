@@ -195,14 +195,17 @@ void getExpectations(StateMachine *sM, Hmm *hmmExpectations, const char *sX, con
                      bool alignmentHasRaggedLeftEnd, bool alignmentHasRaggedRightEnd);
 
 /* Consumers of the posterior lists, evaluated on the GPU (inc/pairwiseAligner.h:86-98, :272-290;
- * impl/pairwiseAligner.c:1519-1790).  reweightAlignedPairs2 consumes its input list unless gapGamma <= 0. */
+ * impl/pairwiseAligner.c:1519-1790).  reweightAlignedPairs2 consumes its input list unless gapGamma <= 0; the scores
+ * listed for one base must stay within about +-215 x PAIR_ALIGNMENT_PROB_1 (cpecan_reweight_aligned_pairs), else the call
+ * fails like any other error of this layer. */
 stList *reweightAlignedPairs2(stList *alignedPairs, int64_t seqLengthX, int64_t seqLengthY, double gapGamma);
 double scoreByPosteriorProbability(int64_t lX, int64_t lY, stList *alignedPairs);
 double scoreByPosteriorProbabilityIgnoringGaps(stList *alignedPairs);
 double scoreByIdentity(char *subSeqX, char *subSeqY, int64_t lX, int64_t lY, stList *alignedPairs);
 double scoreByIdentityIgnoringGaps(char *subSeqX, char *subSeqY, stList *alignedPairs);
 /* inc/multipleAligner.h (impl/multipleAligner.c:945): consumes its input list.  The reference perturbs every weight by
- * st_random() * 0.00001 before comparing (multipleAligner.c:145); this one does not. */
+ * st_random() * 0.00001 before comparing (multipleAligner.c:145); this one does not, and it refuses a list that names
+ * one cell (x, y) twice (cpecan_filter_pairs_ordered). */
 stList *filterPairwiseAlignmentToMakePairsOrdered(stList *alignedPairs, const char *seqX, const char *seqY, float matchGamma);
 stList *getMaximalExpectedAccuracyPairwiseAlignment(stList *alignedPairs, stList *gapXPairs, stList *gapYPairs,
                                                     int64_t seqXLength, int64_t seqYLength, double *alignmentScore,

@@ -530,7 +530,9 @@ int cpecan_compute_forward_probability(const cpecan_model *m, const char *sX, co
                                        int64_t nAnchors, const cpecan_params *p, int raggedLeft, int raggedRight,
                                        double *logProb);
 /* ---- the consumers on lists held by the caller (one problem; uploaded, processed on the GPU, copied back) ---- */
-/* reweightAlignedPairs2 (:1550): triples (score, x, y) rewritten in place. */
+/* reweightAlignedPairs2 (:1550): triples (score, x, y) rewritten in place.  With gapGamma > 0 the scores listed for one
+ * base of X or of Y must add up to a value in [CPECAN_PROB_1 - INT32_MAX, CPECAN_PROB_1 - INT32_MIN] (about +-215 pairs of
+ * probability one; a posterior list stays near 1): CPECAN_EINVAL otherwise, the device keeps that mass in 32 bits. */
 int cpecan_reweight_aligned_pairs(int32_t *triples, int64_t n, int64_t lX, int64_t lY, double gapGamma);
 /* scoreByPosteriorProbability / ...IgnoringGaps (:1587-1597). */
 int cpecan_posterior_scores(const int32_t *triples, int64_t n, int64_t lX, int64_t lY, double *byPosterior,
@@ -539,7 +541,8 @@ int cpecan_posterior_scores(const int32_t *triples, int64_t n, int64_t lX, int64
 int cpecan_identity_scores(const int32_t *triples, int64_t n, const char *sX, const char *sY, double *byIdentity,
                            double *byIdentityIgnoringGaps);
 /* filterPairwiseAlignmentToMakePairsOrdered (impl/multipleAligner.c:945), without the reference's random jitter (see
- * CPECAN_POST_ORDERED); the pairs must be distinct cells; *out is malloc'd (cpecan_free). */
+ * CPECAN_POST_ORDERED); the pairs must be distinct cells -- a list that names a cell twice is refused with
+ * CPECAN_EINVAL; *out is malloc'd (cpecan_free). */
 int cpecan_filter_pairs_ordered(const int32_t *pairs, int64_t n, int64_t lX, int64_t lY, float matchGamma, int32_t **out,
                                 int64_t *nOut);
 /* getMaximalExpectedAccuracyPairwiseAlignment (:1628): *out is malloc'd (cpecan_free). */

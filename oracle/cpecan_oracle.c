@@ -990,8 +990,12 @@ static int64_t gap_mass(const int64_t *cum, int64_t start, int64_t length) {
     return length == 0 ? 0 : cum[start + length - 1] - (start > 0 ? cum[start - 1] : 0);
 }
 
-int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, int64_t nGapX, const int64_t *gapY,
-                          int64_t nGapY, int64_t lX, int64_t lY, float gapGamma, int64_t *out, double *alignmentScore) {
+/* trVisited / trEnded / trPrev / trRecord (n + 1 entries each, the sentinel last; NULL: no trace): how many earlier pairs
+ * the walk back of pair i looked at, whether it ended on a dominated record (1) or ran off the front of the list (0), the
+ * predecessor it chose and whether the pair set a record. */
+static int64_t mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, int64_t nGapX, const int64_t *gapY,
+                             int64_t nGapY, int64_t lX, int64_t lY, float gapGamma, int64_t *out, double *alignmentScore,
+                             int64_t *trVisited, int64_t *trEnded, int64_t *trPrev, int64_t *trRecord) {
     double *best = calloc((size_t)n + 1, sizeof(double));   /* score of the best chain ending at pair i */
     int64_t *prev = calloc((size_t)n + 1, sizeof(int64_t)); /* its predecessor */
     char *record = calloc((size_t)n + 1, 1);                /* chain score incl. trailing gaps is a running maximum */
@@ -1010,9 +1014,10 @@ int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, 
         }
         /* :1660-1661: int64 + (int64 * float): the product and the sum are float arithmetic */
         double score = w + (gap_mass(cx, 0, x) + gap_mass(cy, 0, y)) * gapGamma;
-        int64_t from = -1;
+        int64_t from = -1, visited = 0, ended = 0;
         for (int64_t j = i - 1; j >= 0; j--) {
             const int64_t x2 = pairs[3 * j + 1], y2 = pairs[3 * j + 2];
+            visited++;
             if (x2 < x && y2 < y) {
                 /* :1673-1675: (int64 + double) + float product, truncated to int64 */
                 const int64_t s = w + best[j] + (gap_mass(cx, x2 + 1, x - x2 - 1) + gap_mass(cy, y2 + 1, y - y2 - 1)) * gapGamma;
@@ -1020,9 +1025,14 @@ int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, 
                     score = s;
                     from = j;
                 }
-                if (record[j]) break; /* :1685: nothing further back can do better */
+                if (record[j]) { /* :1685: nothing further back can do better */
+                    ended = 1;
+                    break;
+                }
             }
         }
+        if (trVisited) trVisited[i] = visited;
+        if (trEnded) trEnded[i] = ended;
         prev[i] = from;
         best[i] = score;
         /* :1695-1696 */
@@ -1031,6 +1041,10 @@ int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, 
             top = s;
             record[i] = 1;
         }
+    }
+    for (int64_t i = 0; i <= n; i++) {
+        if (trPrev) trPrev[i] = prev[i];
+        if (trRecord) trRecord[i] = record[i];
     }
     int64_t count = 0;
     for (int64_t i = prev[n]; i >= 0; i = prev[i]) count++;
@@ -1048,6 +1062,18 @@ int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, 
     free(cy);
     if (alignmentScore) *alignmentScore = top;
     return count;
+}
+
+int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, int64_t nGapX, const int64_t *gapY,
+                          int64_t nGapY, int64_t lX, int64_t lY, float gapGamma, int64_t *out, double *alignmentScore) {
+    return mea_alignment(pairs, n, gapX, nGapX, gapY, nGapY, lX, lY, gapGamma, out, alignmentScore, NULL, NULL, NULL, NULL);
+}
+
+int64_t orc_mea_alignment_traced(const int64_t *pairs, int64_t n, const int64_t *gapX, int64_t nGapX, const int64_t *gapY,
+                                 int64_t nGapY, int64_t lX, int64_t lY, float gapGamma, int64_t *out, double *alignmentScore,
+                                 int64_t *visited, int64_t *ended, int64_t *prev, int64_t *record) {
+    return mea_alignment(pairs, n, gapX, nGapX, gapY, nGapY, lX, lY, gapGamma, out, alignmentScore, visited, ended, prev,
+                         record);
 }
 
 static int up(char c) { return toupper((unsigned char)c); }
@@ -1131,7 +1157,12 @@ static int cmp_pair_by_xy(const void *a, const void *b) {
     return i < j ? -1 : (i > j ? 1 : 0);
 }
 
-int64_t orc_filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, int64_t lY, double matchGamma, int64_t *out) {
+/* trPred / trQuery / trDropped (n entries each; NULL: no trace), per pair: the predecessor (-1 none, -3: the pair does not
+ * take part); whether its predecessor was the frontier's last entry, or the frontier was empty (1), or an entry inside
+ * it (0); and what its insertion did: -1 redundant, else the number of entries it replaced (0: room was made for it),
+ * plus 1000000 when it went in behind every other entry, i.e. extended the frontier.  *trM: the pairs that take part. */
+static int64_t filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, int64_t lY, double matchGamma, int64_t *out,
+                                    int64_t *trM, int64_t *trPred, int64_t *trQuery, int64_t *trDropped) {
     /* With two sequences every column holds one base, every weight links one X base to one Y base with
      * numberOfWeights == 1 (multipleAligner.c:140-147), both sequences carry the same number of weights so X stays X
      * (:361-367), and getMultipleSequenceAlignmentProgressive makes the single call of pairwiseAlignColumns (:358-492)
@@ -1161,7 +1192,11 @@ int64_t orc_filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, in
                 while (f[at + 1].y < pairs[3 * i + 2]) at++;
                 pred[i] = f[at].pair;
                 score[i] = f[at].score + w * 1.0;
+                if (trQuery) trQuery[i] = at == nf - 2;
+                if (trM) (*trM)++;
             }
+            if (trPred) trPred[i] = pred[i];
+            if (trDropped) trDropped[i] = -1;
         }
         /* ... and then put into the frontier from the right (:412-433) */
         for (int64_t k = b - 1; k >= a; k--) {
@@ -1173,6 +1208,7 @@ int64_t orc_filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, in
             if (score[i] >= f[at].score || f[at].y > y) {
                 int64_t end = at;
                 while (score[i] >= f[end].score) end++; /* entries at or right of y that score no better */
+                if (trDropped) trDropped[i] = end - at + (end == nf - 1 ? 1000000 : 0);
                 if (end == at) { /* make room */
                     memmove(&f[at + 1], &f[at], sizeof(FrontierEntry) * (size_t)(nf - at));
                     nf++;
@@ -1203,6 +1239,16 @@ int64_t orc_filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, in
     free(chosen);
     free(f);
     return count;
+}
+
+int64_t orc_filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, int64_t lY, double matchGamma, int64_t *out) {
+    return filter_pairs_ordered(pairs, n, lX, lY, matchGamma, out, NULL, NULL, NULL, NULL);
+}
+
+int64_t orc_filter_pairs_ordered_traced(const int64_t *pairs, int64_t n, int64_t lX, int64_t lY, double matchGamma,
+                                        int64_t *out, int64_t *m, int64_t *pred, int64_t *query, int64_t *dropped) {
+    *m = 0;
+    return filter_pairs_ordered(pairs, n, lX, lY, matchGamma, out, m, pred, query, dropped);
 }
 
 /* filterToRemoveOverlap, impl/pairwiseAligner.c:1095-1135: pairs sorted by (x, y, expansion); a pair survives when it is

@@ -174,6 +174,12 @@ double orc_score_by_posterior_ignoring_gaps(const int64_t *triples, int64_t n);
  * returns the number written. */
 int64_t orc_mea_alignment(const int64_t *pairs, int64_t n, const int64_t *gapX, int64_t nGapX, const int64_t *gapY,
                           int64_t nGapY, int64_t lX, int64_t lY, float gapGamma, int64_t *out, double *alignmentScore);
+/* The same with a trace of the chain, n + 1 entries per array (the sentinel last): how many earlier pairs the walk back of
+ * a pair looked at, whether it ended on a dominated record (1) or ran off the front of the list (0), the predecessor, and
+ * whether the pair set a record.  For tests that construct a walk of a chosen length. */
+int64_t orc_mea_alignment_traced(const int64_t *pairs, int64_t n, const int64_t *gapX, int64_t nGapX, const int64_t *gapY,
+                                 int64_t nGapY, int64_t lX, int64_t lY, float gapGamma, int64_t *out, double *alignmentScore,
+                                 int64_t *visited, int64_t *ended, int64_t *prev, int64_t *record);
 /* leftShiftAlignment, :1726-1762.  out holds n + min(lX, lY) + 1 triples; returns the number written. */
 int64_t orc_left_shift_alignment(const int64_t *pairs, int64_t n, const char *sX, const char *sY, int64_t *out);
 /* scoreByIdentity / scoreByIdentityIgnoringGaps, :1562-1580 */
@@ -184,8 +190,17 @@ double orc_score_by_identity_ignoring_gaps(const char *sX, const char *sY, const
  * the survivors come out in reverse input order.  The reference adds st_random() * 0.00001 to every weight (:145), so
  * its own output is not a function of its input; this restatement leaves the jitter out -- PARITY UNPINNED (the
  * reference's test of pairwiseAlignColumns, tests/multipleAlignerTest.c, checks properties only, which the tests here
- * repeat).  The pairs must be distinct cells.  out holds n triples; returns the number written. */
+ * repeat; tests/ordered_model.py states the same rule without a frontier and tests/test_consumer_cases_cpu.py holds
+ * this function to it list for list).  The pairs must be distinct cells: of two copies this function keeps the one
+ * with the lower index, the reference would return both, and the library refuses the list.  out holds n triples;
+ * returns the number written. */
 int64_t orc_filter_pairs_ordered(const int64_t *pairs, int64_t n, int64_t lX, int64_t lY, double matchGamma, int64_t *out);
+/* The same with a trace, n entries per array: *m the pairs that take part; per pair its predecessor (-1 none, -3 the pair
+ * does not take part), whether the predecessor was the frontier's last entry or the frontier empty (1) or an entry inside
+ * it (0), and what its insertion did: -1 redundant, else the number of entries it replaced (0: room was made), plus
+ * 1000000 when it went in behind every other entry (it extended the frontier). */
+int64_t orc_filter_pairs_ordered_traced(const int64_t *pairs, int64_t n, int64_t lX, int64_t lY, double matchGamma,
+                                        int64_t *out, int64_t *m, int64_t *pred, int64_t *query, int64_t *dropped);
 /* filterToRemoveOverlap, impl/pairwiseAligner.c:1095-1135 (input sorted by x, then y); out holds n triples */
 int64_t orc_filter_to_remove_overlap(const int64_t *pairs, int64_t n, int64_t *out);
 

@@ -131,6 +131,10 @@ def lib():
         L.orc_score_by_identity_ignoring_gaps.argtypes = [C.c_char_p, C.c_char_p, i64p, C.c_int64]
         L.orc_filter_pairs_ordered.restype = C.c_int64
         L.orc_filter_pairs_ordered.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int64, C.c_double, i64p]
+        L.orc_mea_alignment_traced.restype = C.c_int64
+        L.orc_mea_alignment_traced.argtypes = L.orc_mea_alignment.argtypes + [i64p] * 4
+        L.orc_filter_pairs_ordered_traced.restype = C.c_int64
+        L.orc_filter_pairs_ordered_traced.argtypes = L.orc_filter_pairs_ordered.argtypes + [i64p] * 4
         L.orc_filter_to_remove_overlap.restype = C.c_int64
         L.orc_filter_to_remove_overlap.argtypes = [i64p, C.c_int64, i64p]
         L.orc_trace_free.argtypes = [C.POINTER(Trace)]
@@ -381,6 +385,40 @@ def filter_pairs_ordered(pairs, lX, lY, match_gamma):
     cnt = lib().orc_filter_pairs_ordered(pa, n, lX, lY, float(np.float32(match_gamma)),
                                          out.ctypes.data_as(C.POINTER(C.c_int64)))
     return out[:cnt].copy()
+
+
+def mea_alignment_traced(pairs, gap_x, gap_y, lX, lY, gap_gamma):
+    """(alignment, alignmentScore, trace): trace holds int64[n + 1] arrays (the sentinel last) -- `visited`, the earlier
+    pairs the walk back looked at; `ended`, 1 when it stopped on a dominated record, 0 when it ran off the front;
+    `prev`; `record`."""
+    a, pa, n = _triples(pairs)
+    gx, pgx, ngx = _triples(gap_x)
+    gy, pgy, ngy = _triples(gap_y)
+    out = np.zeros((max(n, 1), 3), dtype=np.int64)
+    score = C.c_double()
+    tr = {k: np.zeros(n + 1, dtype=np.int64) for k in ("visited", "ended", "prev", "record")}
+    cnt = lib().orc_mea_alignment_traced(pa, n, pgx, ngx, pgy, ngy, lX, lY, C.c_float(gap_gamma),
+                                         out.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(score),
+                                         *[tr[k].ctypes.data_as(C.POINTER(C.c_int64)) for k in ("visited", "ended", "prev", "record")])
+    return out[:cnt].copy(), score.value, tr
+
+
+def filter_pairs_ordered_traced(pairs, lX, lY, match_gamma):
+    """(list, trace): trace holds `m`, the pairs that take part, and int64[n] arrays -- `pred` (-1 none, -3 takes no part),
+    `query` (1: the predecessor was the frontier's last entry, or the frontier empty), `dropped` (-1 redundant, else the
+    entries replaced) and `extended` (1: inserted behind every other entry)."""
+    a, pa, n = _triples(pairs)
+    out = np.zeros((max(n, 1), 3), dtype=np.int64)
+    m = C.c_int64()
+    tr = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("pred", "query", "dropped")}
+    cnt = lib().orc_filter_pairs_ordered_traced(pa, n, lX, lY, float(np.float32(match_gamma)),
+                                                out.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(m),
+                                                *[tr[k].ctypes.data_as(C.POINTER(C.c_int64)) for k in ("pred", "query", "dropped")])
+    tr = {k: v[:n] for k, v in tr.items()}
+    tr["extended"] = (tr["dropped"] >= 1000000).astype(np.int64)
+    tr["dropped"] = np.where(tr["dropped"] >= 1000000, tr["dropped"] - 1000000, tr["dropped"])
+    tr["m"] = m.value
+    return out[:cnt].copy(), tr
 
 
 def filter_to_remove_overlap(pairs):
