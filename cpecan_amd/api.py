@@ -302,6 +302,8 @@ def lib():
     L.cpecan_batch_band_edge.argtypes = [vp, C.c_int64, C.POINTER(BandEdge)]
     L.cpecan_band_edge_of_pairs.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(PairwiseAlignmentParameters), C.c_int,
                                             C.c_int, i32p, C.c_int64, C.POINTER(BandEdge)]
+    L.cpecan_similarity_score.restype = C.c_int64  # include/cpecan_sets.h; the rest of that header is bound by sets.py
+    L.cpecan_similarity_score.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     _lib = L
     return L
 
@@ -950,6 +952,11 @@ def reweightAlignedPairs2(alignedPairs, seqLengthX, seqLengthY, gapGamma):  # im
     _check(lib().cpecan_reweight_aligned_pairs(a.ctypes.data_as(C.POINTER(C.c_int32)), n, seqLengthX, seqLengthY,
                                                float(gapGamma)), "cpecan_reweight_aligned_pairs")
     return a
+
+
+def similarity_score(scoreSum, lX, lY):  # getAlignmentScore, impl/multipleAligner.c:613-618
+    """cpecan_similarity_score (include/cpecan_sets.h): the similarity of a pair from the integer sum of its scores; pure."""
+    return _check(lib().cpecan_similarity_score(int(scoreSum), int(lX), int(lY)), "cpecan_similarity_score")
 
 
 def _posterior_scores(alignedPairs, lX, lY):

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "cpecan_dropin.h"
+#include "cpecan_sets.h"
 
 static void die(const char *fmt, ...) {
     va_list ap;
@@ -28,7 +29,7 @@ struct _stList {
 };
 struct _stIntTuple {
     int64_t length;
-    int64_t v[4];
+    int64_t v[5];
 };
 #define WEAK __attribute__((weak))
 
@@ -64,7 +65,7 @@ WEAK stIntTuple *stIntTuple_construct3(int64_t a, int64_t b, int64_t c) {
     stIntTuple *t = malloc(sizeof *t);
     if (!t) die("out of memory");
     t->length = 3;
-    t->v[0] = a; t->v[1] = b; t->v[2] = c; t->v[3] = 0;
+    t->v[0] = a; t->v[1] = b; t->v[2] = c; t->v[3] = t->v[4] = 0;
     return t;
 }
 WEAK stIntTuple *stIntTuple_construct2(int64_t a, int64_t b) {
@@ -76,6 +77,12 @@ static stIntTuple *tuple4(int64_t a, int64_t b, int64_t c, int64_t d) {
     stIntTuple *t = stIntTuple_construct3(a, b, c);
     t->length = 4;
     t->v[3] = d;
+    return t;
+}
+WEAK stIntTuple *stIntTuple_construct5(int64_t a, int64_t b, int64_t c, int64_t d, int64_t e) {
+    stIntTuple *t = tuple4(a, b, c, d);
+    t->length = 5;
+    t->v[4] = e;
     return t;
 }
 WEAK void stIntTuple_destruct(stIntTuple *t) { free(t); }
@@ -567,6 +574,62 @@ stList *getBlastPairsForPairwiseAlignmentParameters(const char *sX, const char *
     cpecan_free(runs);
     return l;
 }
+/* ---------------- the pairwise stage of the multiple aligner: impl/multipleAligner.c:653-681, :976-990 ---------------- */
+SeqFrag *seqFrag_construct(const char *seq, int64_t leftEndId, int64_t rightEndId) {
+    SeqFrag *f = malloc(sizeof *f);
+    const size_t l = strlen(seq);
+    if (!f || !(f->seq = malloc(l + 1))) die("out of memory");
+    memcpy(f->seq, seq, l + 1);
+    f->length = (int64_t)l;
+    f->leftEndId = leftEndId;
+    f->rightEndId = rightEndId;
+    return f;
+}
+void seqFrag_destruct(SeqFrag *seqFrag) {
+    free(seqFrag->seq);
+    free(seqFrag);
+}
+stList *makeAllPairwiseAlignments(StateMachine *sM, stList *seqFrags, PairwiseAlignmentParameters *p, stList **seqPairSimilarityScores) {
+    cpecan_params q;
+    flatten_params(p, &q);
+    cpecan_sets_options o;
+    cpecan_sets_options_default(&o);
+    o.gapGamma = p->gapGamma;
+    o.constraintDiagonalTrim = p->constraintDiagonalTrim;
+    o.anchorMatrixBiggerThanThis = p->anchorMatrixBiggerThanThis;
+    o.repeatMaskMatrixBiggerThanThis = p->repeatMaskMatrixBiggerThanThis;
+    cpecan_sets *s = NULL;
+    check(cpecan_sets_create(&s, flat_or_die(sM), &q, &o, cpecan_current_device()), "cpecan_sets_create");
+    for (int64_t i = 0; i < stList_length(seqFrags); i++) { /* one set: a fragment's global index is its place in the list */
+        SeqFrag *f = stList_get(seqFrags, i);
+        if (cpecan_sets_add_fragment(s, 0, f->seq, f->length, f->leftEndId, f->rightEndId) != i) die("cpecan_hip: cpecan_sets_add_fragment failed");
+    }
+    const int64_t nPairs = cpecan_sets_pairs(s, CPECAN_SETS_ALL, NULL, 0);
+    if (nPairs < 0) die("cpecan_hip: cpecan_sets_pairs failed");
+    int64_t *pairs = malloc(sizeof(int64_t) * 2 * (size_t)(nPairs ? nPairs : 1));
+    if (!pairs) die("out of memory");
+    cpecan_sets_pairs(s, CPECAN_SETS_ALL, pairs, nPairs);
+    *seqPairSimilarityScores = stList_construct3(0, (void (*)(void *))stIntTuple_destruct);
+    stList *multipleAlignedPairs = stList_construct3(0, (void (*)(void *))stIntTuple_destruct);
+    if (nPairs > 0) { /* (a list of fewer than two fragments asks nothing of the GPU, as in the reference) */
+        cpecan_sets_result *r = NULL;
+        check(cpecan_sets_align(s, pairs, nPairs, &r), "makeAllPairwiseAlignments");
+        const int32_t *t = NULL;
+        const int64_t *sim = NULL;
+        int64_t n = 0;
+        check(cpecan_sets_result_pairs(r, &t, &n), "cpecan_sets_result_pairs");
+        check(cpecan_sets_result_similarity(r, &sim, NULL), "cpecan_sets_result_similarity");
+        for (int64_t i = 0; i < n; i++)
+            stList_append(multipleAlignedPairs, stIntTuple_construct5(t[5 * i], t[5 * i + 1], t[5 * i + 2], t[5 * i + 3], t[5 * i + 4]));
+        for (int64_t k = 0; k < nPairs; k++)
+            stList_append(*seqPairSimilarityScores, stIntTuple_construct3(sim[k], pairs[2 * k], pairs[2 * k + 1]));
+        cpecan_sets_result_free(r);
+    }
+    free(pairs);
+    cpecan_sets_destroy(s);
+    return multipleAlignedPairs;
+}
+
 static stList *anchors_for(const char *sX, const char *sY, PairwiseAlignmentParameters *p) {
     return getBlastPairsForPairwiseAlignmentParameters(sX, sY, (int64_t)strlen(sX), (int64_t)strlen(sY), p);
 }

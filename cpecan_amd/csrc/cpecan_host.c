@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "cpecan_internal.h"
+#include "cpecan_sets.h" /* cpecan_batch_set_quintuples / cpecan_batch_quintuples */
 #include "cpecan_band.inl"
 
 /* ------------------------------------------------------------------------------------------------
@@ -451,6 +452,11 @@ struct cpecan_batch {
     int32_t *postMea, *postShift;
     int bandEdge;            /* cpecan_batch_set_band_edge: downloads also compute the statistic */
     cpecan_band_edge *edges; /* [nProblems] of the downloaded run, or NULL: it was not asked for */
+    /* cpecan_batch_set_quintuples (include/cpecan_sets.h): the two names of every problem, or NULL: the stage is off */
+    int32_t *quintNames;
+    int32_t *quints;                 /* the downloaded run's records (host pool), its nProblems + 1 offsets and nProblems sums */
+    int64_t *quintOffsets, *quintSums;
+    double quintStageMs;
     cpecan_stats stats;
     /* cpecan_batch_download_begin / _end */
     pthread_t dlThread;
@@ -672,8 +678,13 @@ static void free_results(cpecan_batch *b) {
     cpk_host_free(b->postMea);
     cpk_host_free(b->postShift);
     free(b->edges);
+    cpk_host_free(b->quints);
+    free(b->quintOffsets);
+    free(b->quintSums);
     b->results = b->postMea = b->postShift = NULL;
     b->edges = NULL;
+    b->quints = NULL;
+    b->quintOffsets = b->quintSums = NULL;
 }
 
 void cpecan_batch_destroy(cpecan_batch *b) {
@@ -691,6 +702,7 @@ void cpecan_batch_destroy(cpecan_batch *b) {
     cpk_host_free(b->segs);
     free(b->forward);
     cpk_host_free(b->chars);
+    free(b->quintNames);
     free(b);
 }
 
@@ -1944,7 +1956,22 @@ static int run_post(cpecan_batch *b) {
             if (!b->postShift) rc = CPECAN_ENOMEM;
         }
     }
+    if (rc == CPECAN_OK && b->quintNames) { /* the quintuple stage: list 0 of every problem as records, and their score sums */
+        b->quints = cpk_host_alloc(sizeof(int32_t) * 5 * (size_t)(job.meaCap ? job.meaCap : 1));
+        b->quintOffsets = malloc(sizeof(int64_t) * (size_t)(b->nProblems + 1));
+        b->quintSums = calloc((size_t)(b->nProblems ? b->nProblems : 1), sizeof(int64_t));
+        b->quintStageMs = 0.0;
+        if (!b->quints || !b->quintOffsets || !b->quintSums) rc = CPECAN_ENOMEM;
+        job.names = b->quintNames;
+        job.quints = b->quints;
+        job.sums = b->quintSums;
+        job.stageMs = &b->quintStageMs;
+    }
     if (rc == CPECAN_OK) rc = cpk_device_post(b->dev, &job);
+    if (rc == CPECAN_OK && b->quintNames) {
+        for (int64_t i = 0; i < b->nProblems; i++) b->quintOffsets[i] = pp[i].meaOut;
+        b->quintOffsets[b->nProblems] = job.meaCap;
+    }
     for (int64_t i = 0; rc == CPECAN_OK && i < b->nProblems; i++) {
         HostProblem *pr = &b->problems[i];
         for (int k = 0; k < CPK_POST_SCORES; k++) pr->scores[k] = scores[CPK_POST_SCORES * i + k];
@@ -1976,6 +2003,57 @@ int cpecan_batch_set_post(cpecan_batch *b, int flags, double gapGamma) {
     if (flags && (b->emit == CPECAN_EMIT_FORWARD || b->emit == CPECAN_EMIT_EXPECT)) return CPECAN_EINVAL;
     b->postFlags = flags;
     b->postGapGamma = gapGamma;
+    return CPECAN_OK;
+}
+
+int cpecan_batch_set_quintuples(cpecan_batch *b, const int32_t *names, int64_t nProblems) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b) return CPECAN_EINVAL;
+    if (!names) {
+        free(b->quintNames);
+        b->quintNames = NULL;
+        return CPECAN_OK;
+    }
+    if (b->emit == CPECAN_EMIT_FORWARD || b->emit == CPECAN_EMIT_EXPECT) {
+        cpk_set_error("quintuples are made of the pair lists: EXPECT and FORWARD batches have none");
+        return CPECAN_EINVAL;
+    }
+    if (nProblems != b->nProblems) {
+        cpk_set_error("cpecan_batch_set_quintuples: names for %lld problems, the batch holds %lld", (long long)nProblems,
+                      (long long)b->nProblems);
+        return CPECAN_EINVAL;
+    }
+    int32_t *copy = malloc(sizeof(int32_t) * 2 * (size_t)(nProblems ? nProblems : 1));
+    if (!copy) return CPECAN_ENOMEM;
+    if (nProblems) memcpy(copy, names, sizeof(int32_t) * 2 * (size_t)nProblems);
+    free(b->quintNames);
+    b->quintNames = copy;
+    return CPECAN_OK;
+}
+
+int cpecan_batch_quintuples(const cpecan_batch *b, const int32_t **quints, const int64_t **offsets, const int64_t **sums) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !b->downloaded) return CPECAN_ESTATE;
+    if (!b->quints) {
+        cpk_set_error("quintuples were not asked for: cpecan_batch_set_quintuples before the download");
+        return CPECAN_ESTATE;
+    }
+    if (quints) *quints = b->quints;
+    if (offsets) *offsets = b->quintOffsets;
+    if (sums) *sums = b->quintSums;
+    return CPECAN_OK;
+}
+
+int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offsets, int64_t **sums, double *stageMs) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !b->downloaded || !b->quints) return CPECAN_ESTATE;
+    *quints = b->quints;
+    *offsets = b->quintOffsets;
+    *sums = b->quintSums;
+    if (stageMs) *stageMs = b->quintStageMs;
+    b->quints = NULL;
+    b->quintOffsets = b->quintSums = NULL;
+    b->downloaded = 0; /* the run's results have left the batch */
     return CPECAN_OK;
 }
 
@@ -2125,6 +2203,13 @@ int cpecan_batch_download(cpecan_batch *b) {
     if (b->nRegions == 0) {
         if (b->bandEdge) b->edges = calloc((size_t)(b->nProblems ? b->nProblems : 1), sizeof(cpecan_band_edge));
         if (b->bandEdge && !b->edges) return CPECAN_ENOMEM;
+        if (b->quintNames) { /* no region, no pair: empty records, offsets and sums of 0 */
+            b->quints = cpk_host_alloc(sizeof(int32_t) * 5);
+            b->quintOffsets = calloc((size_t)(b->nProblems + 1), sizeof(int64_t));
+            b->quintSums = calloc((size_t)(b->nProblems ? b->nProblems : 1), sizeof(int64_t));
+            b->quintStageMs = 0.0;
+            if (!b->quints || !b->quintOffsets || !b->quintSums) return CPECAN_ENOMEM;
+        }
         b->downloaded = 1;
         return CPECAN_OK;
     }
@@ -2226,7 +2311,8 @@ int cpecan_batch_download(cpecan_batch *b) {
         const double tD4 = now_ms();
         if (rc == CPECAN_OK) rc = run_post(b); /* consumers of the lists, on the device, before they leave it */
         const double tD5 = now_ms();
-        if (rc == CPECAN_OK) rc = cpk_device_fetch(b->dev, b->results, total, &b->stats.d2hMs);
+        /* with the quintuple stage the records have left the device in run_post: the triples stay where they are */
+        if (rc == CPECAN_OK && !b->quintNames) rc = cpk_device_fetch(b->dev, b->results, total, &b->stats.d2hMs);
         b->stats.pairs = total;
         if (trace_host())
             fprintf(stderr, "cpecan download: wait + counts %.1f ms, overflow scan %.1f, list plan %.1f (%lld chunks), gather %.1f, consumers %.1f, fetch %.1f (%lld triples)\n",
@@ -2279,6 +2365,10 @@ int cpecan_batch_result(const cpecan_batch *b, int64_t problem, int which, const
     if (!b || !b->downloaded) return CPECAN_ESTATE;
     if (problem < 0 || problem >= b->nProblems || which < 0) return CPECAN_EINVAL;
     if (which >= b->nLists && !(which == 3 && (b->postFlags & (CPECAN_POST_MEA | CPECAN_POST_ORDERED)))) return CPECAN_EINVAL;
+    if (which < 3 && b->quints) {
+        cpk_set_error("the batch downloads quintuples (cpecan_batch_set_quintuples): its triples stayed on the device");
+        return CPECAN_ESTATE;
+    }
     *triples = b->problems[problem].triples[which];
     *n = b->problems[problem].nTriples[which];
     return CPECAN_OK;

@@ -223,6 +223,12 @@ typedef struct {
     int32_t *counts;         /* [nProblems][2]: MEA or ordered pairs, left-shifted pairs */
     int32_t *mea;            /* [meaCap*3] or NULL */
     int32_t *shift;          /* [shiftCap*3] or NULL */
+    /* the quintuple stage (include/cpecan_sets.h), behind every consumer; names NULL: not selected, nothing of it is
+     * allocated or launched */
+    const int32_t *names;    /* host: [nProblems][2] */
+    int32_t *quints;         /* host out: [meaCap*5], problem i at 5 * problems[i].meaOut */
+    int64_t *sums;           /* host out: [nProblems] */
+    double *stageMs;         /* host out, or NULL: HIP-event time of the stage's kernel */
 } CpkPostJob;
 
 /* Runs the job on the batch's compact result buffer (after cpk_device_gather, before cpk_device_fetch). */
@@ -243,6 +249,10 @@ int cpk_host_threads(void); /* threads of the host's parallel loops (cpecan_host
  * CpkRegion array in device order, devToHost, the CpkSegment slots, CpkGeometry with the output and debug totals.  For
  * tests: the plan is dropped again (cpecan_host.c). */
 int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]);
+/* After the download of a batch with cpecan_batch_set_quintuples: hands the three arrays of cpecan_batch_quintuples over to
+ * the caller -- quints goes back with cpk_host_free, offsets and sums with free -- with the stage's kernel time; the batch
+ * forgets them (cpecan_sets.c keeps them as its result). */
+int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offsets, int64_t **sums, double *stageMs);
 /* Plans an unfrozen batch as cpecan_batch_upload would and then its launches (cpk_plan.inl, plan_batch) for a device of
  * numCUs compute units and memBytes of free memory that is not there: a kernel is taken to use the registers its build
  * allows.  out receives CPK_LAUNCH_PLAN_FIELDS numbers per launch class, in launch order (cpk_plan_describe); returns

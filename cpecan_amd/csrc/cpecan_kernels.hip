@@ -1589,6 +1589,36 @@ static int post_core(PostScratch &sc, int32_t *dTriples, const CpkPostJob *job) 
                            dShift, dCounts);
         HIP_TRY(hipGetLastError());
     }
+    // the quintuple stage of the sets layer: behind every consumer, on list 0 as they left it
+    int32_t *dQuints = nullptr;
+    long long *dSums = nullptr;
+    hipEvent_t evStage[2] = {nullptr, nullptr};
+    struct StageEvents {  // (released on every way out)
+        hipEvent_t *ev;
+        ~StageEvents() {
+            for (int k = 0; k < 2; k++)
+                if (ev[k]) (void)hipEventDestroy(ev[k]);
+        }
+    } stageEvents{evStage};
+    if (job->names) {
+        int32_t *dNames = nullptr;
+        if (int rc = sc.alloc(&dNames, (size_t)nP * 2)) return rc;
+        if (int rc = sc.alloc(&dQuints, (size_t)job->meaCap * 5)) return rc;
+        if (int rc = sc.alloc(&dSums, (size_t)nP)) return rc;
+        HIP_TRY(hipMemcpyAsync(dNames, job->names, sizeof(int32_t) * 2 * (size_t)nP, hipMemcpyHostToDevice, st));
+        if (job->stageMs) {
+            HIP_TRY(hipEventCreate(&evStage[0]));
+            HIP_TRY(hipEventCreate(&evStage[1]));
+            HIP_TRY(hipEventRecord(evStage[0], st));
+        }
+        hipLaunchKernelGGL(cpecan_post_quintuples, dim3((unsigned)nP), dim3(256), 0, st, dProblems, dTriples, dNames, dQuints,
+                           dSums);
+        HIP_TRY(hipGetLastError());
+        if (job->stageMs) HIP_TRY(hipEventRecord(evStage[1], st));
+        if (job->quints && job->meaCap > 0)
+            HIP_TRY(hipMemcpyAsync(job->quints, dQuints, sizeof(int32_t) * 5 * (size_t)job->meaCap, hipMemcpyDeviceToHost, st));
+        if (job->sums) HIP_TRY(hipMemcpyAsync(job->sums, dSums, sizeof(long long) * (size_t)nP, hipMemcpyDeviceToHost, st));
+    }
     if (job->scores)
         HIP_TRY(hipMemcpyAsync(job->scores, dScores, sizeof(double) * (size_t)nP * kPostScores, hipMemcpyDeviceToHost, st));
     if (job->counts) HIP_TRY(hipMemcpyAsync(job->counts, dCounts, sizeof(int32_t) * (size_t)nP * 2, hipMemcpyDeviceToHost, st));
@@ -1597,6 +1627,11 @@ static int post_core(PostScratch &sc, int32_t *dTriples, const CpkPostJob *job) 
     if (job->shift && dShift)
         HIP_TRY(hipMemcpyAsync(job->shift, dShift, sizeof(int32_t) * 3 * (size_t)job->shiftCap, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (job->names && job->stageMs) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, evStage[0], evStage[1]));
+        *job->stageMs = ms;
+    }
     return CPECAN_OK;
 }
 

@@ -884,6 +884,41 @@ __global__ void __launch_bounds__(256) cpecan_post_list_scores(const CpkPostProb
     }
 }
 
+// The quintuple stage of the sets layer (include/cpecan_sets.h; impl/multipleAligner.c:621-634 and the sum of :608-612).
+// Runs behind every consumer, on list 0 as REWEIGHT left it.  One workgroup per problem: pair i of the list becomes record
+// n - 1 - i of the problem's slice -- convertAlignedPairsToMultipleAlignedPairs pops from the end -- as (score, names[0],
+// x, names[1], y), and the scores are added up in 64 bits (a 300 bp pair already sums to 2.9e9): every lane its own pairs,
+// the wave by shuffles, the four waves through LDS.  Integers: the sum does not depend on the order.
+__global__ void __launch_bounds__(256) cpecan_post_quintuples(const CpkPostProblem *problems, const int32_t *triples,
+                                                              const int32_t *names, int32_t *quints, long long *sums) {
+    const CpkPostProblem pb = problems[blockIdx.x];
+    const int32_t *t = triples + 3 * pb.off[0];
+    const int n = pb.n[0];
+    int32_t *q = quints + 5 * pb.meaOut;  // meaOut: the list-0 lengths of the problems in front (post_layout)
+    const int32_t seq1 = names[2 * (size_t)blockIdx.x], seq2 = names[2 * (size_t)blockIdx.x + 1];
+    __shared__ long long partial[256 / CPK_WAVE];
+    long long sum = 0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int32_t s = t[3 * i], x = t[3 * i + 1], y = t[3 * i + 2];
+        int32_t *o = q + 5 * (int64_t)(n - 1 - i);
+        o[0] = s;
+        o[1] = seq1;
+        o[2] = x;
+        o[3] = seq2;
+        o[4] = y;
+        sum += s;
+    }
+#pragma unroll
+    for (int off = CPK_WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    if ((threadIdx.x & (CPK_WAVE - 1)) == 0) partial[threadIdx.x / CPK_WAVE] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long total = 0;
+        for (int w = 0; w < 256 / CPK_WAVE; w++) total += partial[w];
+        sums[blockIdx.x] = total;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Posterior mass on the band's edge (cpecan_band_edge_of_pairs is the host's statement of it).
 // Runs on the compact buffer behind cpecan_gather_lists and in front of every consumer, so the scores are the sweep's.

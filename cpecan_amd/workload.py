@@ -65,6 +65,30 @@ def make_pair(seed, index, length, expansion, anchor_every=50, sub=0.05, dele=0.
     return _BASES[xb].tobytes(), _BASES[y].tobytes(), anchors
 
 
+def make_fragment_set(seed, index, n_fragments=8, min_len=300, max_len=600, sub=0.05, dele=0.02, ins=0.02):
+    """Set `index` of a multiple-alignment workload (the fragments of one end, impl/multipleAligner.c): a uniform ACGT root
+    of max_len bases; fragment k is a window of it, min_len .. max_len long, mutated as make_pair mutates X.  Returns
+    [(seq: bytes, leftEndId, rightEndId)]: the end ids are the window's two edges, so two fragments share an end id exactly
+    when their windows share that edge.  A function of (seed, index) alone."""
+    set_seed = int(splitmix64(seed ^ 0x5E75, [index])[0])
+    root = (splitmix64(set_seed, np.arange(max_len, dtype=np.uint64)) & np.uint64(3)).astype(np.int64)
+    out = []
+    for k in range(n_fragments):
+        u = splitmix64(int(splitmix64(set_seed, [max_len + k])[0]), np.arange(2 + 3 * max_len, dtype=np.uint64))
+        L = min_len + int(u[0] % np.uint64(max_len - min_len + 1))
+        start = int(u[1] % np.uint64(max_len - L + 1))
+        xb = root[start:start + L]
+        r = _unit(u[2:2 + L])
+        alt = (xb + 1 + (u[2 + max_len:2 + max_len + L] % np.uint64(3)).astype(np.int64)) % 4
+        insb = (u[2 + 2 * max_len:2 + 2 * max_len + L] & np.uint64(3)).astype(np.int64)
+        is_sub = r < sub
+        is_del = (r >= sub) & (r < sub + dele)
+        is_ins = (r >= sub + dele) & (r < sub + dele + ins)
+        cols = np.stack([np.where(is_ins, insb, -1), np.where(is_del, -1, np.where(is_sub, alt, xb))], axis=1).reshape(-1)
+        out.append((_BASES[cols[cols >= 0]].tobytes(), start, start + L))
+    return out
+
+
 def make_batch(seed, n_pairs, length, expansion, first=0, **kw):
     return [make_pair(seed, first + i, length, expansion, **kw) for i in range(n_pairs)]
 

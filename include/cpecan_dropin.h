@@ -51,6 +51,7 @@ void *stList_get(stList *list, int64_t index);
 void stList_append(stList *list, void *item);
 stIntTuple *stIntTuple_construct2(int64_t a, int64_t b);
 stIntTuple *stIntTuple_construct3(int64_t a, int64_t b, int64_t c);
+stIntTuple *stIntTuple_construct5(int64_t a, int64_t b, int64_t c, int64_t d, int64_t e);
 void stIntTuple_destruct(stIntTuple *t);
 int64_t stIntTuple_get(stIntTuple *t, int64_t index);
 int64_t stIntTuple_length(stIntTuple *t);
@@ -214,6 +215,22 @@ stList *leftShiftAlignment(stList *alignedPairs, char *seqX, char *seqY);
 stList *getShiftedMEAAlignment(char *seqX, char *seqY, stList *anchorAlignment, PairwiseAlignmentParameters *p,
                                StateMachine *sM, bool alignmentHasRaggedLeftEnd, bool alignmentHasRaggedRightEnd,
                                double *alignmentScore);
+
+/* ---- inc/multipleAligner.h: the pairwise stage of the multiple aligner (include/cpecan_sets.h) ---- */
+typedef struct _seqFrag SeqFrag;
+struct _seqFrag { /* inc/multipleAligner.h:22-28 */
+    char *seq;
+    int64_t length;
+    int64_t leftEndId;
+    int64_t rightEndId;
+};
+SeqFrag *seqFrag_construct(const char *seq, int64_t leftEndId, int64_t rightEndId); /* copies seq (impl/multipleAligner.c:976) */
+void seqFrag_destruct(SeqFrag *seqFrag);
+/* impl/multipleAligner.c:668-681: every pair seq1 < seq2 of the list aligned, reweighted and scored in ONE anchor batch and
+ * ONE DP batch on the caller's current device.  Returns the (score, seq1, pos1, seq2, pos2) tuples in the reference's order;
+ * *seqPairSimilarityScores receives the (similarity, seq1, seq2) tuples.  Both lists carry stIntTuple_destruct. */
+stList *makeAllPairwiseAlignments(StateMachine *sM, stList *seqFrags, PairwiseAlignmentParameters *pairwiseAlignmentBandingParameters,
+                                  stList **seqPairSimilarityScores);
 
 typedef struct _diagonal {
     int64_t xay;
