@@ -95,10 +95,10 @@ typedef struct {
     int32_t maxRefresh;   /* most refresh points in any segment */
     int32_t useGlobalRoll;/* slow path: rolling buffers and symbol strings stay in global memory (too big for LDS) */
     int32_t seqLdsBytes;  /* fast path: bytes of LDS for the two padded symbol strings of the largest region */
-    int32_t debug;
+    int32_t debug;        /* 0 or 1: the sweeps fill the debug buffers (F + B of every emitted cell, the totals used) */
     int32_t fusedSpin;    /* one-launch form: polls of an item for its region's forward values before it gives up (reported, re-run in two launches) */
     int32_t expInSweep;   /* expectation emitter: the events are formed inside the traceback (every diagonal of the class fits one 64-lane group) */
-    int32_t reserved0;
+    int32_t absWholeStrings; /* absolute-position sweeps stage both whole symbol strings, not a window per segment (CPECAN_ABS_WINDOWS=0) */
     int64_t ringCells;    /* forward ring capacity per slot, in cells */
     int64_t fbCells;      /* posterior-candidate scratch per slot, in cells (most emitted cells of one segment) */
     int64_t refreshCells; /* c/m scratch per slot = maxWidth * maxRefresh (each) */

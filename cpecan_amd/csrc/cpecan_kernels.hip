@@ -1243,9 +1243,6 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
     a.symbols = d->dSymbols;
     a.model = d->dModel;
     a.geo = d->geo;
-#ifdef CPK_DIAGNOSTICS  // tools/ab_build.sh <tag> -DCPK_DIAGNOSTICS: phase bisection for timing runs; never in the shipped library
-    if (const char *skip = getenv("CPECAN_DEBUG_SKIP")) a.geo.debug |= (atoi(skip) & 6);
-#endif
     a.ring = d->dRing;
     a.cand = d->dCand;
     a.cbuf = d->dC;

@@ -67,7 +67,7 @@ cpecan_pairhmm_packed(const KArgs a) {
 
     fill_cubics(lds);
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
-    double *wt = lds + kLdsCubics + kLdsEm;
+    double *wt = lds + kLdsCubics;
     if constexpr (SLOTS) fill_weights<S>(wt, *mp, a.slotModels[0].kc, lane);
     else fill_weights<S>(wt, *mp, a.kc, lane);
     constexpr bool kExpect = EMIT == CPECAN_EMIT_EXPECT;
@@ -79,7 +79,7 @@ cpecan_pairhmm_packed(const KArgs a) {
     constexpr bool kIndel = EMIT == CPECAN_EMIT_INDEL;
     constexpr bool kKeepB = kExpect || kIndel;
     constexpr int NL = kIndel ? 3 : 1;
-    double *eLds = lds + kLdsCubics + kLdsEm + kLdsWeights;  // expectation emitter: emission sums of this wave, four copies
+    double *eLds = lds + kLdsCubics + kLdsWeights;  // expectation emitter: emission sums of this wave, four copies
     if (kExpect)
         for (int i = lane; i < kExpectCopies * 80; i += CPK_WAVE) eLds[i] = 0.0;
     constexpr int kNT = S == 5 ? 13 : 9;
@@ -87,7 +87,7 @@ cpecan_pairhmm_packed(const KArgs a) {
 #pragma unroll
     for (int i = 0; i < kNT; i++) tAcc[i] = 0.0;
     double likelihood = 0.0;
-    uint8_t *mine = reinterpret_cast<uint8_t *>(lds + kLdsCubics + kLdsEm + kLdsWeights + (kExpect ? kExpectCopies * 80 : 0)) +
+    uint8_t *mine = reinterpret_cast<uint8_t *>(lds + kLdsCubics + kLdsWeights + (kExpect ? kExpectCopies * 80 : 0)) +
                     (size_t)g * pack_group_bytes(S, GW);
     double *rows = reinterpret_cast<double *>(mine);                                   // rolling buffers
     int4 *ebuf = reinterpret_cast<int4 *>(mine + pack_rows_bytes(S, GW));              // table entries of the chunk
@@ -98,7 +98,7 @@ cpecan_pairhmm_packed(const KArgs a) {
     // the cell functions only need the tables; every position-dependent input is passed per call
     // (RDBL = kSplit: a split region's ring counts doubles and pads the match row, Sweep::ringIdx)
     using SW = Sweep<S, false, 2 * S + 1, false, kSplit>;
-    SW sw{a, a.kc, DiagCache{nullptr, 0, 0, lane, 0, 0, 0, 0}, nullptr, nullptr, rows, lds + kLdsCubics, wt, lg,
+    SW sw{a, a.kc, DiagCache{nullptr, 0, 0, lane, 0, 0, 0, 0}, nullptr, nullptr, rows, wt, lg,
           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, GW + 1, lane, lane * R, 0, CpkDiag{}, CpkDiag{}};
     const unsigned long long groupBits = (GW == 64 ? ~0ull : ((1ull << GW) - 1ull)) << (g * GW);
     const unsigned long long belowMe = groupBits & ((1ull << lane) - 1ull);

@@ -209,7 +209,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
     c.geo.fbCells = geo.pFbCells[k];
     c.geo.maxRefresh = geo.pMaxRefresh[k];
     c.geo.refreshCells = (int64_t)GW * geo.pMaxRefresh[k];
-    c.ldsBytes = sizeof(double) * (size_t)(kLdsCubics + kLdsEm + kLdsWeights + (expect ? kExpectCopies * 80 : 0)) +
+    c.ldsBytes = sizeof(double) * (size_t)(kLdsCubics + kLdsWeights + (expect ? kExpectCopies * 80 : 0)) +
                  (size_t)G * pack_group_bytes(S, GW);
     int perCU = 0;
     if (int rc = waves_per_cu(c.form, c.ldsBytes, 1, in, &perCU)) return rc;
@@ -333,8 +333,8 @@ static void set_row_form(LaunchClass &cc, bool abs, const PlanKnobs &knobs) {
     const int S = cc.geo.nStates, emit = cc.geo.emit;
     cc.abs = abs;
     cc.geo.rollStride = cc.geo.maxWidth + (abs ? kAbsSlack : 1);
-    cc.geo.reserved0 = (abs && knobs.absWindows.off()) ? 1 : 0;
-    cc.geo.seqLdsBytes = (abs && !cc.geo.reserved0) ? cc.geo.wWinLdsBytes[cc.k] : cc.geo.wSeqLdsBytes[cc.k];
+    cc.geo.absWholeStrings = (abs && knobs.absWindows.off()) ? 1 : 0;
+    cc.geo.seqLdsBytes = (abs && !cc.geo.absWholeStrings) ? cc.geo.wWinLdsBytes[cc.k] : cc.geo.wSeqLdsBytes[cc.k];
     cc.geo.rollDoubles = (int64_t)(abs ? 2 * S : 2 * S + 1) * cc.geo.rollStride;
     const size_t header = sizeof(double) * (lds_header_doubles(emit) + lds_stage_doubles(emit, abs));
     cc.ldsBytes = cc.geo.useGlobalRoll ? header
@@ -432,7 +432,7 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
         c.threads = CPK_WAVE * kTeamWaves * (big ? 2 : 1);
         c.geo.useGlobalRoll = 0;
         c.abs = false;
-        c.geo.reserved0 = 0;
+        c.geo.absWholeStrings = 0;
         c.geo.expInSweep = 0;  // (the team's expectation emitter is the second pass: B of the emitted cells in `bring`)
         c.geo.rollStride = teamStride;
         c.geo.seqLdsBytes = geo.wSeqLdsBytes[k];

@@ -35,7 +35,6 @@ struct Sweep {
     __device__ __forceinline__ int symX(int p) const { return FAST ? (sxp[p >> 1] >> ((p & 1) * 4)) & 15 : sxp[p]; }
     __device__ __forceinline__ int symY(int p) const { return FAST ? (syp[p >> 1] >> ((p & 1) * 4)) & 15 : syp[p]; }
     double *roll;        // rolling buffers: `stride` positions of R = 2S+1 doubles; position 0 = -inf guard
-    const double *em;    // LDS emissions: [0..24] match, [25..29] gapX, [30..34] gapY
     // LDS (emission + transition) sums, the second operand of every DP term `from + (eP + tP)` (pairwiseAligner.c:384):
     //   wt[(cX*5 + cY)*kWM + i]             match emission + {matchContinue, matchFromShortX, matchFromShortY, [matchFromLongX, matchFromLongY]}
     //   wt[25*kWM + cX*kWG + i]             gapX emission  + {open, extend, [longOpen, longExtend] | switchToX}
@@ -82,10 +81,8 @@ struct Sweep {
         return s == 0 ? (size_t)k : (size_t)We + (size_t)k * (S - 1) + (size_t)(s - 1);
     }
     __device__ __forceinline__ double *ringAt(const CpkDiag &g) const { return ring + (size_t)g.ringOff * (RDBL ? 1 : S); }
-    // CPK_COH_ST / CPK_COH_LD = 0: timing-only builds (tools/ab_build.sh) that drop one side's device scope -- results
-    // of the one-launch form are then undefined
     __device__ __forceinline__ static void ringSt(double *p, double v) {
-        if (COH && CPK_COH_ST) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *p = v;
     }
     // One cell's forward values -> the ring (rs states: 1 = the match row only, S = all).  next / prev: the lane above /
@@ -96,10 +93,7 @@ struct Sweep {
     // DPP and writes both as one aligned 16 bytes, the neighbour writes nothing, and a cell's other states leave as
     // 16-byte writes too (S - 1 is even, their run starts on an even double).
     __device__ __forceinline__ void ringPut(double *out, int W, int k, bool next, bool prev, const double (&v)[S], int rs) const {
-#ifdef CPK_TIMING_NO_RING_STORES  // timing experiment (tools/ab_build.sh): what the forward sweep costs without its stores
-        if (a.geo.maxWidth >= 0) return;
-#endif
-        if (!(COH && CPK_COH_ST && CPK_COH_PAIRS)) {
+        if (!COH) {
             if (rs > 0) {
                 ringSt(out + ringIdx(W, 0, k), v[0]);
                 if (rs > 1) {
@@ -135,7 +129,7 @@ struct Sweep {
         }
     }
     __device__ __forceinline__ static double ringLd(const double *p) {
-        return (COH && CPK_COH_LD) ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ld_self(p);
+        return COH ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ld_self(p);
     }
 
     // ---- forward: impl/pairwiseAligner.c:609-629 with stateMachine{5,3}_cellCalculate as the per-cell body ----
@@ -153,13 +147,8 @@ struct Sweep {
 #pragma unroll
         for (int q = 0; q < NC; q++) {
             const int x = c.xlo + k[q], y = c.d - x;
-#ifdef CPK_TIMING_NO_SYMBOLS  // timing experiment (tools/ab_build.sh): symbols from the lane number instead of LDS -- results invalid
-            cX[q] = (x + lane) & 3;
-            cY[q] = (y + 2 * lane) & 3;
-#else
             cX[q] = symX(x);
             cY[q] = symY(y);
-#endif
         }
         fwdCellsSym<NC>(c, cX, cY, kR, v);
     }
@@ -512,11 +501,7 @@ struct Sweep {
     // cells [kb, kb + 64) of one diagonal, clipped to [kb, hi)
     __device__ __forceinline__ void absFwdGroup(const AbsDiag &c, double *out, int rs, int kb, int hi) {
         const int k0 = kb + lane;
-#ifdef CPK_TIMING_LANES  // timing experiment: only the first CPK_TIMING_LANES lanes of every group work (results invalid)
-        if (k0 < hi && lane < CPK_TIMING_LANES) {
-#else
         if (k0 < hi) {
-#endif
             const int kk[1] = {k0};
             const int kkR[1] = {c.ownR + kb * R + laneR};
             FwdCtx f;
@@ -534,33 +519,6 @@ struct Sweep {
             for (int st = 0; st < S; st++) c.cur[st + kkR[0]] = v[0][st];
             ringPut(out, c.W, k0, k0 + 1 < hi && lane < CPK_WAVE - 1, lane > 0, v[0], rs);
         }
-    }
-    // cells [kb, kb + 128) of one diagonal, clipped to [kb, hi): two cells per lane, 64 apart, in lock-step
-    __device__ __forceinline__ void absFwdGroup2(const AbsDiag &c, double *out, int rs, int kb, int hi) {
-        const int k0 = kb + lane, k1 = k0 + CPK_WAVE;
-        const bool on1 = k1 < hi;
-        // lanes without a second cell recompute their first one (k0 < hi holds for every lane: hi - kb > 64)
-        const int kk[2] = {k0, on1 ? k1 : k0};
-        const int kkR[2] = {c.ownR + kb * R + laneR, c.ownR + (on1 ? kb + CPK_WAVE : kb) * R + laneR};
-        FwdCtx f;
-        f.d = c.d;
-        f.xlo = c.xlo;
-        f.dlR = 0;
-        f.w1R = 0;
-        f.dmR = 0;
-        f.w2R = 0;
-        f.p1 = c.lu;
-        f.p2 = c.cur;
-        double v[2][S];
-        fwdCells<2>(f, kk, kkR, v);
-#pragma unroll
-        for (int st = 0; st < S; st++) c.cur[st + kkR[0]] = v[0][st];
-        if (on1) {
-#pragma unroll
-            for (int st = 0; st < S; st++) c.cur[st + kkR[1]] = v[1][st];
-        }
-        ringPut(out, c.W, k0, lane < CPK_WAVE - 1, lane > 0, v[0], rs);
-        if (on1) ringPut(out, c.W, k1, k1 + 1 < hi && lane < CPK_WAVE - 1, lane > 0, v[1], rs);
     }
     __device__ void absFlushTail() {
         if (!atail.has) return;
@@ -581,22 +539,8 @@ struct Sweep {
         const AbsDiag c = absDiag(d, g, pLo);
         double *out = ringAt(g);
         int lo = 0;
-#if defined(CPK_ABS_FWD_FORM) && CPK_ABS_FWD_FORM > 0
-        // timing experiments (tools/ab_build.sh): no streaming; FORM 2: pairs of groups in lock-step (two cells per lane).
-        // Measured (profiles/r03_forward_what_bounds_it.txt, r03_ab_forward_pairs_under_subscribed.txt): the pairs are 6 %
-        // slower with every wave slot busy and within 1.5 % of the stream on launches with fewer regions than slots (1250 /
-        // 2500 config-B pairs, config A) -- two cells per lane buy nothing on this kernel.
-        for (; CPK_ABS_FWD_FORM == 2 && W - lo > CPK_WAVE; lo += 2 * CPK_WAVE) absFwdGroup2(c, out, ringStates, lo, W);
-#ifdef CPK_TIMING_GROUP_REPEAT  // timing experiment: every group computed CPK_TIMING_GROUP_REPEAT times (0: not at all)
-        for (; lo < W; lo += CPK_WAVE)
-            for (int rep = 0; rep < CPK_TIMING_GROUP_REPEAT; rep++) absFwdGroup(c, out, ringStates, lo, W);
-#else
-        for (; lo < W; lo += CPK_WAVE) absFwdGroup(c, out, ringStates, lo, W);
-#endif
-        apos2 = apos1;
-        apos1 = pLo;
-        return;
-#endif
+        // (Two cells per lane, pairs of groups in lock-step, buy nothing on this kernel: 6 % slower with every wave slot
+        // busy, within 1.5 % otherwise -- profiles/r03_forward_what_bounds_it.txt, r03_ab_forward_pairs_under_subscribed.txt.)
         if (atail.has) {
             // Lanes [0, r) finish diagonal A = d - 1, lanes [r, r + b) start this one.  Its cells [0, b) read F[A] up to
             // position pLo + b - 1 + (d & 1), which earlier groups must have written: below the first leftover cell of A.
@@ -1040,18 +984,9 @@ struct Sweep {
         double fmCur[NL][kPrefetch];
         auto loadRows = [&](const CpkDiag &gd, int offd, double (&dst)[NL][kPrefetch]) {
             static_assert(NL == 1, "the unclamped prefetch addresses the match row (cell k at element k)");
-#ifdef CPK_TIMING_HOT_ROWS  // timing experiment: every prefetch reads the same (cache-hot) words -- results invalid
-            const double *src = ring + lane + (offd & 1);
-#else
             const double *src = ringAt(gd) + (lane - offd);  // lane - offd may be negative: the ring is padded in front
-#endif
-#ifdef CPK_TIMING_NO_PREFETCH  // timing experiment: no F rows at all
-#pragma unroll
-            for (int q = 0; q < kPrefetch; q++) dst[0][q] = (double)(src != nullptr);
-#else
 #pragma unroll
             for (int q = 0; q < kPrefetch; q++) dst[0][q] = ringLd(src + q * CPK_WAVE);
-#endif
         };
         // posterior candidates of one group of an emitted diagonal: fb = F + B of the NL emitted states
         auto emitCells = [&](int d, int x, bool on, const double (&f0)[NL], const double (&v)[S], int dbgAt) {
@@ -1133,13 +1068,8 @@ struct Sweep {
                 const bool in = (unsigned)k < (unsigned)W;
                 // (lane * R is a member; k * R would be a multiply per lane that hipcc computes once per kernel and keeps)
                 const double *row = cx.cur + cx.ownR + (in ? (q * CPK_WAVE - off) * R + laneR : 0);
-#ifdef CPK_TIMING_NO_PASSES  // timing experiment: of the pass only the candidate bound is left -- results invalid
-                constexpr int nS = 1;
-#else
-                constexpr int nS = S;
-#endif
 #pragma unroll
-                for (int s2 = 0; s2 < nS; s2++) b[s2][q] = lds1(row + s2);
+                for (int s2 = 0; s2 < S; s2++) b[s2][q] = lds1(row + s2);
                 const int x = cx.xlo + k, y = cx.d - x;
                 cell[q] = in && x > 0 && y > 0;
             }
@@ -1148,7 +1078,6 @@ struct Sweep {
                 acc[q] = fm[0][q] + b[0][q];
                 if (CANDS) laneMax = fmaxf(laneMax, cell[q] ? (float)acc[q] : -__builtin_huge_valf());
             }
-#ifndef CPK_TIMING_NO_PASSES
 #pragma unroll
             for (int s2 = 1; s2 < S; s2++) {
                 double t[n];
@@ -1158,7 +1087,6 @@ struct Sweep {
             }
 #pragma unroll
             for (int q = 0; q < n; q++) pendC[q] = acc[q];
-#endif
         };
         auto refreshDots = [&](const AbsDiag &cx, const CpkDiag &g, int off, int jr, const double (&fm)[NL][kPrefetch],
                                const double (&rfC)[S][kPrefetch]) {
@@ -1187,11 +1115,9 @@ struct Sweep {
                     cbuf[(size_t)k * J + jr] = t;
                 }
             }
-#ifndef CPK_TIMING_NO_PASSES
             pendCW = W;
             pendCOff = off;
             pendCj = jr;
-#endif
             if (CANDS) {
                 lastMax = fmaxf(wave_max_f32(laneMax), lastMax - 1.0f);
                 keepFrom = (double)(lastMax + logThr - kCandMargin);
@@ -1311,15 +1237,10 @@ struct Sweep {
             const CpkDiag gnext2 = dc.at(ci);
             const int gnpos2 = dc.posAt(ci) >> 16;
             double rfC[S][kPrefetch];  // a refresh point reads every state of F[d2]: requested here, used behind the groups
-#ifndef CPK_TIMING_NO_PASSES
             if (refresh) loadRefreshRows(g, off, rfC);
-#endif
             // One group of 64 cells: lane by lane cell k0 of diagonal t (wave-uniform except in the shared group); lanes that
             // are not `on` compute a cell of their diagonal all the same and store nothing.
             auto group = [&](const AbsDiag &t, int k0, int kR0, bool on, const double (&f0)[NL], int tCellOff) {
-#ifdef CPK_TIMING_TRACE_REPEAT  // timing experiment: every traceback group computed this many times (0: not at all)
-              for (int rep = 0; rep < CPK_TIMING_TRACE_REPEAT; rep++) {
-#endif
                 BwdCtx c;
                 c.d2 = t.d;
                 c.xlo = t.xlo;
@@ -1337,14 +1258,7 @@ struct Sweep {
 #pragma unroll
                     for (int st = 0; st < S; st++) t.cur[st + kR0] = v[0][st];
                 }
-#ifdef CPK_TIMING_TRACE_NO_EMIT
-                if (emit && a.geo.maxWidth < 0) emitCells(t.d, t.xlo + k0, on, f0, v[0], tCellOff + k0);
-#else
                 if (emit) emitCells(t.d, t.xlo + k0, on, f0, v[0], tCellOff + k0);
-#endif
-#ifdef CPK_TIMING_TRACE_REPEAT
-              }
-#endif
             };
             int q0 = 0;
             if (carry) {  // the shared group: lanes [0, off) finish the diagonal above, the others start this one
@@ -1390,12 +1304,7 @@ struct Sweep {
                 for (int l = 0; l < NL; l++) f0[l] = ringLd(ringAt(g) + ringIdx(W, l, on ? k0 : W - 1));
                 group(cx, on ? k0 : W - 1, on ? cx.ownR + kb * R + laneR : cx.ownR + (W - 1) * R, on, f0, g.cellOff);
             }
-#ifdef CPK_TIMING_NO_PASSES  // timing experiment: neither the straddle series nor the dot products; the candidate bound of a
-                             // refresh point stays (dotGroups) -- without it every cell of the segment is a candidate
-            if (refresh || (feeds && a.geo.maxWidth < 0)) {
-#else
             if (feeds || refresh) {  // one diagonal in five: all its cells are done (no tail waits), a pass of its own follows
-#endif
                 roll_fence<false>();
                 if (feeds) {  // F.m of the cells from the prefetched registers, B.m from the rows
 #pragma unroll
@@ -2179,12 +2088,6 @@ constexpr int kModeWhole = 0, kModeForward = 1, kModeTrace = 2, kModeFused = 3;
 // handful of spills) three fit, and a queue that long runs 9-34 % faster with them (cpk_device_upload).
 // ABS: the sweeps of a split class over absolute positions (Sweep::forwardStreamAbs / tracebackAbs): match emitter, LDS rows,
 // fixed expansion (KArgs::dpos holds the positions)
-#ifndef CPK_FUSED_PRIO
-#define CPK_FUSED_PRIO 0
-#endif
-#ifndef CPK_INSWEEP_PLAIN_FWD
-#define CPK_INSWEEP_PLAIN_FWD 1  // bands this narrow have no whole group in front of a tail: the plain per-diagonal forward (1.2 % faster, config 5)
-#endif
 // INSWEEP: expectation emitter, every diagonal of the class within one 64-lane group: the events are formed inside the
 // traceback (Sweep::tracebackExpect / scaleWindows) instead of in a second pass (Sweep::expectations)
 // (INSWEEP = 1: a class without a diagonal wider than 64 cells -- one group per diagonal, nothing kept for a second)
@@ -2221,11 +2124,10 @@ cpecan_pairhmm_sweep(const KArgs a) {
     // (GANG: the tables once, filled by wave 0 -- fill_cubics strides over threadIdx.x --, then rows, stage and symbols per wave)
     fill_cubics(lds);
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
-    double *em = lds + kLdsCubics;  // (no plain emission table any more: kLdsEm == 0, every term reads `wt`)
-    double *wt = lds + kLdsCubics + kLdsEm;
+    double *wt = lds + kLdsCubics;
     if constexpr (SLOTS) fill_weights<S>(wt, *mp, a.slotModels[0].kc, lane);
     else if (!GANG || wave == 0) fill_weights<S>(wt, *mp, a.kc, lane);
-    double *eLds = lds + kLdsCubics + kLdsEm + kLdsWeights;  // emission-expectation sums of this wave (expectation emitter)
+    double *eLds = lds + kLdsCubics + kLdsWeights;  // emission-expectation sums of this wave (expectation emitter)
     constexpr int kECopies = lds_expect_copies(INSWEEP != 0);
     if (EMIT == CPECAN_EMIT_EXPECT)
         for (int i = lane; i < kECopies * 80; i += CPK_WAVE) eLds[i] = 0.0;
@@ -2286,13 +2188,8 @@ cpecan_pairhmm_sweep(const KArgs a) {
         // Every lane takes part in the ticket fetch (lane 0 adds 1, the others add 0; hipcc folds this into one
         // atomic per wave).  Do NOT write this as `if (lane == 0) ticket = atomicAdd(..)`: hipcc 7.2 jump-threads
         // the lane test across the loop back-edge and re-runs the readfirstlane with 63 lanes -> endless loop.
-#if defined(CPK_DIAGNOSTICS) && defined(CPK_TICKET_LANE0)
-        // the form that hangs, kept for the ISA comparison only (profiles/r02_ticket_fetch_isa.txt)
-        unsigned int ticket = 0;
-        if (lane == 0) ticket = atomicAdd(a.queue, 1u);
-#else
+        // (Both forms side by side, for the ISA comparison only: tools/ticket_forms.hip, profiles/r02_ticket_fetch_isa.txt.)
         const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? 1u : 0u);
-#endif
         const int tk = __builtin_amdgcn_readfirstlane((int)ticket);
         int tkRegion = tk;  // (SLOTS: the region of virtual region tk)
         if constexpr (SLOTS) {
@@ -2318,22 +2215,13 @@ cpecan_pairhmm_sweep(const KArgs a) {
         const bool traceRole = MODE == kModeTrace || (MODE == kModeFused && tk >= a.regionCount);  // wave-uniform
         const bool forwardRole = MODE == kModeForward || (MODE == kModeFused && !traceRole);
         const int ti = MODE == kModeFused ? tk - a.regionCount : tk;
-#if CPK_FUSED_PRIO
-        // One launch, regions and items in one queue: the forward sweep of a region is the chain everything else of the
-        // region waits for, so its wave goes ahead of the item waves that share its SIMD (s_setprio: the arbiter picks the
-        // highest-priority wave that can issue).
-        if (MODE == kModeFused) {
-            if (forwardRole) __builtin_amdgcn_s_setprio(CPK_FUSED_PRIO);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
         const int r = traceRole ? a.items[ti].region : a.regionBase + tkRegion;
         const int itemSeg = traceRole ? a.items[ti].seg : 0;
 
         const CpkRegion &rg = a.regions[r];
         const int lX = rg.lX, lY = rg.lY, N = lX + lY;
         const uint8_t *gx = a.symbols + rg.seqXOff, *gy = a.symbols + rg.seqYOff;
-        if (FAST && (!ABS || a.geo.reserved0)) {  // (reserved0: CPECAN_ABS_WINDOWS=0, whole strings for the absolute-position sweeps too)
+        if (FAST && (!ABS || a.geo.absWholeStrings)) {  // (CPECAN_ABS_WINDOWS=0: whole strings for the absolute-position sweeps too)
             // stage N + bases + N of both strings into LDS, two symbols per byte (per-cell reads come from here)
             // (absolute positions: the symbols a SEGMENT's diagonals touch, staged per segment below)
             stage_symbols<CPK_WAVE>(seqLds, gx, lX + 2, lane);
@@ -2347,7 +2235,6 @@ cpecan_pairhmm_sweep(const KArgs a) {
                           FAST ? seqLds : gx,
                           FAST ? seqLds + ((lX + 3) >> 1) : gy,
                           roll,
-                          em,
                           wt,
                           lg,
                           MODE == kModeWhole ? a.ring + slot * (size_t)a.geo.ringCells * S : a.ring + (size_t)rg.ringBase,
@@ -2438,7 +2325,7 @@ cpecan_pairhmm_sweep(const KArgs a) {
             const int siFirst = traceRole ? itemSeg : 0, siEnd = traceRole ? itemSeg + 1 : rg.nSeg;
             for (int si = siFirst; si < siEnd; si++) {
                 const CpkSegment sg = a.segs[rg.segOff + si];
-                if (ABS && !a.geo.reserved0) {
+                if (ABS && !a.geo.absWholeStrings) {
                     // Symbol windows (round 4): only the symbols the diagonals of THIS step touch are staged -- the forward
                     // sweep of diagonals d .. dTop, or the traceback of tbPrev + 1 .. dTop, whose cells also read the symbols
                     // one past their own (Sweep::bwdCells) -- ~0.7 KB instead of the 2 KB of both whole strings of a 2 kb pair.
@@ -2476,13 +2363,15 @@ cpecan_pairhmm_sweep(const KArgs a) {
                         }
                         const bool all = EMIT != CPECAN_EMIT_MATCH || toRefresh == 0 || d >= sg.dTop - 1;
                         toRefresh = toRefresh == 0 ? CPK_REFRESH_PERIOD - 1 : toRefresh - 1;
+                        // INSWEEP: bands this narrow have no whole group in front of a tail -- the plain per-diagonal forward
+                        // (1.2 % faster, config 5)
                         if (ABS) sw.forwardStreamAbs(d, sw.dc.at(d - sw.dc.base), sw.dc.posAt(d - sw.dc.base), all ? S : 1);
-                        else if (FAST && !(INSWEEP && CPK_INSWEEP_PLAIN_FWD)) sw.forwardStream(d, sw.dc.at(d - sw.dc.base), all ? S : 1);
+                        else if (FAST && !INSWEEP) sw.forwardStream(d, sw.dc.at(d - sw.dc.base), all ? S : 1);
                         else sw.forward(d, sw.dc.at(d - sw.dc.base), all ? S : 1);
                     }
                 }
                 if (ABS && !traceRole) sw.absFlushTail();
-                else if (FAST && !(INSWEEP && CPK_INSWEEP_PLAIN_FWD) && !traceRole) sw.flushTail();  // the traceback needs every cell of dTop
+                else if (FAST && !INSWEEP && !traceRole) sw.flushTail();  // the traceback needs every cell of dTop
                 if (forwardRole) {  // the tracebacks of this region are items of their own (of the next launch, or of this one)
                     if (MODE == kModeFused) {
                         // the ring stores are device-scope write-through (Sweep::ringSt): once they are acknowledged -- this
@@ -2509,9 +2398,6 @@ cpecan_pairhmm_sweep(const KArgs a) {
                         continue;
                     }
                 }
-#ifdef CPK_DIAGNOSTICS
-                if (a.geo.debug & 2) continue;  // diagnostic build only: time the forward sweep alone (no traceback, no output)
-#endif
                 const double *endPrior = (sg.atEnd && rg.raggedRight) ? mp->raggedEnd : mp->end;
                 int nCand[NL];
                 if constexpr (ABS) sw.template tracebackAbs<NL, true>(sg, endPrior, (a.geo.debug & 1) ? a.dbgFb + rg.dbgCellOff : nullptr, nCand);

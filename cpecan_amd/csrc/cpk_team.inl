@@ -20,7 +20,7 @@ constexpr int kTeamXchg = 48;   // doubles of LDS for the exchange area (counts 
 
 // (expect: the workgroup's emission sums of the expectation emitter, kExpectCopies copies of 80, behind the exchange area)
 __host__ __device__ constexpr int team_header_doubles(bool expect = false) {
-    return kLdsCubics + kLdsEm + kLdsWeights + kTeamXchg + (expect ? kExpectCopies * 80 : 0);
+    return kLdsCubics + kLdsWeights + kTeamXchg + (expect ? kExpectCopies * 80 : 0);
 }
 
 // EMIT (round 4): CPECAN_EMIT_MATCH, or CPECAN_EMIT_INDEL -- the three lists of diagonalCalculationPosteriorProbs
@@ -44,17 +44,15 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
     int curSlot = 0;
     const int stride = a.geo.rollStride;
 
-    // LDS (doubles): logAdd cubics | emissions | weights | exchange area | rolling rows | symbol strings
-    logadd_fp_mode();  // (every wave: fill_cubics below sets it for the one wave that fills the table)
+    // LDS (doubles): logAdd cubics | weights | exchange area | rolling rows | symbol strings
     if (wave == 0) {
         fill_cubics(lds);
-        if constexpr (SLOTS) fill_weights<S>(lds + kLdsCubics + kLdsEm, *mp, a.slotModels[0].kc, lane);
-        else fill_weights<S>(lds + kLdsCubics + kLdsEm, *mp, a.kc, lane);
+        if constexpr (SLOTS) fill_weights<S>(lds + kLdsCubics, *mp, a.slotModels[0].kc, lane);
+        else fill_weights<S>(lds + kLdsCubics, *mp, a.kc, lane);
     }
     const Cubic *lg = reinterpret_cast<const Cubic *>(lds);
-    double *em = lds + kLdsCubics;
-    double *wt = lds + kLdsCubics + kLdsEm;
-    int *xi = reinterpret_cast<int *>(lds + kLdsCubics + kLdsEm + kLdsWeights);  // [0]: ticket, [8 + parity * T + w]: counts
+    double *wt = lds + kLdsCubics;
+    int *xi = reinterpret_cast<int *>(lds + kLdsCubics + kLdsWeights);  // [0]: ticket, [8 + parity * T + w]: counts
     float *xf = reinterpret_cast<float *>(xi + 8 + 2 * NL * T);              // [parity * T + w]: maxima (counts: [8 + (parity * NL + l) * T + w])
     double *eLds = lds + team_header_doubles();  // (expectation emitter only)
     double *roll = lds + team_header_doubles(kExpect);
@@ -126,7 +124,7 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
                 for (int i = tid; i < kExpectCopies * 80; i += CPK_WAVE * T) eLds[i] = 0.0;
                 curSlot = vs;
                 mp = &a.slotModels[vs].m;
-                if (wave == 0) fill_weights<S>(lds + kLdsCubics + kLdsEm, *mp, a.slotModels[vs].kc, lane);
+                if (wave == 0) fill_weights<S>(lds + kLdsCubics, *mp, a.slotModels[vs].kc, lane);
                 __syncthreads();
             }
         } else if (tk >= a.regionCount) break;
@@ -145,7 +143,6 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
                   seqLds,
                   seqLds + ((lX + 3) >> 1),
                   roll,
-                  em,
                   wt,
                   lg,
                   a.ring + slot * (size_t)a.geo.ringCells * S,
@@ -169,12 +166,6 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
         int count[NL];
 #pragma unroll
         for (int l = 0; l < NL; l++) count[l] = 0;
-#ifdef CPK_DIAGNOSTICS
-        if (a.geo.debug & 4) {  // diagnostic build (CPECAN_DEBUG_SKIP=4): regions are fetched and staged, nothing is computed
-            if (tid == 0) a.outCounts[r] = 0;
-            continue;
-        }
-#endif
         if (N > 0) {
             sw.dc.load(0);
             const double *startPrior = rg.raggedLeft ? mp->raggedStart : mp->start;
@@ -239,9 +230,6 @@ __global__ void __launch_bounds__(CPK_WAVE *T) cpecan_pairhmm_team(const KArgs a
                         f1 = g;
                     }
                 }
-#ifdef CPK_DIAGNOSTICS
-                if (a.geo.debug & 2) continue;  // diagnostic (CPECAN_DEBUG_SKIP=2): the forward sweep alone, no output
-#endif
                 // ---- traceback of the segment (pairwiseAligner.c:796-862) ----
                 const double *endPrior = (sg.atEnd && rg.raggedRight) ? mp->raggedEnd : mp->end;
                 double ep[S];

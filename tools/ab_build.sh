@@ -1,10 +1,8 @@
 #!/bin/bash
-# builds an alternative libcpecan_hip.so with extra -D flags into build_ab/<tag>.so (for A/B timing in ONE gpurun call:
-# boxes differ by several % in clock, so variants are only comparable within a call).  usage: tools/ab_build.sh tag -DX=1 ...
+# builds an alternative libcpecan_hip.so with extra -D flags into build_ab/<tag>.so (for A/B timing in ONE call on the GPU
+# box: boxes differ by several % in clock, so variants are only comparable within a call).  usage: tools/ab_build.sh tag -DX=1 ...
+# The recipe is the `ab` target of cpecan_amd/csrc/Makefile: the same host objects as the shipped library.
 set -e
 tag=$1; shift
-cd "$(dirname "$0")/../cpecan_amd/csrc"
-mkdir -p ../../build_ab
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Wno-unused-function -Wno-pass-failed -I../../include -I. "$@" -c -o /tmp/ab_$tag.o cpecan_kernels.hip
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../build_ab/$tag.so cpecan_host.o cpecan_dropin.o cpecan_realign.o cpecan_em.o cpecan_anchor.o /tmp/ab_$tag.o -lm -lgomp -lpthread
+make -C "$(dirname "$0")/../cpecan_amd/csrc" ab AB_TAG="$tag" AB_FLAGS="$*"
 echo built build_ab/$tag.so
