@@ -951,6 +951,12 @@ static int64_t *unaligned_mass(const int64_t *triples, int64_t n, int64_t len, i
     return mass;
 }
 
+void orc_indel_probabilities(const int64_t *triples, int64_t n, int64_t len, int byX, int64_t *out) {
+    int64_t *mass = unaligned_mass(triples, n, len, byX ? 1 : 2);
+    for (int64_t i = 0; i < len; i++) out[i] = mass[i];
+    free(mass);
+}
+
 void orc_reweight_aligned_pairs(int64_t *triples, int64_t n, int64_t lX, int64_t lY, double gapGamma) {
     if (gapGamma <= 0.0) return; /* :1551 */
     int64_t *mx = unaligned_mass(triples, n, lX, 1), *my = unaligned_mass(triples, n, lY, 2);

@@ -7,14 +7,17 @@
  * only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it.
  * The product library (cpecan_amd/csrc) never links, includes or calls anything here.
  *
- * Parity pin: the reference cannot be compiled in this image (it needs the
- * un-vendored sibling library sonLib, include.mk:2-9), so this oracle is pinned by
+ * Parity pin: this oracle is pinned by
  * (a) every fixed-input fixture of the reference's own tests
  *     (tests/pairwiseAlignerTest.c: test_diagonal :17, test_bands :69, test_symbol :146,
  *      test_cell :155, test_diagonalDPCalculations :242, test_getSplitPoints :578,
- *      test_hmm :997) and
- * (b) the known answers the survey recorded from the reference.
- * See tests/test_oracle_golden.py.
+ *      test_hmm :997),
+ * (b) the known answers the survey recorded from the reference
+ *     -- tests/test_oracle_golden.py -- and
+ * (c) records of the reference's own impl/pairwiseAligner.c and impl/stateMachine.c, built on the stand-in
+ *     headers of ref_standin/ (Makefile target `ref`, ref_driver.c) and run on small constructed inputs:
+ *     tests/golden/reference_runs.json.gz, which tests/test_reference_runs_cpu.py requires of this oracle
+ *     list for list and double for double, bit for bit.
  *
  * All arrays are flat; all functions are re-entrant.
  */
@@ -162,10 +165,14 @@ int64_t orc_batch_expectations(const OrcModel *m, OrcHmm *acc, const char *seqBl
 
 /* ---- consumers of the posterior lists.  Triples are (score, x, y) int64. ----
  * Pinning: orc_left_shift_alignment is pinned by the reference's test vector (tests/pairwiseAlignerTest.c:944-995).
- * The reference has no test of reweightAlignedPairs2 or of the MEA chain: those two restatements are checked by
- * hand-worked cases and an independent chain DP only -- PARITY UNPINNED for them. */
+ * The reference has no test of reweightAlignedPairs2 or of the MEA chain: those two restatements are pinned by the
+ * records of the reference's own run (tests/golden/reference_runs.json.gz), as are the left shift, the four scores and
+ * filterToRemoveOverlap. */
 /* reweightAlignedPairs2, impl/pairwiseAligner.c:1519-1558: in place; gapGamma <= 0 leaves the list unchanged. */
 void orc_reweight_aligned_pairs(int64_t *triples, int64_t n, int64_t lX, int64_t lY, double gapGamma);
+/* getIndelProbabilities, :1519-1534: what reweightAlignedPairs2 takes off each weight, per base of X (byX) or of Y; out
+ * holds len entries. */
+void orc_indel_probabilities(const int64_t *triples, int64_t n, int64_t len, int byX, int64_t *out);
 /* scoreByPosteriorProbability / scoreByPosteriorProbabilityIgnoringGaps, :1578-1597 */
 double orc_score_by_posterior(int64_t lX, int64_t lY, const int64_t *triples, int64_t n);
 double orc_score_by_posterior_ignoring_gaps(const int64_t *triples, int64_t n);

@@ -116,6 +116,7 @@ def lib():
         L.orc_batch_expectations.argtypes = [C.POINTER(Model), C.POINTER(Hmm), C.c_char_p, i64p, i64p, i64p, C.c_int64,
                                              C.POINTER(Params), C.c_int, C.c_int, C.c_int]
         L.orc_reweight_aligned_pairs.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int64, C.c_double]
+        L.orc_indel_probabilities.argtypes = [i64p, C.c_int64, C.c_int64, C.c_int, i64p]
         L.orc_score_by_posterior.restype = C.c_double
         L.orc_score_by_posterior.argtypes = [C.c_int64, C.c_int64, i64p, C.c_int64]
         L.orc_score_by_posterior_ignoring_gaps.restype = C.c_double
@@ -336,6 +337,14 @@ def reweight_aligned_pairs(pairs, lX, lY, gap_gamma):
     a = a.copy()
     lib().orc_reweight_aligned_pairs(a.ctypes.data_as(C.POINTER(C.c_int64)), n, lX, lY, float(gap_gamma))
     return a
+
+
+def indel_probabilities(pairs, length, by_x):
+    """getIndelProbabilities: int64[length], per base of X (by_x) or of Y."""
+    a, ptr, n = _triples(pairs)
+    out = np.zeros(max(length, 1), dtype=np.int64)
+    lib().orc_indel_probabilities(ptr, n, length, int(by_x), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    return out[:length].copy()
 
 
 def score_by_posterior(lX, lY, pairs):
