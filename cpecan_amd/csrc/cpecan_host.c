@@ -1710,6 +1710,15 @@ int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t
     return rc;
 }
 
+/* For tests: the launches the uploaded batch really has, as its device planned them (cpk_plan_describe's numbers).
+ * (A weak reference, as cpk_plan_describe above: a stand-in for the device layer need not have it.) */
+extern __typeof__(cpk_device_launch_forms) cpk_device_launch_forms __attribute__((weak));
+int cpk_batch_launch_forms(cpecan_batch *b, int64_t *out, int maxClasses) {
+    if (!b || !out || !b->frozen || dl_busy(b) || !cpk_device_launch_forms) return CPECAN_ESTATE;
+    if (b->nRegions == 0 || !b->dev) return 0;
+    return cpk_device_launch_forms(b->dev, out, maxClasses);
+}
+
 int cpecan_batch_upload(cpecan_batch *b) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || b->frozen) return CPECAN_ESTATE;

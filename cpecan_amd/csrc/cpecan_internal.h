@@ -257,11 +257,24 @@ int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offse
  * numCUs compute units and memBytes of free memory that is not there: a kernel is taken to use the registers its build
  * allows.  out receives CPK_LAUNCH_PLAN_FIELDS numbers per launch class, in launch order (cpk_plan_describe); returns
  * the number of classes, or an error code (< 0).  For tests: the plan is dropped again. */
-#define CPK_LAUNCH_PLAN_FIELDS 24
+#define CPK_LAUNCH_PLAN_FIELDS 25
 int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *out, int maxClasses);
 int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, int dynamic, int64_t nDiags, int64_t nSegs, int64_t nSymbolBytes,
                       int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs, int64_t memBytes,
                       int64_t *out, int maxClasses);
+/* The plan an uploaded batch really got (valid after cpecan_batch_upload): the launch classes of its device, planned with
+ * the registers and static LDS the loaded kernels report -- the same CPK_LAUNCH_PLAN_FIELDS numbers per class, in the same
+ * order; returns the number of classes (0: a batch without regions), or an error code (< 0).  For tests.  The classes
+ * are shown as they stand: after a download that re-ran a one-launch class in two launches (an item gave up waiting,
+ * cpk_device_download) that class has the two-launch form, so reading the plan again behind the download tells whether
+ * the one launch produced the results. */
+int cpk_batch_launch_forms(cpecan_batch *b, int64_t *out, int maxClasses);
+int cpk_device_launch_forms(const CpkDevice *dev, int64_t *out, int maxClasses);
+/* The table of kernel variants that are built (cpk_kernel_table.inl) as data, CPK_KERNEL_FORM_FIELDS numbers per entry:
+ * family, S, emit, mode, fast, wps, abs, inSweep, slots, dynamic, width, gang.  Returns the number of entries, or
+ * CPECAN_EINVAL where maxEntries is too few.  No device needed. */
+#define CPK_KERNEL_FORM_FIELDS 12
+int cpk_kernel_table_forms(int64_t *out, int maxEntries);
 
 /* ---- the anchor finder (cpk_anchor.inl; host side in cpecan_anchor.c) ---- */
 /* One problem of an anchor pass: two substrings of the context's symbol buffer.  The host fills the first block, the

@@ -931,6 +931,21 @@ static void count_waves(CpkDevice *d) {
         d->totalWaves += (c.split() && c.wavesTrace > c.waves ? c.wavesTrace : c.wavesWith(d->activeModels)) * (c.threads / CPK_WAVE);
 }
 
+// CPK_LAUNCH_PLAN_FIELDS numbers per class, in launch order: what cpk_plan_describe and cpk_device_launch_forms answer.
+static int describe_classes(const std::vector<LaunchClass> &classes, int64_t *out, int maxClasses) {
+    if ((int)classes.size() > maxClasses) return CPECAN_EINVAL;
+    for (size_t i = 0; i < classes.size(); i++) {
+        const LaunchClass &c = classes[i];
+        const int64_t f[CPK_LAUNCH_PLAN_FIELDS] = {
+            c.packed, c.k, c.regionCount, c.geo.maxWidth, c.geo.nStates, c.form.family, c.form.mode, c.form.wps, c.form.abs, c.form.gang,
+            c.split() && !c.fused() ? c.formTrace.wps : 0, c.split() && !c.fused() ? c.formTrace.gang : 0, c.waves, c.wavesTrace, c.gang,
+            c.gangTrace, (int64_t)c.ldsBytes, (int64_t)c.ldsBytesFwd, (int64_t)c.firstLdsBytes(), (int64_t)c.traceLdsBytes(), c.subSlots,
+            c.threads, c.itemCount, c.firstGrid(1), c.geo.useGlobalRoll};
+        for (int j = 0; j < CPK_LAUNCH_PLAN_FIELDS; j++) out[i * CPK_LAUNCH_PLAN_FIELDS + j] = f[j];
+    }
+    return (int)classes.size();
+}
+
 // The launches of a batch on a device that is not there (tests of the plan): CPK_LAUNCH_PLAN_FIELDS numbers per class.
 extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, int dynamic, int64_t nDiags, int64_t nSegs,
                                  int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
@@ -943,17 +958,21 @@ extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *region
     const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
     std::vector<LaunchClass> classes;
     if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, modelSlots, &classes)) return rc;
-    if ((int)classes.size() > maxClasses) return CPECAN_EINVAL;
-    for (size_t i = 0; i < classes.size(); i++) {
-        const LaunchClass &c = classes[i];
-        const int64_t f[CPK_LAUNCH_PLAN_FIELDS] = {
-            c.packed, c.k, c.regionCount, c.geo.maxWidth, c.geo.nStates, c.form.family, c.form.mode, c.form.wps, c.form.abs, c.form.gang,
-            c.split() && !c.fused() ? c.formTrace.wps : 0, c.split() && !c.fused() ? c.formTrace.gang : 0, c.waves, c.wavesTrace, c.gang,
-            c.gangTrace, (int64_t)c.ldsBytes, (int64_t)c.ldsBytesFwd, (int64_t)c.firstLdsBytes(), (int64_t)c.traceLdsBytes(), c.subSlots,
-            c.threads, c.itemCount, c.firstGrid(1)};
-        for (int j = 0; j < CPK_LAUNCH_PLAN_FIELDS; j++) out[i * CPK_LAUNCH_PLAN_FIELDS + j] = f[j];
+    return describe_classes(classes, out, maxClasses);
+}
+// ... and of an uploaded batch on the device it was planned for, with the registers the loaded kernels report: the same numbers.
+extern "C" int cpk_device_launch_forms(const CpkDevice *d, int64_t *out, int maxClasses) { return describe_classes(d->classes, out, maxClasses); }
+// kKernelTable as data (tests: every built variant has a test that runs it): CPK_KERNEL_FORM_FIELDS numbers per entry, the
+// fields of KernelForm in their order; returns the number of entries.  No device needed.
+extern "C" int cpk_kernel_table_forms(int64_t *out, int maxEntries) {
+    const int n = (int)(sizeof kKernelTable / sizeof kKernelTable[0]);
+    if (n > maxEntries) return CPECAN_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const KernelForm &k = kKernelTable[i].form;
+        const int64_t f[CPK_KERNEL_FORM_FIELDS] = {k.family, k.S, k.emit, k.mode, k.fast, k.wps, k.abs, k.inSweep, k.slots, k.dynamic, k.width, k.gang};
+        for (int j = 0; j < CPK_KERNEL_FORM_FIELDS; j++) out[i * CPK_KERNEL_FORM_FIELDS + j] = f[j];
     }
-    return (int)classes.size();
+    return n;
 }
 
 // Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch).

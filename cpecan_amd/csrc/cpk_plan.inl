@@ -108,6 +108,7 @@ struct PlanKnobs {
     Knob<int> expInSweep{"CPECAN_EXP_INSWEEP"};  // =0 (tests, A/B runs): expectation events by the second pass everywhere; 2: inside the traceback whatever the LDS costs
     Knob<int> expOneGroup{"CPECAN_EXP_ONE_GROUP"};  // =0: always the expectation build for two groups per diagonal
     Knob<int> team{"CPECAN_TEAM"};  // =<cells> (tests, diagnostics): a team of waves from that band width; 0: never
+    // (the match suite -- tests/match_cases.py -- sets CPECAN_DENSE, CPECAN_FUSED3, CPECAN_TRACE3 and CPECAN_FWD3 to reach every build of the match kernels for two and for three waves per SIMD)
     Knob<int> dense{"CPECAN_DENSE"};  // =1 / 0: the three-state kernels allocated for three waves per SIMD always / never
     Knob<int> fusedSpin{"CPECAN_FUSED_SPIN"};  // polls of a fused item for its region's forward values (tests force the retry with a few)
     Knob<int> fused3{"CPECAN_FUSED3"};  // =0: never the three-waves-per-SIMD build of the one-launch form

@@ -10,7 +10,7 @@ from cpecan_amd.workload import CONFIGS, config_problems, make_batch, make_pair
 
 FIELDS = ("packed", "k", "regions", "maxWidth", "nStates", "family", "mode", "wps", "abs", "gang", "traceWps", "traceGang", "waves",
           "wavesTrace", "gangWaves", "gangWavesTrace", "ldsBytes", "ldsBytesFwd", "firstLdsBytes", "traceLdsBytes", "subSlots",
-          "threads", "items", "firstGrid")
+          "threads", "items", "firstGrid", "globalRows")
 CUS = 256
 CU_LDS = 160 * 1024
 TABLES = 8 * (64 + 168)  # logAdd cubics + (emission + transition) sums: what a gang keeps once

@@ -29,6 +29,10 @@ pytestmark = pytest.mark.gpu
 
 SIZES = (2, 3, 11)
 SHORT = dict(minDiagsBetweenTraceBack=50, traceBackDiagonals=7)  # a traceback every 42 diagonals of a narrow band
+# A diagonal is a traceback point only if it has at most 2 * diagonalExpansion + 1 cells (pairwiseAligner.c:792-793).  Under the
+# default expansion of 20 an unanchored region wider than 41 cells therefore has two segments, one across all its wide
+# diagonals; under 130 every diagonal of the shapes below is a permitted point and a region has a segment every 42 diagonals.
+WIDTH_EXPANSIONS = (20, 130)
 # every region in a wide class (no packed kernel), every class with a traceback in two launches; CPECAN_ABS at its default
 BASE_ENV = {"CPECAN_PACKED": "0", "CPECAN_SPLIT": "1", "CPECAN_TRACE_HOST": "1"}
 
@@ -111,8 +115,12 @@ def _width_problems(width):
 # ---- the private block's size and alignment change with the widest diagonal; both state counts ----
 @pytest.mark.parametrize("width,mtype", [(1, 0), (63, 0), (64, 2), (65, 0), (65, 2), (127, 0), (128, 2), (129, 0), (157, 0), (157, 2)])
 def test_widest_diagonals_around_the_groups(width, mtype, monkeypatch, capfd):
+    """Two runs (WIDTH_EXPANSIONS): two segments per region, whose hand-off lies on a diagonal of at most 41 cells, and many
+    segments per region -- at least (lX + lY) / 50, tests/test_match_cases_cpu.py --, which hand over on the widest diagonals."""
     # (diagonals of one cell: one of the two sequences is empty, the sweeps run and there is no match cell to emit)
-    _check(monkeypatch, capfd, mtype, _width_problems(width), dict(threshold=0.01, **SHORT), oracle=(1,), emits=width > 1)
+    for expansion in WIDTH_EXPANSIONS:
+        _check(monkeypatch, capfd, mtype, _width_problems(width), dict(threshold=0.01, diagonalExpansion=expansion, **SHORT), oracle=(1,),
+               emits=width > 1)
 
 
 # ---- fewer regions than waves: most waves of the workgroup find the queue empty at once ----

@@ -10,8 +10,16 @@ agree with the oracle.  The shapes: unanchored pairs, so the whole matrix is the
 min(lX, lY) + 1 cells; lX - lY = 17, so 18 consecutive diagonals have exactly that width and, with a refresh point every
 tenth emitted diagonal, at least one of them is a refresh point.  Widths 63, 64, 65 / 127, 128, 129 / 191, 192, 193 put the
 refresh diagonals into one, two and three groups of 64 lanes with 63, 0 and 1 cells in the last; 193, 255 and 257 are wider
-than the three prefetched groups.  A traceback every 42 diagonals, so every region has many segments; the last segment of
-every region starts on a refresh point, and the 8-base region (33 diagonals) is nothing but that segment."""
+than the three prefetched groups.
+
+Every case runs under two band expansions (EXPANSIONS).  A diagonal is a traceback point only if it has at most
+2 * diagonalExpansion + 1 cells (pairwiseAligner.c:792-793), so under the default expansion of 20 no diagonal wider than 41
+cells is one: every region from width 25 up has exactly two segments, one of which spans all its wide diagonals, and the
+9-cell region has one.  Under an expansion of 130 every diagonal of every region is a permitted traceback point: a
+traceback every 42 diagonals, so every region has many segments -- 4, 7, 10, 13 for widths 65, 129, 193, 257
+(tests/test_match_cases_cpu.py asserts at least (lX + lY) / 50) --, a segment hands over to the next on diagonals of
+63, 64, 65, ... cells, the last segment of every region starts on a refresh point, and the 8-base region (33 diagonals) is
+nothing but that segment."""
 import functools
 import os
 import subprocess
@@ -22,6 +30,7 @@ import pytest
 import oracle_binding as ob
 import table_cases as tc
 from cpecan_amd import api
+from match_cases import GAP, pair as _pair  # the pair family: shared with the match suite
 from parity import assert_pairs_match
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,39 +40,25 @@ BASE_ENV = {"CPECAN_PACKED": "0", "CPECAN_SPLIT": "1"}
 FORMS = [(abs_, gang) for abs_ in (None, "0") for gang in ("0", "11")]  # (CPECAN_ABS, CPECAN_GANG); None: the default
 WIDTHS = (9, 25, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 257)
 DEBUG_WIDTHS = (9, 64, 129, 191, 257)
-GAP = 17
+EXPANSIONS = (20, 130)  # two segments per region (none ends on a diagonal wider than 41 cells) / a segment every 42 diagonals
 
 
 def _sm(mtype):
     return api.stateMachine5_construct(mtype) if mtype in (0, 1) else api.stateMachine3_construct(mtype)
 
 
-@functools.lru_cache(maxsize=None)
-def _pair(width):
-    """A pair of related sequences of width - 1 + GAP and width - 1 bases: sY is sX without GAP bases, one at a time and
-    evenly spread, and with every 11th base replaced."""
-    m = width - 1
-    sx = tc.seq(m + GAP, 7)
-    drop = {(i + 1) * (m + GAP) // (GAP + 1) for i in range(GAP)}
-    assert len(drop) == GAP
-    sy = [c for i, c in enumerate(sx) if i not in drop]
-    for i in range(5, len(sy), 11):
-        sy[i] = "ACGT"[("ACGT".index(sy[i]) + 1) % 4]
-    return sx, "".join(sy), ()
-
-
 def _problems():
     return [_pair(w) for w in WIDTHS]
 
 
-def _pkw(threshold):
-    return dict(threshold=threshold, **SHORT)
+def _pkw(threshold, expansion=EXPANSIONS[0]):
+    return dict(threshold=threshold, diagonalExpansion=expansion, **SHORT)
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle(mtype, threshold, width):
+def _oracle(mtype, threshold, width, expansion=EXPANSIONS[0]):
     sx, sy, a = _pair(width)
-    return ob.aligned_pairs(ob.model(mtype), sx, sy, a, ob.params(**_pkw(threshold)))
+    return ob.aligned_pairs(ob.model(mtype), sx, sy, a, ob.params(**_pkw(threshold, expansion)))
 
 
 @pytest.mark.parametrize("mtype", [0, 2])
@@ -73,8 +68,9 @@ def test_every_problem_emits_pairs(mtype, threshold):
     for w in WIDTHS:
         sx, sy, _ = _pair(w)
         assert (len(sx), len(sy)) == (w - 1 + GAP, w - 1)
-        n = len(_oracle(mtype, threshold, w))
-        assert n >= 1 and (w < 60 or n >= (w - 1) // 2), (w, n)
+        for expansion in EXPANSIONS:
+            n = len(_oracle(mtype, threshold, w, expansion))
+            assert n >= 1 and (w < 60 or n >= (w - 1) // 2), (w, expansion, n)
 
 
 def _set_form(monkeypatch, form):
@@ -117,28 +113,37 @@ def test_wave_max_program(tmp_path):
 @pytest.mark.parametrize("mtype", [0, 2])
 @pytest.mark.parametrize("threshold", [0.01, 0.0])
 def test_lists_are_the_same_bits_in_every_form(mtype, threshold, monkeypatch):
-    problems, pkw = _problems(), _pkw(threshold)
-    want = None
-    for form in FORMS:
-        _set_form(monkeypatch, form)
-        got, _ = _run(mtype, problems, pkw)
-        assert all(len(g) for g in got), (form, [len(g) for g in got])
-        if want is None:
-            want = got
-            continue
-        for w, a, b in zip(WIDTHS, got, want):
-            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), "width %d: %r differs from %r" % (w, form, FORMS[0])
-    for w, g in zip(WIDTHS, want):  # one problem per shape -- every one of them -- against the oracle
-        assert_pairs_match(g, _oracle(mtype, threshold, w), threshold=threshold)
+    """Both expansions: two segments per region, and a segment every 42 diagonals (the module's docstring)."""
+    for expansion in EXPANSIONS:
+        problems, pkw = _problems(), _pkw(threshold, expansion)
+        want = None
+        for form in FORMS:
+            _set_form(monkeypatch, form)
+            got, _ = _run(mtype, problems, pkw)
+            assert all(len(g) for g in got), (form, [len(g) for g in got])
+            if want is None:
+                want = got
+                continue
+            for w, a, b in zip(WIDTHS, got, want):
+                assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), \
+                    "width %d, expansion %d: %r differs from %r" % (w, expansion, form, FORMS[0])
+        for w, g in zip(WIDTHS, want):  # one problem per shape -- every one of them -- against the oracle
+            assert_pairs_match(g, _oracle(mtype, threshold, w, expansion), threshold=threshold)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mtype", [0, 2])
 @pytest.mark.parametrize("width", DEBUG_WIDTHS)
 def test_debug_buffers_are_the_same_bits_in_every_form(width, mtype, monkeypatch):
+    """Both expansions, as above: with the wider one the segments of a region hand over on its widest diagonals."""
+    for expansion in EXPANSIONS:
+        _debug_buffers_in_every_form(width, mtype, expansion, monkeypatch)
+
+
+def _debug_buffers_in_every_form(width, mtype, expansion, monkeypatch):
     from parity import LOG_TOL
     sx, sy, a = _pair(width)
-    pkw = _pkw(0.01)
+    pkw = _pkw(0.01, expansion)
     _, tr = ob.aligned_pairs_traced(ob.model(mtype), sx, sy, a, ob.params(**pkw), False, False)
     cells = (tr["n_cells"], tr["n_diagonals"])
     first = None
