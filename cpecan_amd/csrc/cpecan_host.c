@@ -1704,8 +1704,25 @@ int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t
     CpkModel km;
     int rc = batch_plan(b, &hp, &geo, &km);
     if (rc == CPECAN_OK)
-        rc = cpk_plan_describe(&geo, hp.devRegions, hp.dynamic, hp.totalDiags, hp.nSegs, b->nSymbols, b->nAnchorVals / b->anchorStride,
+        rc = cpk_plan_describe(&geo, hp.devRegions, hp.segs, hp.dynamic, hp.totalDiags, hp.nSegs, b->nSymbols, b->nAnchorVals / b->anchorStride,
                                hp.outTriples, b->nLists, b->modelSlots, numCUs, memBytes, out, maxClasses);
+    host_plan_free(&hp);
+    return rc;
+}
+/* ... and the chains of that plan with its traceback queues (cpecan_internal.h). */
+extern __typeof__(cpk_plan_chains) cpk_plan_chains __attribute__((weak));
+int cpk_batch_chain_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut,
+                         int64_t maxItems, int64_t *nItems) {
+    if (!b || !chainsOut || b->frozen || dl_busy(b) || !cpk_plan_chains) return CPECAN_ESTATE;
+    if (nItems) *nItems = 0;
+    if (b->nRegions == 0) return 0;
+    HostPlan hp;
+    CpkGeometry geo;
+    CpkModel km;
+    int rc = batch_plan(b, &hp, &geo, &km);
+    if (rc == CPECAN_OK)
+        rc = cpk_plan_chains(&geo, hp.devRegions, hp.segs, hp.dynamic, hp.totalDiags, hp.nSegs, b->nSymbols, b->nAnchorVals / b->anchorStride,
+                             hp.outTriples, b->nLists, b->modelSlots, numCUs, memBytes, chainsOut, maxClasses, itemsOut, maxItems, nItems);
     host_plan_free(&hp);
     return rc;
 }

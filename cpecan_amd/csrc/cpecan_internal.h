@@ -40,7 +40,9 @@ typedef struct {
     int32_t emitCells; /* band cells on the emitted diagonals tbPrev+1..tbFrom: no list of the segment can be longer */
 } CpkSegment;
 
-/* One traceback work item of a split class: segment `seg` (index within its region) of device region `region`. */
+/* One traceback work item of a split class: segment `seg` (index within its region) of device region `region`.
+ * seg = -K < 0: a CHAIN -- the forward sweep of the region's segments K .. last, resumed from the two diagonals the ring
+ * holds at the top of segment K - 1, and then their tracebacks, by one wave (cpk_sweep.inl "CHAIN"; cpk_plan.inl). */
 typedef struct {
     int32_t region, seg;
 } CpkItem;
@@ -256,12 +258,29 @@ int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offse
 /* Plans an unfrozen batch as cpecan_batch_upload would and then its launches (cpk_plan.inl, plan_batch) for a device of
  * numCUs compute units and memBytes of free memory that is not there: a kernel is taken to use the registers its build
  * allows.  out receives CPK_LAUNCH_PLAN_FIELDS numbers per launch class, in launch order (cpk_plan_describe); returns
- * the number of classes, or an error code (< 0).  For tests: the plan is dropped again. */
+ * the number of classes, or an error code (< 0).  For tests: the plan is dropped again.
+ * The 23rd number counts the traceback SEGMENTS the class's queue hands out.  Without chains that is the length of the queue;
+ * a chain item (below) counts as the segments it covers, so the number is the same with and without chains.  The length
+ * of the queue itself is what cpk_batch_chain_plan returns in *nItems (and per class by counting its item records). */
 #define CPK_LAUNCH_PLAN_FIELDS 25
 int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *out, int maxClasses);
-int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, int dynamic, int64_t nDiags, int64_t nSegs, int64_t nSymbolBytes,
-                      int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs, int64_t memBytes,
-                      int64_t *out, int maxClasses);
+int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
+                      int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
+                      int64_t memBytes, int64_t *out, int maxClasses);
+/* The chains of the same plan (cpk_plan.inl, plan_chains), beside cpk_batch_launch_plan, whose record keeps its layout:
+ * chainsOut receives CPK_CHAIN_PLAN_FIELDS numbers per launch class, in launch order -- the first segment of the class's
+ * chains (0: it has none) and their number.  itemsOut (may be null) receives the traceback queues built from the plan,
+ * CPK_CHAIN_ITEM_FIELDS numbers per item in queue order -- class, device region, segment (-K: a chain from segment K), cost in
+ * cells, segments of the region, leading segments of the region that the forward launch sweeps --, at most maxItems of them;
+ * *nItems their number.  Returns the number of classes, or an
+ * error code (< 0).  For tests: the plan is dropped again. */
+#define CPK_CHAIN_PLAN_FIELDS 2
+#define CPK_CHAIN_ITEM_FIELDS 6
+int cpk_batch_chain_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut,
+                         int64_t maxItems, int64_t *nItems);
+int cpk_plan_chains(const CpkGeometry *geo, CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
+                    int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
+                    int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut, int64_t maxItems, int64_t *nItems);
 /* The plan an uploaded batch really got (valid after cpecan_batch_upload): the launch classes of its device, planned with
  * the registers and static LDS the loaded kernels report -- the same CPK_LAUNCH_PLAN_FIELDS numbers per class, in the same
  * order; returns the number of classes (0: a batch without regions), or an error code (< 0).  For tests.  The classes
@@ -272,9 +291,11 @@ int cpk_batch_launch_forms(cpecan_batch *b, int64_t *out, int maxClasses);
 int cpk_device_launch_forms(const CpkDevice *dev, int64_t *out, int maxClasses);
 /* The table of kernel variants that are built (cpk_kernel_table.inl) as data, CPK_KERNEL_FORM_FIELDS numbers per entry:
  * family, S, emit, mode, fast, wps, abs, inSweep, slots, dynamic, width, gang.  Returns the number of entries, or
- * CPECAN_EINVAL where maxEntries is too few.  No device needed. */
+ * CPECAN_EINVAL where maxEntries is too few.  No device needed.  cpk_kernel_table_chain: in step with it, one number per
+ * entry -- 1 for a CHAIN build (KernelForm::chain), which the twelve fields do not tell from the gang it stands in for. */
 #define CPK_KERNEL_FORM_FIELDS 12
 int cpk_kernel_table_forms(int64_t *out, int maxEntries);
+int cpk_kernel_table_chain(int64_t *out, int maxEntries);
 
 /* ---- the anchor finder (cpk_anchor.inl; host side in cpecan_anchor.c) ---- */
 /* One problem of an anchor pass: two substrings of the context's symbol buffer.  The host fills the first block, the

@@ -891,8 +891,11 @@ static int stage_reserve(CpkDevice *d, size_t bytes) {
 }
 
 // split classes: the regions get rings of their own (no wrap: every segment stays readable) and their tracebacks
-// become queue items, longest first
-static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regions, const CpkSegment *segs, int S, std::vector<CpkItem> *items) {
+// become queue items, longest first.  A class with chains (plan_chains): one chain item (seg = -chainFrom) for every region
+// with more than chainFrom segments in place of the plain items of those segments, in the same list by the same measure.
+// costs (tests): the measure of every item, in step with *items.
+static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regions, const CpkSegment *segs, int S, std::vector<CpkItem> *items,
+                             std::vector<int64_t> *costs = nullptr) {
     for (LaunchClass &c : classes) {
         if (!c.split()) continue;
         int64_t ringAt = 0;  // in doubles, from the class's ring pointer (dRing + oRing)
@@ -904,16 +907,21 @@ static void build_item_queue(std::vector<LaunchClass> &classes, CpkRegion *regio
             rg.ringBase = ringAt;
             rg.split = 1;
             ringAt += split_ring_doubles(rg, S);
-            for (int32_t si = 0; si < rg.nSeg; si++) {
+            const bool chained = c.chainFrom > 0 && rg.nSeg > c.chainFrom;
+            if (chained) byCost.push_back({chain_cost(rg, segs, c.chainFrom), CpkItem{(int32_t)di, -c.chainFrom}});
+            for (int32_t si = 0; si < (chained ? c.chainFrom : rg.nSeg); si++) {
                 const CpkSegment &sg = segs[rg.segOff + si];
                 // fused: a segment's forward values exist when the forward wave has passed its top diagonal -- items in
                 // the order in which they become ready (that diagonal), longest first among equals
-                const int64_t cost = (int64_t)(sg.dTop - sg.tbPrev) * rg.maxWidth;
+                const int64_t cost = item_cost(rg, sg);
                 byCost.push_back({c.fused() ? ((int64_t)0x7fffffff - sg.dTop) * ((int64_t)1 << 32) + (cost >> 8) : cost, CpkItem{(int32_t)di, si}});
             }
         }
         std::stable_sort(byCost.begin(), byCost.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
-        for (const auto &e : byCost) items->push_back(e.second);
+        for (const auto &e : byCost) {
+            items->push_back(e.second);
+            if (costs) costs->push_back(e.first);
+        }
         c.itemCount = (int64_t)items->size() - c.itemBase;
     }
 }
@@ -932,6 +940,9 @@ static void count_waves(CpkDevice *d) {
 }
 
 // CPK_LAUNCH_PLAN_FIELDS numbers per class, in launch order: what cpk_plan_describe and cpk_device_launch_forms answer.
+// (The 23rd number, "items" to the tests, is the TRACEBACK SEGMENTS the class's queue hands out, not the queue's length: a
+// chain counts as the segments it covers, so the number does not move with the chains -- tests/test_gang_plan_cpu.py holds
+// the default plan to that of CPECAN_GANG=0 in it.  The length of the queue itself: cpk_plan_chains, *nItems.)
 static int describe_classes(const std::vector<LaunchClass> &classes, int64_t *out, int maxClasses) {
     if ((int)classes.size() > maxClasses) return CPECAN_EINVAL;
     for (size_t i = 0; i < classes.size(); i++) {
@@ -940,30 +951,79 @@ static int describe_classes(const std::vector<LaunchClass> &classes, int64_t *ou
             c.packed, c.k, c.regionCount, c.geo.maxWidth, c.geo.nStates, c.form.family, c.form.mode, c.form.wps, c.form.abs, c.form.gang,
             c.split() && !c.fused() ? c.formTrace.wps : 0, c.split() && !c.fused() ? c.formTrace.gang : 0, c.waves, c.wavesTrace, c.gang,
             c.gangTrace, (int64_t)c.ldsBytes, (int64_t)c.ldsBytesFwd, (int64_t)c.firstLdsBytes(), (int64_t)c.traceLdsBytes(), c.subSlots,
-            c.threads, c.itemCount, c.firstGrid(1), c.geo.useGlobalRoll};
+            c.threads, c.itemCount + c.chainedSegs - c.chains, c.firstGrid(1), c.geo.useGlobalRoll};
         for (int j = 0; j < CPK_LAUNCH_PLAN_FIELDS; j++) out[i * CPK_LAUNCH_PLAN_FIELDS + j] = f[j];
     }
     return (int)classes.size();
 }
 
 // The launches of a batch on a device that is not there (tests of the plan): CPK_LAUNCH_PLAN_FIELDS numbers per class.
-extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, int dynamic, int64_t nDiags, int64_t nSegs,
-                                 int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
-                                 int64_t memBytes, int64_t *out, int maxClasses) {
+static int plan_without_device(const CpkGeometry *geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
+                               int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
+                               int64_t memBytes, std::vector<LaunchClass> *classes) {
     const PlanKnobs knobs;  // (reads the environment)
     PlanDevice dev;
     dev.numCUs = numCUs;
     dev.freeBytes = dev.totalBytes = (size_t)memBytes;
     dev.queryKernels = false;
     const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
+    return plan_batch(*geo, regions, segs, dynamic, sizes, dev, knobs, modelSlots, classes);
+}
+extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags,
+                                 int64_t nSegs, int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots,
+                                 int numCUs, int64_t memBytes, int64_t *out, int maxClasses) {
     std::vector<LaunchClass> classes;
-    if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, modelSlots, &classes)) return rc;
+    if (int rc = plan_without_device(geo, regions, segs, dynamic, nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists, modelSlots,
+                                     numCUs, memBytes, &classes))
+        return rc;
     return describe_classes(classes, out, maxClasses);
+}
+// The chains of the same plan (plan_chains) and the item queues built from it, for tests.  chainsOut: CPK_CHAIN_PLAN_FIELDS
+// numbers per class, in launch order -- the first segment of its chains (0: none) and how many there are.  itemsOut (may be
+// null): CPK_CHAIN_ITEM_FIELDS numbers per queue item of every split class, in queue order -- class, device region, segment
+// (-K: a chain from segment K), cost, segments of the region, leading segments of the region that the class's forward launch
+// sweeps (forward_launch_segments; the whole region where the forward sweep is not a launch of its own); *nItems receives their
+// number (no more than maxItems are written).  Returns the number of classes.  `regions` gets its rings set as an upload sets them.
+extern "C" int cpk_plan_chains(const CpkGeometry *geo, CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
+                               int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
+                               int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut, int64_t maxItems, int64_t *nItems) {
+    std::vector<LaunchClass> classes;
+    if (int rc = plan_without_device(geo, regions, segs, dynamic, nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists, modelSlots,
+                                     numCUs, memBytes, &classes))
+        return rc;
+    if ((int)classes.size() > maxClasses) return CPECAN_EINVAL;
+    for (size_t i = 0; i < classes.size(); i++) {
+        chainsOut[i * CPK_CHAIN_PLAN_FIELDS] = classes[i].chainFrom;
+        chainsOut[i * CPK_CHAIN_PLAN_FIELDS + 1] = classes[i].chains;
+    }
+    if (itemsOut && nItems) {
+        std::vector<CpkItem> items;
+        std::vector<int64_t> costs;
+        build_item_queue(classes, regions, segs, geo->nStates, &items, &costs);
+        *nItems = (int64_t)items.size();
+        for (size_t ci = 0; ci < classes.size(); ci++) {
+            const LaunchClass &c = classes[ci];
+            if (!c.split()) continue;
+            for (int64_t i = c.itemBase; i < c.itemBase + c.itemCount && i < maxItems; i++) {
+                const CpkRegion &rg = regions[items[i].region];
+                const int64_t f[CPK_CHAIN_ITEM_FIELDS] = {(int64_t)ci, items[i].region, items[i].seg, costs[i], rg.nSeg, forward_launch_segments(c.chainFrom, rg.nSeg)};
+                for (int j = 0; j < CPK_CHAIN_ITEM_FIELDS; j++) itemsOut[i * CPK_CHAIN_ITEM_FIELDS + j] = f[j];
+            }
+        }
+    }
+    return (int)classes.size();
 }
 // ... and of an uploaded batch on the device it was planned for, with the registers the loaded kernels report: the same numbers.
 extern "C" int cpk_device_launch_forms(const CpkDevice *d, int64_t *out, int maxClasses) { return describe_classes(d->classes, out, maxClasses); }
 // kKernelTable as data (tests: every built variant has a test that runs it): CPK_KERNEL_FORM_FIELDS numbers per entry, the
 // fields of KernelForm in their order; returns the number of entries.  No device needed.
+// ... and, in step with it, whether an entry is a CHAIN build (KernelForm::chain): one number per entry.
+extern "C" int cpk_kernel_table_chain(int64_t *out, int maxEntries) {
+    const int n = (int)(sizeof kKernelTable / sizeof kKernelTable[0]);
+    if (n > maxEntries) return CPECAN_EINVAL;
+    for (int i = 0; i < n; i++) out[i] = kKernelTable[i].form.chain;
+    return n;
+}
 extern "C" int cpk_kernel_table_forms(int64_t *out, int maxEntries) {
     const int n = (int)(sizeof kKernelTable / sizeof kKernelTable[0]);
     if (n > maxEntries) return CPECAN_EINVAL;
@@ -1013,7 +1073,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     dev.idleCachedBytes = cache_bytes(d->device);
     dev.othersAlive = d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0;  // (this batch no longer counts: ran_set above)
     const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
-    if (int rc = plan_batch(*geo, regions, dynamic, sizes, dev, knobs, d->modelSlots, &d->classes)) return rc;
+    if (int rc = plan_batch(*geo, regions, segs, dynamic, sizes, dev, knobs, d->modelSlots, &d->classes)) return rc;
     const int slotCount = d->modelSlots > 0 ? d->modelSlots : 1;
     {
         // (the rings start 64 doubles into their block and the block ends 256 doubles behind them: the streamed traceback's
@@ -1310,6 +1370,7 @@ extern "C" int cpk_device_run(CpkDevice *d, void *stream) {
         p.bring = d->dBring ? d->dBring + c.oBring : nullptr;
         p.expectOut = d->dExpect + c.oExpect;
         p.queue = d->dQueue + i;
+        p.fwdSegs = c.chainFrom;  // (the kernel: forward_launch_segments(a.fwdSegs, rg.nSeg))
         if (c.fused()) {
             p.items = d->dItems + c.itemBase;
             p.itemCount = (int32_t)c.itemCount;

@@ -64,8 +64,13 @@ struct KArgs {
     // models of this run.  forwardOut is [slot][nRegions] then and expectOut [slot][wave][128].
     const CpkSlotModel *slotModels;
     int32_t nModels;
-    int32_t reserved1;
+    // The CHAIN builds only (cpk_sweep.inl "CHAIN"; never read by the others): the leading segments of a region that the
+    // forward launch sweeps -- the later ones are swept by the region's chain item in the traceback launch.  0: all.
+    int32_t fwdSegs;
 };
+// The leading segments of a region of nSeg that a forward launch with KArgs::fwdSegs sweeps: the kernel's own bound, and
+// what the host reports of the plan (cpk_plan_chains).
+__host__ __device__ constexpr int forward_launch_segments(int fwdSegs, int nSeg) { return fwdSegs > 0 && fwdSegs < nSeg ? fwdSegs : nSeg; }
 
 // logAdd, impl/pairwiseAligner.c:287-307: with hi = max(x, y), lo = min(x, y), d = hi - lo the reference returns hi when
 // lo == -inf or d >= 7.5, else lo + P(d), P one of four cubics chosen by d <= 1.0 / <= 2.5 / <= 4.5 / else, evaluated in

@@ -16,10 +16,11 @@ struct KernelForm {
     bool slots = false, dynamic = false;  // dynamic: packed, per-anchor expansions (DYN)
     int width = 0;      // packed: lanes of a group (GW); team: waves (T)
     bool gang = false;  // sweep: workgroups of several waves that share the LDS tables (GANG)
+    bool chain = false; // sweep: gangs of a class whose traceback launch sweeps the regions' later segments forward (CHAIN)
 };
 constexpr bool operator==(const KernelForm &a, const KernelForm &b) {
     return a.family == b.family && a.S == b.S && a.emit == b.emit && a.mode == b.mode && a.fast == b.fast && a.wps == b.wps && a.abs == b.abs &&
-           a.inSweep == b.inSweep && a.slots == b.slots && a.dynamic == b.dynamic && a.width == b.width && a.gang == b.gang;
+           a.inSweep == b.inSweep && a.slots == b.slots && a.dynamic == b.dynamic && a.width == b.width && a.gang == b.gang && a.chain == b.chain;
 }
 struct KernelEntry { KernelForm form; KernelFn fn; };
 // One macro per family builds the key and the pointer of an entry from the same argument list; _F repeats it for LDS and
@@ -27,6 +28,9 @@ struct KernelEntry { KernelForm form; KernelFn fn; };
 #define CPK_SWEEP_GANG(S, FAST, EMIT, MODE, WPS, ABS, INSWEEP, SLOTS, GANG) \
     {KernelForm{kFamilySweep, S, EMIT, MODE, FAST, WPS, ABS, INSWEEP, SLOTS, false, 0, GANG}, cpecan_pairhmm_sweep<S, FAST, EMIT, MODE, WPS, ABS, INSWEEP, SLOTS, GANG>},
 #define CPK_SWEEP(...) CPK_SWEEP_GANG(__VA_ARGS__, false)
+#define CPK_SWEEP_CHAIN(S, MODE) \
+    {KernelForm{kFamilySweep, S, CPECAN_EMIT_MATCH, MODE, true, 3, true, 0, false, false, 0, true, true}, \
+     cpecan_pairhmm_sweep<S, true, CPECAN_EMIT_MATCH, MODE, 3, true, 0, false, true, true>},
 #define CPK_PACKED(S, GW, EMIT, DYN, MODE, SLOTS) \
     {KernelForm{kFamilyPacked, S, EMIT, MODE, false, 0, false, 0, SLOTS, DYN, GW}, cpecan_pairhmm_packed<S, GW, EMIT, DYN, MODE, SLOTS>},
 #define CPK_TEAM(S, T, EMIT, SLOTS) \
@@ -62,6 +66,10 @@ constexpr KernelEntry kKernelTable[] = {
     // ... the two launches at three waves per SIMD as gangs: workgroups of several waves, one copy of the tables
     CPK_BOTH(CPK_SWEEP_GANG, true, CPECAN_EMIT_MATCH, kModeForward, 3, true, 0, false, true)
     CPK_BOTH(CPK_SWEEP_GANG, true, CPECAN_EMIT_MATCH, kModeTrace, 3, true, 0, false, true)
+    // ... and the gangs of a class with chains: a forward launch that stops behind a region's first segments, a traceback
+    // launch whose items may sweep the later ones forward before they trace them back
+    CPK_BOTH(CPK_SWEEP_CHAIN, kModeForward)
+    CPK_BOTH(CPK_SWEEP_CHAIN, kModeTrace)
     // dense classes: the three-state match kernels for three waves per SIMD (the forward launch needs 70 VGPRs: one variant)
     CPK_SWEEP_F(3, CPECAN_EMIT_MATCH, kModeWhole, 3, false, 0, false)
     CPK_SWEEP_F(3, CPECAN_EMIT_MATCH, kModeTrace, 3, false, 0, false)
@@ -85,6 +93,7 @@ constexpr KernelEntry kKernelTable[] = {
 };
 #undef CPK_SWEEP
 #undef CPK_SWEEP_GANG
+#undef CPK_SWEEP_CHAIN
 #undef CPK_PACKED
 #undef CPK_TEAM
 #undef CPK_SWEEP_F
@@ -137,6 +146,8 @@ constexpr bool split_forms_have_kernels(const KernelForm &whole, bool dense) {  
             s.wps = 3;  // the requests for three waves per SIMD: the forward launch; a five-state traceback or one launch
             if (abs && (mode == kModeForward || s.S == 5) && !has_kernel(s)) return false;
             s.gang = true;  // ... and their gangs: the two launches (take_gang)
+            if (abs && mode != kModeFused && !has_kernel(s)) return false;
+            s.chain = true;  // ... and the chains of those gangs (plan_chains)
             if (abs && mode != kModeFused && !has_kernel(s)) return false;
         }
     return true;

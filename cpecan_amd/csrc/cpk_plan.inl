@@ -36,6 +36,11 @@ struct LaunchClass {
     // wave per workgroup.  `waves` / `wavesTrace` stay counts of WAVES -- whole gangs --, ldsBytes / ldsBytesFwd the LDS of one.
     int gang = 0, gangTrace = 0;
     int64_t itemBase = 0, itemCount = 0;  // its items in dItems
+    // Chains (plan_chains): the forward launch sweeps the first chainFrom segments of a region, a chain item of the traceback
+    // launch the later ones of each of the `chains` regions that have more.  0: the forward launch sweeps everything.
+    int chainFrom = 0;
+    int64_t chains = 0, chainedSegs = 0;  // (chainedSegs: the segments those chains cover)
+    bool chainsNeedGang = false;  // its traceback launch is a gang, its forward launch is not: no chains for that alone (the class line says so)
     int64_t ringTotal = 0;                // doubles of all its regions' rings (ringEl is 0 then: nothing per slot)
     int64_t ringEl = 0, candEl = 0, refEl = 0, totEl = 0, bringEl = 0, grollEl = 0;  // elements per scratch slot
     int64_t oRing = 0, oCand = 0, oRef = 0, oTot = 0, oBring = 0, oGroll = 0, oExpect = 0;  // element offsets of the class
@@ -114,6 +119,7 @@ struct PlanKnobs {
     Knob<int> fused3{"CPECAN_FUSED3"};  // =0: never the three-waves-per-SIMD build of the one-launch form
     Knob<int> trace3{"CPECAN_TRACE3"};  // =0: never the three-waves-per-SIMD build of the traceback launch
     Knob<int> fwd3{"CPECAN_FWD3"};  // =0: never the three-waves-per-SIMD build of the forward launch
+    Knob<int> chain{"CPECAN_CHAIN"};  // =0: no chains; k >= 1 (tests): chains from segment k wherever both launches of a class are gangs
     Knob<int> gang{"CPECAN_GANG"};  // =0: never workgroups of several waves (gangs); n in 2..12: n waves per workgroup wherever the form allows it and n fit
     Knob<double> memBudgetMb{"CPECAN_MEM_BUDGET_MB"};  // the device memory the batch may plan with (test / diagnostic knob)
     Knob<double> splitBudgetFrac{"CPECAN_SPLIT_BUDGET_FRAC"};  // the share of the device the rings of whole regions may take (default 0.45)
@@ -141,6 +147,7 @@ struct PlanInputs {
     const PlanDevice &dev;
     const PlanKnobs &knobs;
     int modelSlots = 0;  // models reserved with cpecan_batch_reserve_models; 0: a plain batch
+    const CpkSegment *segs = nullptr;  // the regions' traceback segments (CpkRegion::segOff); null: a plan without chains
 };
 
 // Resident workgroups of `wavesPerWorkgroup` waves per CU.  hipOccupancyMaxActiveBlocksPerMultiprocessor answers 3 for
@@ -464,6 +471,7 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
 // Split the class when its regions do not fill the chip and have tracebacks to hand out: the segments of a
 // region are independent once its forward values exist.  CPECAN_SPLIT=1 / 0 (tests, diagnostics): always / never.
 // `perCU`: the resident waves per CU of the class's one-wave-per-region kernel; nSegClass: its traceback segments.
+static void plan_chains(const PlanInputs &in, LaunchClass &c, int64_t nSegClass);  // (below)
 static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegClass, int perCU) {
     const CpkGeometry &geo = in.geo;
     const int S = geo.nStates, numCUs = in.dev.numCUs;
@@ -596,8 +604,71 @@ static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegCla
                 c.waves = (int)(groups * g);
             }
         }
+        plan_chains(in, c, nSegClass);
     }
     return CPECAN_OK;
+}
+
+// The cost of a queue item in cells, the measure the item queue is ordered by: a segment's traceback walks the diagonals
+// tbPrev + 1 .. dTop; a chain from segment K sweeps the diagonals behind the top of segment K - 1 forward as well.
+static int64_t item_cost(const CpkRegion &rg, const CpkSegment &sg) { return (int64_t)(sg.dTop - sg.tbPrev) * rg.maxWidth; }
+static int64_t chain_cost(const CpkRegion &rg, const CpkSegment *segs, int K) {
+    int64_t cost = (int64_t)(segs[rg.segOff + rg.nSeg - 1].dTop - segs[rg.segOff + K - 1].dTop) * rg.maxWidth;
+    for (int32_t si = K; si < rg.nSeg; si++) cost += item_cost(rg, segs[rg.segOff + si]);
+    return cost;
+}
+// Chains: the traceback launch takes over the forward sweep of every region's later segments.  The forward queue of a class
+// holds its regions and nothing else; where there are more of them than waves it runs in whole rounds, and with equal
+// regions (config B: 10 000 for 2816 slots, 3.55 rounds) the last round is paid in full by a launch that cannot even use
+// every CU for it.  The item queue mixes thousands of items of every length, handed out longest first, and ends even.  So
+// the forward launch sweeps only the first K segments of a region and ONE item per region -- a chain, cpk_sweep.inl
+// "CHAIN" -- sweeps the others forward from the two diagonals the ring holds at the top of segment K - 1 and traces them
+// back itself: no wave waits for another.  Taken where both launches are gangs (the builds that exist) and the forward
+// launch is quantised.  A region of K or fewer segments is swept wholly by the forward launch and has plain items only.
+// K is the smallest for which the chains -- the longest items there are, ceil(chains / waves) of them to a wave -- do not
+// stretch the item launch beyond what its work, dealt out evenly, takes:
+//     ceil(chains / trace waves) x longest chain <= (cost of all chains + cost of all plain items) / trace waves.
+// CPECAN_CHAIN=0: none; CPECAN_CHAIN=k (tests): K = k wherever both launches are gangs, whatever the queue.
+static void plan_chains(const PlanInputs &in, LaunchClass &c, int64_t nSegClass) {
+    const Knob<int> &env = in.knobs.chain;
+    c.chainFrom = 0;
+    c.chains = c.chainedSegs = 0;
+    c.chainsNeedGang = false;
+    if (!in.segs || env.off() || c.gangTrace <= 1 || in.modelSlots > 0 || c.geo.emit != CPECAN_EMIT_MATCH) return;
+    if (c.gang <= 1) {  // the CHAIN builds are gangs in both launches
+        c.chainsNeedGang = env.set || c.regionCount > c.waves;
+        return;
+    }
+    const bool forced = env.set;
+    if (!forced && c.regionCount <= c.waves) return;  // every region has a wave of its own: nothing is quantised
+    const CpkRegion *first = in.regions + c.regionBase, *end = first + c.regionCount;
+    int32_t segMax = 0;
+    int64_t plainAll = 0;
+    for (const CpkRegion *rg = first; rg < end; rg++) {
+        segMax = rg->nSeg > segMax ? rg->nSeg : segMax;
+        for (int32_t si = 0; si < rg->nSeg; si++) plainAll += item_cost(*rg, in.segs[rg->segOff + si]);
+    }
+    for (int K = forced ? env.v : 1; K >= 1 && K < segMax; K++) {
+        int64_t chains = 0, chained = 0, longest = 0, total = plainAll;
+        for (const CpkRegion *rg = first; rg < end; rg++) {
+            if (rg->nSeg <= K) continue;
+            const int64_t cost = chain_cost(*rg, in.segs, K);
+            chains++;
+            chained += rg->nSeg - K;
+            longest = cost > longest ? cost : longest;
+            // (the tracebacks of the chained segments are in plainAll already: what a chain adds is its forward sweep)
+            total += (int64_t)(in.segs[rg->segOff + rg->nSeg - 1].dTop - in.segs[rg->segOff + K - 1].dTop) * rg->maxWidth;
+        }
+        const int64_t wt = c.wavesTrace > 0 ? c.wavesTrace : 1;
+        if (forced || (chains + wt - 1) / wt * longest * wt <= total) {
+            c.chainFrom = K;
+            c.chains = chains;
+            c.chainedSegs = chained;
+            c.itemCount = nSegClass - chained + chains;
+            c.form.chain = c.formTrace.chain = true;
+            return;
+        }
+    }
 }
 
 // ", gang of n ..." for a class's CPECAN_TRACE_HOST line: the launches that run as gangs, with the LDS of a workgroup
@@ -605,6 +676,8 @@ static std::string gang_words(const LaunchClass &c) {
     std::string w;
     if (c.gang > 1) w += ", forward launch: gang of " + std::to_string(c.gang) + " (LDS " + std::to_string(c.firstLdsBytes()) + " B)";
     if (c.gangTrace > 1) w += ", traceback launch: gang of " + std::to_string(c.gangTrace) + " (LDS " + std::to_string(c.traceLdsBytes()) + " B)";
+    if (c.chainFrom > 0) w += ", chains from segment " + std::to_string(c.chainFrom) + ": " + std::to_string(c.chains);
+    if (c.chainsNeedGang) w += ", no chains: the forward launch is no gang";
     return w;
 }
 
@@ -693,8 +766,11 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
 static void unsplit(LaunchClass &c, const PlanKnobs &knobs) {
     c.form = with_mode(c.form, kModeWhole, c.dense);
     c.formTrace = KernelForm{};
-    c.form.gang = false;
+    c.form.gang = c.form.chain = false;
     c.gang = c.gangTrace = 0;
+    c.chainFrom = 0;
+    c.chains = c.chainedSegs = 0;
+    c.chainsNeedGang = false;
     c.itemCount = 0;
     c.ringTotal = 0;
     c.ringEl = c.geo.ringCells * c.geo.nStates;
@@ -771,9 +847,9 @@ static int fit_to_memory(const PlanInputs &in, const PlanFixedSizes &sz, std::ve
 
 // The launches of a run: one per size class that has regions -- the split parts of the narrow classes, their whole
 // parts, then the wide classes -- fitted to the device's memory.
-static int plan_batch(const CpkGeometry &geo, const CpkRegion *regions, int dynamic, const PlanFixedSizes &sizes, const PlanDevice &dev,
-                      const PlanKnobs &knobs, int modelSlots, std::vector<LaunchClass> *out) {
-    const PlanInputs in{geo, regions, dynamic, dev, knobs, modelSlots};
+static int plan_batch(const CpkGeometry &geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, const PlanFixedSizes &sizes,
+                      const PlanDevice &dev, const PlanKnobs &knobs, int modelSlots, std::vector<LaunchClass> *out) {
+    const PlanInputs in{geo, regions, dynamic, dev, knobs, modelSlots, segs};
     if (modelSlots > 0 && geo.emit != CPECAN_EMIT_EXPECT && geo.emit != kEmitForward) {
         cpk_set_error("model slots: expectation and forward emitters only");
         return CPECAN_EINVAL;

@@ -13,6 +13,13 @@
 // for both models, so a lane stride of S * 8 bytes is as conflict-free as 2S + 1 rows were, without the padding row
 // (round 4: 1.2 KB of LDS per wave at BASELINE config B, part of what the tenth wave per CU needs).
 // XG: 64-lane groups per diagonal tracebackExpect() is unrolled for (1: no diagonal of the class is wider than a wave)
+
+// exp() behind a call, for the CHAIN build of the traceback launch (Sweep::emitMatches<true>): inlined, hipcc keeps the
+// polynomial's constants -- 18 VGPRs -- in registers from the top of the kernel to its end, through the traceback, which has
+// none to spare once the kernel holds the forward sweep as well.  The same function, so the same bits; one call per 64
+// candidates.  The callee needs 10 VGPRs and no stack.
+__device__ __attribute__((noinline)) static double exp_outlined(double x) { return exp(x); }
+
 template <int S, bool FAST, int ROWS = 2 * S + 1, bool COH = false, bool RDBL = false, bool ABS = false, int XG = 2>
 struct Sweep {
     const KArgs &a;
@@ -610,6 +617,40 @@ struct Sweep {
             }
         }
         roll_fence<!FAST>();
+    }
+
+    // Chains (the CHAIN builds of the kernel): the forward sweep over absolute positions is resumed behind diagonal dTop, a
+    // segment top -- F[dTop - 1] and F[dTop] are in the region's ring with every state.  The rows are wiped and the two
+    // diagonals put back, each at the position its cells have under the base in force AT dTop: that of dTop is its table
+    // entry, that of dTop - 1 follows from its x-y and that base as in absRebase(), so a base that moved in front of dTop
+    // is the same case as one that did not.  What the rows of the unbroken sweep hold beyond these two diagonals is never
+    // read (a position outside the band reads -inf), so the sweep goes on from dTop + 1 bit for bit as it would have.
+    __device__ void absReload(int dTop) {
+        absWipe();
+        const CpkDiag g1 = dc.table[dTop], g2 = dc.table[dTop - 1];
+        const int p1 = dc.posTable[dTop] & 0x7fff;
+        const int base = g1.xmyL - 2 * p1 - (dTop & 1);
+        const int p2 = (g2.xmyL - ((dTop - 1) & 1) - base) >> 1;
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const CpkDiag &g = e ? g2 : g1;
+            const int W = g.width;
+            double *set = roll + ((dTop - e) & 1) * setStride + (e ? p2 : p1) * R;  // cell 0 of the diagonal
+            const double *src = ringAt(g);
+            for (int kb = 0; kb < W; kb += CPK_WAVE) {
+                const int k = kb + lane;
+                if (k < W) {
+#pragma unroll
+                    for (int st = 0; st < S; st++) set[kb * R + laneR + st] = ringLd(src + ringIdx(W, st, k));
+                }
+            }
+        }
+        roll_fence<false>();
+        atail.has = false;
+        apos1 = p1;
+        apos2 = p2;
+        f1 = g1;
+        f2 = g2;
     }
 
     struct BwdCtx {
@@ -1994,7 +2035,8 @@ struct Sweep {
     }
 
     // ---- thresholded posteriors (pairwiseAligner.c:655-689) from the candidate list, walked backwards so that the
-    // output is in the reference's list order (diagonal ascending, x-y descending).
+    // output is in the reference's list order (diagonal ascending, x-y descending).  OUTLINE: exp() behind a call (exp_outlined).
+    template <bool OUTLINE = false>
     __device__ int emitMatches(const CpkSegment &sg, const Candidate *cand, int nCand, int32_t *out, int outCap,
                                int count) {
         const double thr = m.threshold;
@@ -2010,7 +2052,7 @@ struct Sweep {
                 x = (int)(xy & 0xffffffffll);
                 y = (int)(xy >> 32);
                 const double total = ld_self(totals + (sg.tbFrom - (x + y)) / CPK_REFRESH_PERIOD);
-                p = exp(fbv - total);
+                p = OUTLINE ? exp_outlined(fbv - total) : exp(fbv - total);
             }
             const bool keep = valid && p >= thr;
             const unsigned long long mask = __ballot(keep);
@@ -2103,11 +2145,20 @@ constexpr int kModeWhole = 0, kModeForward = 1, kModeTrace = 2, kModeFused = 3;
 // the whole LDS of a CU, so the tables are paid for once per CU instead of once per wave.  The waves meet at ONE barrier,
 // behind the fill of the tables and of their rows; from there on each is on its own -- its fences are wave-scope, it draws
 // its own tickets and leaves at an empty queue while its siblings work on.  The other builds are the code they were.
+// CHAIN: the gangs of a class whose traceback launch takes over the forward sweep of every region's later segments (the
+// plan's choice, cpk_plan.inl "chains": a forward queue of nothing but equal regions runs in whole rounds, the item queue
+// mixes thousands of items and does not).  The forward launch stops behind KArgs::fwdSegs segments of a region that has
+// more.  An item of the traceback launch may be a CHAIN (CpkItem::seg = -K): the wave stages the region as a forward wave
+// does, puts the two diagonals at the top of segment K - 1 back into its rows from the region's ring (Sweep::absReload),
+// runs the forward loop over the segments K .. last into that ring, waits for its own ring stores, and traces those
+// segments back one after the other as it would trace a plain item.  Nothing is handed from wave to wave inside the
+// launch: what a chain reads of the ring is the forward launch's or its own.  The other builds are the code they were.
 template <int S, bool FAST, int EMIT, int MODE = kModeWhole, int WPS = CPK_SWEEP_WAVES, bool ABS = false, int INSWEEP = 0, bool SLOTS = false,
-          bool GANG = false>
+          bool GANG = false, bool CHAIN = false>
 __global__ void __launch_bounds__(GANG ? kGangMaxWaves * CPK_WAVE : CPK_WAVE) __attribute__((amdgpu_waves_per_eu(WPS, WPS)))
 cpecan_pairhmm_sweep(const KArgs a) {
     static_assert(!GANG || (ABS && WPS == 3 && (MODE == kModeForward || MODE == kModeTrace)), "gangs: the two launches of a split class over absolute positions, three waves per SIMD");
+    static_assert(!CHAIN || GANG, "chains: the gangs of the two launches");
     static_assert(!SLOTS || (MODE == kModeWhole && (EMIT == CPECAN_EMIT_EXPECT || EMIT == kEmitForward)), "model slots: expectation and forward emitters, whole regions");
     static_assert(!ABS || (FAST && MODE != kModeWhole && EMIT == CPECAN_EMIT_MATCH), "absolute positions: split classes of the match emitter");
     static_assert(!INSWEEP || (FAST && MODE == kModeWhole && EMIT == CPECAN_EMIT_EXPECT), "in-sweep events: expectation emitter, LDS rows");
@@ -2184,12 +2235,24 @@ cpecan_pairhmm_sweep(const KArgs a) {
         }
     };
     const size_t slot = GANG ? (size_t)blockIdx.x * (blockDim.x / CPK_WAVE) + wave : (size_t)blockIdx.x;  // the scratch slot of this wave
+    // CHAIN, traceback launch: the segments [pendSeg, pendEnd) of region pendRegion, which this wave has just swept forward as
+    // a chain, are its next items -- one per turn of the loop, in place of a ticket
+    constexpr bool CHAINS = CHAIN && MODE == kModeTrace;
+    int pendRegion = 0, pendSeg = 0, pendEnd = 0;
+    const int laneOfWave = lane;
     for (;;) {
+        // CHAINS: the lane as a value hipcc cannot see through, anew per turn.  What a role derives from it (staging offsets,
+        // row pointers) is then derived per item where it is used, not once per kernel and kept through the other role: the
+        // traceback has no register to spare for the forward sweep's.  (The other builds: the same value, the same code.)
+        int laneNow = laneOfWave;
+        if constexpr (CHAINS) asm volatile("" : "+v"(laneNow));
+        const int lane = laneNow;
         // Every lane takes part in the ticket fetch (lane 0 adds 1, the others add 0; hipcc folds this into one
         // atomic per wave).  Do NOT write this as `if (lane == 0) ticket = atomicAdd(..)`: hipcc 7.2 jump-threads
         // the lane test across the loop back-edge and re-runs the readfirstlane with 63 lanes -> endless loop.
         // (Both forms side by side, for the ISA comparison only: tools/ticket_forms.hip, profiles/r02_ticket_fetch_isa.txt.)
-        const unsigned int ticket = atomicAdd(a.queue, lane == 0 ? 1u : 0u);
+        unsigned int ticket = 0;
+        if (!CHAINS || pendSeg >= pendEnd) ticket = atomicAdd(a.queue, lane == 0 ? 1u : 0u);
         const int tk = __builtin_amdgcn_readfirstlane((int)ticket);
         int tkRegion = tk;  // (SLOTS: the region of virtual region tk)
         if constexpr (SLOTS) {
@@ -2210,13 +2273,23 @@ cpecan_pairhmm_sweep(const KArgs a) {
                 fill_weights<S>(wt, *mp, a.slotModels[vs].kc, lane);
                 __syncthreads();
             }
-        } else if (tk >= a.regionCount + (MODE == kModeFused ? a.itemCount : 0)) break;
+        } else if ((!CHAINS || pendSeg >= pendEnd) && tk >= a.regionCount + (MODE == kModeFused ? a.itemCount : 0)) break;
         // kModeTrace: the queue holds (region, segment) items, longest first; kModeFused: regions, then items; else regions
-        const bool traceRole = MODE == kModeTrace || (MODE == kModeFused && tk >= a.regionCount);  // wave-uniform
-        const bool forwardRole = MODE == kModeForward || (MODE == kModeFused && !traceRole);
+        const bool isItem = MODE == kModeTrace || (MODE == kModeFused && tk >= a.regionCount);  // wave-uniform
         const int ti = MODE == kModeFused ? tk - a.regionCount : tk;
-        const int r = traceRole ? a.items[ti].region : a.regionBase + tkRegion;
-        const int itemSeg = traceRole ? a.items[ti].seg : 0;
+        int r = isItem ? a.items[ti].region : a.regionBase + tkRegion;
+        int itemSeg = isItem ? a.items[ti].seg : 0;
+        if constexpr (CHAINS) {
+            if (pendSeg < pendEnd) {
+                r = pendRegion;
+                itemSeg = pendSeg++;
+            }
+        }
+        // a chain item (wave-uniform): the first segment it sweeps forward, 0: a plain item.  The wave takes the forward role
+        // for it, from the top of the segment before, and then the traceback role for each of its segments (pendSeg).
+        const int chainFrom = (CHAINS && itemSeg < 0) ? -itemSeg : 0;
+        const bool traceRole = CHAINS ? chainFrom == 0 : isItem;
+        const bool forwardRole = CHAINS ? chainFrom != 0 : (MODE == kModeForward || (MODE == kModeFused && !traceRole));
 
         const CpkRegion &rg = a.regions[r];
         const int lX = rg.lX, lY = rg.lY, N = lX + lY;
@@ -2302,7 +2375,14 @@ cpecan_pairhmm_sweep(const KArgs a) {
             sw.dc.load(0);
             // diagonal 0: the single cell (0,0) holds the start prior (pairwiseAligner.c:776-777)
             const double *startPrior = rg.raggedLeft ? mp->raggedStart : mp->start;
-            if (!traceRole) {
+            if constexpr (CHAINS) {
+                if (chainFrom) {
+                    // ... and what the forward role derives from the Sweep's copy of the lane and the row geometry, likewise
+                    // (without this the five-state build spills 2 VGPRs; with it neither build has scratch)
+                    asm volatile("" : "+v"(sw.lane), "+v"(sw.laneR), "+s"(sw.setStride), "+s"(sw.stride));
+                    sw.absReload(a.segs[rg.segOff + chainFrom - 1].dTop);  // the top of the segment before
+                }
+            } else if (!traceRole) {
                 const CpkDiag g0 = sw.dc.get(0, false);
                 double *cur = sw.fbuf1(0);
                 if (ABS) {  // empty rows, the single cell of diagonal 0 at its position
@@ -2322,7 +2402,17 @@ cpecan_pairhmm_sweep(const KArgs a) {
             int d = 1;
             int emitSeg = 0, emitFrom = a.segs[rg.segOff].tbFrom;  // the segment whose traceback emits diagonal d: the first with tbFrom >= d
             int toRefresh = (emitFrom - 1) % CPK_REFRESH_PERIOD;    // (emitFrom - d) mod 10 as a countdown: no division per diagonal
-            const int siFirst = traceRole ? itemSeg : 0, siEnd = traceRole ? itemSeg + 1 : rg.nSeg;
+            int siFirst = traceRole ? itemSeg : 0, siEnd = traceRole ? itemSeg + 1 : rg.nSeg;
+            if constexpr (CHAIN && MODE == kModeForward) {  // the later segments of a longer region are its chain's
+                siEnd = forward_launch_segments(a.fwdSegs, siEnd);
+            }
+            if constexpr (CHAINS) {
+                if (chainFrom) {  // the forward sweep goes on behind the top of segment chainFrom - 1
+                    siFirst = chainFrom;
+                    d = a.segs[rg.segOff + chainFrom - 1].dTop + 1;
+                    toRefresh = (emitFrom - d) % CPK_REFRESH_PERIOD;  // (d > emitFrom: set anew at the first diagonal)
+                }
+            }
             for (int si = siFirst; si < siEnd; si++) {
                 const CpkSegment sg = a.segs[rg.segOff + si];
                 if (ABS && !a.geo.absWholeStrings) {
@@ -2424,18 +2514,18 @@ cpecan_pairhmm_sweep(const KArgs a) {
                 for (int l = 0; l < (EMIT == CPECAN_EMIT_EXPECT ? 0 : NL); l++) {
                     if (traceRole) {
                         // the segment's own part of the region's output slice (the other segments are written by other waves)
-                        const int n = sw.emitMatches(sg, sw.cand + (size_t)l * a.geo.fbCells, nCand[l],
-                                                     a.triples + 3 * ((size_t)l * a.outTriplesPerList + rg.outOff + sg.outOff),
-                                                     sg.outCap, 0);
+                        const int n = sw.template emitMatches<CHAINS>(sg, sw.cand + (size_t)l * a.geo.fbCells, nCand[l],
+                                                                      a.triples + 3 * ((size_t)l * a.outTriplesPerList + rg.outOff + sg.outOff),
+                                                                      sg.outCap, 0);
                         if (lane == 0) {
                             a.segStarts[(size_t)l * a.nSegsTotal + rg.segOff + si] = sg.outOff;
                             a.segCounts[(size_t)l * a.nSegsTotal + rg.segOff + si] = n;
                         }
                     } else {
                         if (lane == 0) a.segStarts[(size_t)l * a.nSegsTotal + rg.segOff + si] = count[l];
-                        count[l] = sw.emitMatches(sg, sw.cand + (size_t)l * a.geo.fbCells, nCand[l],
-                                                  a.triples + 3 * ((size_t)l * a.outTriplesPerList + rg.outOff), rg.outCap,
-                                                  count[l]);
+                        count[l] = sw.template emitMatches<CHAINS>(sg, sw.cand + (size_t)l * a.geo.fbCells, nCand[l],
+                                                                      a.triples + 3 * ((size_t)l * a.outTriplesPerList + rg.outOff), rg.outCap,
+                                                                      count[l]);
                     }
                 }
                 if (MODE == kModeWhole && !sg.atEnd) {
@@ -2446,6 +2536,14 @@ cpecan_pairhmm_sweep(const KArgs a) {
                     sw.reloadForward(gTop, sg.dTop);
                     sw.f2 = gTopM1;
                     sw.f1 = gTop;
+                }
+            }
+            if constexpr (CHAINS) {
+                if (chainFrom) {
+                    gang_fence();  // every ring store of this wave is done before it reads them back
+                    pendRegion = r;
+                    pendSeg = chainFrom;
+                    pendEnd = rg.nSeg;
                 }
             }
         }
