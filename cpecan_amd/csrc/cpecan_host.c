@@ -332,6 +332,30 @@ int cpecan_band(const int64_t *anchors, int64_t nAnchors, int64_t lX, int64_t lY
     return rc;
 }
 
+/* One anchor entry of an add call, whichever form the call came in: (x, y, length, expansion); a triple is a run of one.
+ * The cursor walks a problem's entries in order. */
+typedef struct {
+    int64_t x, y, len, expansion;
+} AnchorEntry;
+typedef struct {
+    const int64_t *at, *end;
+    int runs; /* quadruples (x, y, length, expansion); 0: triples (x, y, expansion) */
+} AnchorCursor;
+static inline int next_entry(AnchorCursor *c, AnchorEntry *e) {
+    const int64_t *a = c->at;
+    if (a == c->end) return 0;
+    *e = c->runs ? (AnchorEntry){a[0], a[1], a[2], a[3]} : (AnchorEntry){a[0], a[1], 1, a[2]};
+    c->at = a + (c->runs ? 4 : 3);
+    return 1;
+}
+/* Anchors go to a problem's split rectangles in order (pairwiseAligner.c:1296-1308): the entries whose first diagonal x + y
+ * lies below diagEnd = x2 + y2 of the rectangle belong to it -- a rectangle ends inside a gap, never inside a run.  The next
+ * entry into *e if it belongs to the rectangle.  (The cursor is a local of the loop that uses it: this runs once per anchor of
+ * the batch, beside stores through pointers that could alias anything longer-lived.) */
+static inline int next_in_rect(AnchorCursor *c, int64_t diagEnd, AnchorEntry *e) {
+    return c->at != c->end && c->at[0] + c->at[1] < diagEnd && next_entry(c, e);
+}
+
 /* getSplitPoints, pairwiseAligner.c:1206-1257.  A gap between consecutive anchors whose matrix exceeds
  * maxMatrixSize closes the current rectangle half-way into the gap (at most sqrt(max) deep) and opens the
  * next one the same distance before the following anchor. */
@@ -358,19 +382,21 @@ static int cut_if_large(SplitState *s, int64_t fromX, int64_t fromY, int64_t toX
     return 1;
 }
 
-int64_t cpecan_split_points(const int64_t *anchors, int64_t nAnchors, int64_t lX, int64_t lY, int64_t maxMatrixSize,
-                            int raggedLeft, int raggedRight, int64_t *out) {
-    if (lX < 0 || lY < 0 || nAnchors < 0 || !out) return CPECAN_EINVAL;
+/* Between two anchors of a run the gap is empty (0 x 0 cells), so only the gaps in front of an entry and behind the last one
+ * can be cut: runs give the same rectangles as their anchors one by one. */
+static int64_t split_points_entries(AnchorCursor cur, int64_t lX, int64_t lY, int64_t maxMatrixSize, int raggedLeft, int raggedRight,
+                                    int64_t *out) {
     SplitState s = {0, 0, out, 0, maxMatrixSize, (int64_t)sqrt((double)maxMatrixSize)};
+    const int none = cur.at == cur.end;
     int64_t fromX = 0, fromY = 0;
-    for (int64_t i = 0; i < nAnchors; i++) {
-        const int64_t ax = anchors[3 * i], ay = anchors[3 * i + 1];
-        if (ax < fromX || ay < fromY || ax >= lX || ay >= lY) return CPECAN_EINVAL; /* :1240-1243 */
-        cut_if_large(&s, fromX, fromY, ax, ay, raggedLeft && i == 0);
-        fromX = ax + 1;
-        fromY = ay + 1;
+    AnchorEntry e;
+    for (int first = 1; next_entry(&cur, &e); first = 0) {
+        if (e.x < fromX || e.y < fromY || e.len < 1 || e.x + e.len > lX || e.y + e.len > lY) return CPECAN_EINVAL; /* :1240-1243 */
+        cut_if_large(&s, fromX, fromY, e.x, e.y, raggedLeft && first);
+        fromX = e.x + e.len;
+        fromY = e.y + e.len;
     }
-    const int cutAtEnd = cut_if_large(&s, fromX, fromY, lX, lY, raggedLeft && nAnchors == 0);
+    const int cutAtEnd = cut_if_large(&s, fromX, fromY, lX, lY, raggedLeft && none);
     if (!cutAtEnd || !raggedRight) {
         int64_t *r = out + 4 * s.count++;
         r[0] = s.x1;
@@ -379,6 +405,12 @@ int64_t cpecan_split_points(const int64_t *anchors, int64_t nAnchors, int64_t lX
         r[3] = lY;
     }
     return s.count;
+}
+
+int64_t cpecan_split_points(const int64_t *anchors, int64_t nAnchors, int64_t lX, int64_t lY, int64_t maxMatrixSize,
+                            int raggedLeft, int raggedRight, int64_t *out) {
+    if (lX < 0 || lY < 0 || nAnchors < 0 || !out) return CPECAN_EINVAL;
+    return split_points_entries((AnchorCursor){anchors, anchors + 3 * nAnchors, 0}, lX, lY, maxMatrixSize, raggedLeft, raggedRight, out);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -725,8 +757,9 @@ int cpecan_batch_set_debug(cpecan_batch *b, int on) {
     return CPECAN_OK;
 }
 
-/* symbol_convertCharToSymbol (pairwiseAligner.c:317-334) and toupper as byte tables: both run over every base added */
-static uint8_t g_symbolOf[256], g_upperOf[256];
+/* symbol_convertCharToSymbol (pairwiseAligner.c:317-334), toupper and the complement of an upper-case letter (A/C/G/T
+ * swapped, everything else as it is) as byte tables: they run over every base added */
+static uint8_t g_symbolOf[256], g_upperOf[256], g_complementOf[256];
 /* Filled ONCE, when the library is loaded.  (Round 1 refilled them in every cpecan_batch_create, resetting every entry to
  * N first: a batch created on one host thread while another thread converted bases saw A/C/G/T as N for an instant --
  * the intermittent mismatch of the two-host-thread test, found in round 2.) */
@@ -734,7 +767,12 @@ __attribute__((constructor)) static void init_byte_tables(void) {
     for (int c = 0; c < 256; c++) {
         g_symbolOf[c] = CPK_SYM_N;
         g_upperOf[c] = (uint8_t)((c >= 'a' && c <= 'z') ? c - 'a' + 'A' : c);
+        g_complementOf[c] = (uint8_t)c;
     }
+    g_complementOf['A'] = 'T';
+    g_complementOf['C'] = 'G';
+    g_complementOf['G'] = 'C';
+    g_complementOf['T'] = 'A';
     g_symbolOf['A'] = g_symbolOf['a'] = 0;
     g_symbolOf['C'] = g_symbolOf['c'] = 1;
     g_symbolOf['G'] = g_symbolOf['g'] = 2;
@@ -762,11 +800,6 @@ static int64_t put_symbols_rc(uint8_t *dst, int64_t at, const char *s, int64_t e
     return at + l + 2;
 }
 
-/* What one problem adds to the batch's arrays; filled by the counting pass of cpecan_batch_add_many. */
-typedef struct {
-    int64_t nRects, symbolBytes, nAnchorsKept, nRunsKept;
-} AddCount;
-
 /* One problem of an add call: its anchors as triples (x, y, expansion), one per anchor, or -- `runs` -- as quadruples
  * (x, y, length, expansion), one per run of diagonal neighbours (cpecan_batch_add_many_runs). */
 typedef struct {
@@ -780,29 +813,8 @@ typedef struct {
     int runs;
     int minus; /* anchors and results are in the coordinates of (X, rc(sY)) */
 } ProblemView;
-
-/* getSplitPoints over runs: between two anchors of a run the gap is empty (0 x 0 cells), so only the gaps in front of a
- * run and behind the last one can be cut -- the same rectangles as cpecan_split_points on the expanded anchors. */
-static int64_t split_points_runs(const int64_t *runs, int64_t nRuns, int64_t lX, int64_t lY, int64_t maxMatrixSize,
-                                 int raggedLeft, int raggedRight, int64_t *out) {
-    SplitState s = {0, 0, out, 0, maxMatrixSize, (int64_t)sqrt((double)maxMatrixSize)};
-    int64_t fromX = 0, fromY = 0;
-    for (int64_t i = 0; i < nRuns; i++) {
-        const int64_t ax = runs[4 * i], ay = runs[4 * i + 1], len = runs[4 * i + 2];
-        if (ax < fromX || ay < fromY || len < 1 || ax + len > lX || ay + len > lY) return CPECAN_EINVAL;
-        cut_if_large(&s, fromX, fromY, ax, ay, raggedLeft && i == 0);
-        fromX = ax + len;
-        fromY = ay + len;
-    }
-    const int cutAtEnd = cut_if_large(&s, fromX, fromY, lX, lY, raggedLeft && nRuns == 0);
-    if (!cutAtEnd || !raggedRight) {
-        int64_t *r = out + 4 * s.count++;
-        r[0] = s.x1;
-        r[1] = s.y1;
-        r[2] = lX;
-        r[3] = lY;
-    }
-    return s.count;
+static inline AnchorCursor cursor_of(const ProblemView *it) {
+    return (AnchorCursor){it->anchors, it->anchors + (it->runs ? 4 : 3) * it->nAnchors, it->runs};
 }
 
 /* The split rectangles of one problem (getSplitPoints semantics, pairwiseAligner.c:1230-1271) into *rects, grown as
@@ -822,11 +834,7 @@ static int64_t problem_rects(const cpecan_batch *b, const ProblemView *it, int64
         (*rects)[3] = it->lY;
         return 1;
     }
-    if (it->runs)
-        return split_points_runs(it->anchors, it->nAnchors, it->lX, it->lY, b->params.splitMatrixBiggerThanThis, it->raggedLeft,
-                                 it->raggedRight, *rects);
-    return cpecan_split_points(it->anchors, it->nAnchors, it->lX, it->lY, b->params.splitMatrixBiggerThanThis, it->raggedLeft,
-                               it->raggedRight, *rects);
+    return split_points_entries(cursor_of(it), it->lX, it->lY, b->params.splitMatrixBiggerThanThis, it->raggedLeft, it->raggedRight, *rects);
 }
 
 static int problem_valid(const ProblemView *it) {
@@ -834,24 +842,14 @@ static int problem_valid(const ProblemView *it) {
         (it->nAnchors > 0 && !it->anchors))
         return 0;
     if (it->lX + it->lY >= (int64_t)1 << 30) return 0;
-    if (it->runs) { /* strictly increasing from the last anchor of one run to the first of the next */
-        int64_t px = -1, py = -1;
-        for (int64_t i = 0; i < it->nAnchors; i++) {
-            const int64_t x = it->anchors[4 * i], y = it->anchors[4 * i + 1], len = it->anchors[4 * i + 2];
-            if (len < 1 || x <= px || y <= py || x + len > it->lX || y + len > it->lY) return 0;
-            if (it->anchors[4 * i + 3] < INT32_MIN || it->anchors[4 * i + 3] > INT32_MAX) return 0;
-            px = x + len - 1;
-            py = y + len - 1;
-        }
-        return 1;
-    }
-    /* anchors must be strictly increasing in both coordinates (pairwiseAligner.c:159-164) */
-    for (int64_t i = 0; i < it->nAnchors; i++) {
-        const int64_t x = it->anchors[3 * i], y = it->anchors[3 * i + 1];
-        if (x < 0 || y < 0 || x >= it->lX || y >= it->lY) return 0;
-        if (it->anchors[3 * i + 2] < INT32_MIN || it->anchors[3 * i + 2] > INT32_MAX) return 0; /* kept as 32-bit values */
-        if (i > 0 && (x <= it->anchors[3 * (i - 1)] || y <= it->anchors[3 * (i - 1) + 1])) return 0;
-    }
+    /* entries strictly increase in both coordinates from the last anchor of one to the first of the next
+     * (pairwiseAligner.c:159-164) and lie inside the matrix; expansions are kept as 32-bit values */
+    AnchorCursor cur = cursor_of(it);
+    AnchorEntry e;
+    for (int64_t px = -1, py = -1; next_entry(&cur, &e); px = e.x + e.len - 1, py = e.y + e.len - 1)
+        if (e.len < 1 || e.x <= px || e.y <= py || e.x + e.len > it->lX || e.y + e.len > it->lY || e.expansion < INT32_MIN ||
+            e.expansion > INT32_MAX)
+            return 0;
     return 1;
 }
 
@@ -868,6 +866,181 @@ static ProblemView view_of(const void *items, int runs, const int32_t *yMinus, i
     return v;
 }
 
+/* The scratch of an add call, one record per problem: what the problem adds to the batch's arrays (stage one) and where its
+ * slices start (stage two); one more than the call has problems. */
+typedef struct {
+    int64_t nRects, symbolBytes, nAnchorsKept, nRunsKept;
+    int64_t regionAt, symbolAt, anchorValAt, runValAt, charAt;
+} AddSlot;
+
+/* Stage one: validates every problem and counts what it needs (the problems are independent: OpenMP when there are enough
+ * of them).  The error names the first bad problem of the call. */
+static int add_count(const cpecan_batch *b, const void *items, int runs, const int32_t *yMinus, int64_t n, AddSlot *slots) {
+    int64_t firstBad = n;
+    int bad = CPECAN_OK;
+#pragma omp parallel num_threads(cpk_host_threads()) if (n >= 64)
+    {
+        int64_t *rects = NULL, cap = 0;
+#pragma omp for schedule(dynamic, 32)
+        for (int64_t i = 0; i < n; i++) {
+            const ProblemView view = view_of(items, runs, yMinus, i), *it = &view;
+            AddSlot *s = &slots[i];
+            memset(s, 0, sizeof *s);
+            const int64_t nRects = problem_valid(it) ? problem_rects(b, it, &rects, &cap) : CPECAN_EINVAL;
+            if (nRects < 0) {
+#pragma omp critical(cpk_add)
+                if (i < firstBad) {
+                    firstBad = i;
+                    bad = nRects == CPECAN_ENOMEM ? CPECAN_ENOMEM : CPECAN_EINVAL;
+                }
+                continue;
+            }
+            AnchorCursor cur = cursor_of(it);
+            AnchorEntry e;
+            int64_t sym = 0, kept = 0, entries = 0;
+            for (int64_t k = 0; k < nRects; k++) {
+                const int64_t *rect = rects + 4 * k, diagEnd = rect[2] + rect[3];
+                sym += (rect[2] - rect[0]) + (rect[3] - rect[1]) + 4; /* N + bases + N, twice */
+                for (; next_in_rect(&cur, diagEnd, &e); entries++) kept += e.len;
+            }
+            s->nRects = nRects;
+            s->symbolBytes = sym;
+            s->nAnchorsKept = kept;
+            /* a batch that keeps runs: the problem's runs as they are, or -- anchors given one by one -- a run of one each */
+            s->nRunsKept = entries;
+        }
+        free(rects);
+    }
+    if (bad == CPECAN_EINVAL) cpk_set_error("problem %lld of the call: bad lengths or anchors", (long long)firstBad);
+    return bad;
+}
+
+/* Stage two: the counts become offsets -- slots[n] receives where the call ends --, and the batch's arrays grow to hold the
+ * call.  Nothing of the batch but the capacities changes here. */
+static int add_reserve(cpecan_batch *b, const void *items, int runs, const int32_t *yMinus, int64_t n, AddSlot *slots) {
+    const int keepRuns = b->runForm == 1;
+    AddSlot at = {0, 0, 0, 0, b->nRegions, b->nSymbols, b->nAnchorVals, b->nRunVals, b->nChars}; /* the running offsets */
+    for (int64_t i = 0; i <= n; i++) {
+        AddSlot *s = &slots[i];
+        s->regionAt = at.regionAt;
+        s->symbolAt = at.symbolAt;
+        s->anchorValAt = at.anchorValAt;
+        s->runValAt = at.runValAt;
+        s->charAt = at.charAt;
+        if (i == n) break;
+        const ProblemView view = view_of(items, runs, yMinus, i);
+        at.regionAt += s->nRects;
+        at.symbolAt += s->symbolBytes;
+        at.anchorValAt += b->anchorStride * s->nAnchorsKept;
+        if (keepRuns) at.runValAt += 4 * s->nRunsKept;
+        at.charAt += view.lX + view.lY;
+    }
+    if (grow((void **)&b->problems, &b->capProblems, b->nProblems + n, sizeof(HostProblem)) ||
+        grow((void **)&b->regions, &b->capRegions, at.regionAt, sizeof(HostRegion)) ||
+        (keepRuns ? grow((void **)&b->runs, &b->capRunVals, at.runValAt, sizeof(int32_t))
+                  : grow((void **)&b->anchors, &b->capAnchorVals, at.anchorValAt, sizeof(int32_t))) ||
+        grow((void **)&b->symbols, &b->capSymbols, at.symbolAt, 1) || grow((void **)&b->chars, &b->capChars, at.charAt + 1, 1) ||
+        (keepRuns && at.anchorValAt / 2 >= ((int64_t)1 << 31))) /* (a run's first anchor is a 32-bit index) */
+        return CPECAN_ENOMEM;
+    return CPECAN_OK;
+}
+
+/* Stage three, one problem: its record, its letters, and per rectangle a region with its symbols and its anchors.  The
+ * rectangles are those stage one counted. */
+static void add_write_problem(cpecan_batch *b, const ProblemView *it, const int64_t *rects, const AddSlot *s, int64_t problem) {
+    const int keepRuns = b->runForm == 1, stride = b->anchorStride;
+    HostProblem *pr = &b->problems[problem];
+    memset(pr, 0, sizeof *pr);
+    pr->firstRegion = s->regionAt;
+    pr->nRegions = s->nRects;
+    pr->lX = it->lX;
+    pr->lY = it->lY;
+    pr->charX = s->charAt;
+    pr->charY = pr->charX + it->lX;
+    pr->minus = it->minus;
+    uint8_t *ch = b->chars + s->charAt;
+    for (int64_t k = 0; k < it->lX; k++) ch[k] = g_upperOf[(unsigned char)it->sX[k]];
+    if (it->minus)
+        for (int64_t k = 0; k < it->lY; k++) ch[it->lX + k] = g_complementOf[g_upperOf[(unsigned char)it->sY[it->lY - 1 - k]]];
+    else
+        for (int64_t k = 0; k < it->lY; k++) ch[it->lX + k] = g_upperOf[(unsigned char)it->sY[k]];
+    int64_t symAt = s->symbolAt, anchorAt = s->anchorValAt, runValAt = s->runValAt;
+    AnchorCursor cur = cursor_of(it);
+    AnchorEntry e;
+    for (int64_t k = 0; k < s->nRects; k++) {
+        const int64_t *rect = rects + 4 * k, x1 = rect[0], y1 = rect[1], diagEnd = rect[2] + rect[3];
+        HostRegion *r = &b->regions[s->regionAt + k];
+        memset(r, 0, sizeof *r);
+        r->problem = problem;
+        r->x1 = x1;
+        r->y1 = y1;
+        r->lX = rect[2] - x1;
+        r->lY = rect[3] - y1;
+        r->raggedLeft = (it->raggedLeft || k > 0) ? 1 : 0;
+        r->raggedRight = (it->raggedRight || k < s->nRects - 1) ? 1 : 0;
+        r->seqXOff = symAt;
+        symAt = put_symbols(b->symbols, symAt, it->sX + x1, r->lX);
+        r->seqYOff = symAt;
+        symAt = it->minus ? put_symbols_rc(b->symbols, symAt, it->sY, it->lY - y1, r->lY) : put_symbols(b->symbols, symAt, it->sY + y1, r->lY);
+        r->anchorOff = anchorAt / stride;
+        if (keepRuns) { /* the runs stay runs: 16 bytes each, whatever their length */
+            r->runOff = runValAt / 4;
+            while (next_in_rect(&cur, diagEnd, &e)) {
+                int32_t *q = b->runs + runValAt;
+                q[0] = (int32_t)(e.x - x1);
+                q[1] = (int32_t)(e.y - y1);
+                q[2] = (int32_t)e.len;
+                q[3] = (int32_t)(anchorAt / 2); /* its first anchor among the batch's (expanded on the device) */
+                runValAt += 4;
+                anchorAt += 2 * e.len;
+                r->nAnchors += e.len;
+                r->nRuns++;
+            }
+            continue;
+        }
+        /* an entry becomes its anchors: the batch's own 8 (12) bytes each, never the API's 24 */
+        while (next_in_rect(&cur, diagEnd, &e)) {
+            const int32_t rx = (int32_t)(e.x - x1), ry = (int32_t)(e.y - y1), ex = (int32_t)e.expansion;
+            int32_t *a = b->anchors + anchorAt;
+            if (e.len == 1) { /* a triple: no loop to set up for the one anchor (6e7 of them in a config-4 batch) */
+                a[0] = rx;
+                a[1] = ry;
+                if (stride == 3) a[2] = ex;
+            } else
+                for (int64_t q = 0; q < e.len; q++, a += stride) {
+                    a[0] = rx + (int32_t)q;
+                    a[1] = ry + (int32_t)q;
+                    if (stride == 3) a[2] = ex;
+                }
+            anchorAt += stride * e.len;
+            r->nAnchors += e.len;
+        }
+    }
+}
+
+/* Stage three: every problem writes its own slices.  The rectangles are recomputed, not kept from stage one. */
+static int add_write(cpecan_batch *b, const void *items, int runs, const int32_t *yMinus, int64_t n, const AddSlot *slots) {
+    int oom = 0;
+#pragma omp parallel num_threads(cpk_host_threads()) if (n >= 64)
+    {
+        int64_t *rects = NULL, cap = 0;
+#pragma omp for schedule(dynamic, 32)
+        for (int64_t i = 0; i < n; i++) {
+            const ProblemView view = view_of(items, runs, yMinus, i);
+            if (problem_rects(b, &view, &rects, &cap) != slots[i].nRects) { /* only an allocation failure can change the answer */
+#pragma omp atomic write
+                oom = 1;
+                continue;
+            }
+            add_write_problem(b, &view, rects, &slots[i], b->nProblems + i);
+        }
+        free(rects);
+    }
+    return oom ? CPECAN_ENOMEM : CPECAN_OK;
+}
+
+/* An add call in three stages -- count, reserve, write -- and then the commit: the used lengths move only when every stage
+ * went through, so a failed call leaves the batch as it was. */
 static int64_t add_many(cpecan_batch *b, const void *items, int runs, const int32_t *yMinus, int64_t n) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || b->frozen) return CPECAN_ESTATE;
@@ -877,212 +1050,22 @@ static int64_t add_many(cpecan_batch *b, const void *items, int runs, const int3
         const char *env = getenv("CPECAN_KEEP_RUNS");
         b->runForm = (runs && b->anchorStride == 2 && !(env && atoi(env) == 0)) ? 1 : 0;
     }
-    const int keepRuns = b->runForm == 1;
-    AddCount *cnt = malloc(sizeof(AddCount) * (size_t)n);
-    int64_t *offs = malloc(sizeof(int64_t) * 4 * (size_t)n); /* first region, symbol byte, anchor triple, char of each */
-    if (!cnt || !offs) {
-        free(cnt);
-        free(offs);
-        return CPECAN_ENOMEM;
+    AddSlot *slots = malloc(sizeof(AddSlot) * (size_t)(n + 1)); /* the one exit below frees it */
+    int64_t rc = slots ? add_count(b, items, runs, yMinus, n, slots) : CPECAN_ENOMEM;
+    if (rc == CPECAN_OK) rc = add_reserve(b, items, runs, yMinus, n, slots);
+    if (rc == CPECAN_OK) rc = add_write(b, items, runs, yMinus, n, slots);
+    if (rc == CPECAN_OK) {
+        const AddSlot *end = &slots[n];
+        rc = b->nProblems; /* the index of the call's first problem */
+        b->nProblems += n;
+        b->nRegions = end->regionAt;
+        b->nSymbols = end->symbolAt;
+        b->nAnchorVals = end->anchorValAt;
+        b->nRunVals = end->runValAt;
+        b->nChars = end->charAt;
     }
-    /* pass 1: what every problem needs (the problems are independent: OpenMP when there are enough of them) */
-    int64_t firstBad = n;
-    int bad = CPECAN_OK;
-#pragma omp parallel num_threads(cpk_host_threads()) if (n >= 64)
-    {
-        int64_t *rects = NULL, cap = 0;
-#pragma omp for schedule(dynamic, 32)
-        for (int64_t i = 0; i < n; i++) {
-            const ProblemView view = view_of(items, runs, yMinus, i), *it = &view;
-            int64_t nRects = problem_valid(it) ? problem_rects(b, it, &rects, &cap) : CPECAN_EINVAL;
-            if (nRects < 0) {
-#pragma omp critical(cpk_add)
-                if (i < firstBad) {
-                    firstBad = i;
-                    bad = nRects == CPECAN_ENOMEM ? CPECAN_ENOMEM : CPECAN_EINVAL;
-                }
-                cnt[i].nRects = cnt[i].symbolBytes = cnt[i].nAnchorsKept = cnt[i].nRunsKept = 0;
-                continue;
-            }
-            int64_t sym = 0, kept = 0;
-            int64_t at = 0; /* entries (anchors or runs) handed to rectangles so far; a rectangle ends inside a gap, never inside a run */
-            for (int64_t k = 0; k < nRects; k++) {
-                sym += (rects[4 * k + 2] - rects[4 * k]) + (rects[4 * k + 3] - rects[4 * k + 1]) + 4; /* N + bases + N, twice */
-                if (it->runs) {
-                    for (; at < it->nAnchors && it->anchors[4 * at] + it->anchors[4 * at + 1] < rects[4 * k + 2] + rects[4 * k + 3]; at++)
-                        kept += it->anchors[4 * at + 2];
-                } else {
-                    while (kept < it->nAnchors && it->anchors[3 * kept] + it->anchors[3 * kept + 1] < rects[4 * k + 2] + rects[4 * k + 3]) kept++;
-                }
-            }
-            cnt[i].nRects = nRects;
-            cnt[i].symbolBytes = sym;
-            cnt[i].nAnchorsKept = kept;
-            /* a batch that keeps runs: the problem's runs as they are, or -- anchors given one by one -- a run of one each */
-            cnt[i].nRunsKept = it->runs ? at : kept;
-        }
-        free(rects);
-    }
-    if (firstBad < n) {
-        free(cnt);
-        free(offs);
-        if (bad == CPECAN_EINVAL) cpk_set_error("problem %lld of the call: bad lengths or anchors", (long long)firstBad);
-        return bad;
-    }
-    int64_t nRegions = b->nRegions, nSymbols = b->nSymbols, nAnchorVals = b->nAnchorVals, nChars = b->nChars, nRunVals = b->nRunVals;
-    int64_t *runAt = keepRuns ? malloc(sizeof(int64_t) * (size_t)n) : NULL; /* first run value of each problem */
-    if (keepRuns && !runAt) {
-        free(cnt);
-        free(offs);
-        return CPECAN_ENOMEM;
-    }
-    for (int64_t i = 0; i < n; i++) {
-        offs[4 * i] = nRegions;
-        offs[4 * i + 1] = nSymbols;
-        offs[4 * i + 2] = nAnchorVals;
-        offs[4 * i + 3] = nChars;
-        if (keepRuns) {
-            runAt[i] = nRunVals;
-            nRunVals += 4 * cnt[i].nRunsKept;
-        }
-        nRegions += cnt[i].nRects;
-        nSymbols += cnt[i].symbolBytes;
-        nAnchorVals += b->anchorStride * cnt[i].nAnchorsKept;
-        const ProblemView view = view_of(items, runs, yMinus, i);
-        nChars += view.lX + view.lY;
-    }
-    if (grow((void **)&b->problems, &b->capProblems, b->nProblems + n, sizeof(HostProblem)) ||
-        grow((void **)&b->regions, &b->capRegions, nRegions, sizeof(HostRegion)) ||
-        (keepRuns ? grow((void **)&b->runs, &b->capRunVals, nRunVals, sizeof(int32_t))
-                  : grow((void **)&b->anchors, &b->capAnchorVals, nAnchorVals, sizeof(int32_t))) ||
-        grow((void **)&b->symbols, &b->capSymbols, nSymbols, 1) || grow((void **)&b->chars, &b->capChars, nChars + 1, 1) ||
-        (keepRuns && nAnchorVals / 2 >= ((int64_t)1 << 31))) { /* (a run's first anchor is a 32-bit index) */
-        free(cnt);
-        free(offs);
-        free(runAt);
-        return CPECAN_ENOMEM;
-    }
-    /* pass 2: every problem writes its own slices */
-    const int64_t firstProblem = b->nProblems;
-    int oom = 0;
-#pragma omp parallel num_threads(cpk_host_threads()) if (n >= 64)
-    {
-        int64_t *rects = NULL, cap = 0;
-#pragma omp for schedule(dynamic, 32)
-        for (int64_t i = 0; i < n; i++) {
-            const ProblemView view = view_of(items, runs, yMinus, i), *it = &view;
-            const int64_t nRects = problem_rects(b, it, &rects, &cap);
-            if (nRects != cnt[i].nRects) { /* only an allocation failure can change the answer */
-#pragma omp atomic write
-                oom = 1;
-                continue;
-            }
-            HostProblem *pr = &b->problems[firstProblem + i];
-            memset(pr, 0, sizeof *pr);
-            pr->firstRegion = offs[4 * i];
-            pr->nRegions = nRects;
-            pr->lX = it->lX;
-            pr->lY = it->lY;
-            uint8_t *ch = b->chars + offs[4 * i + 3];
-            pr->charX = offs[4 * i + 3];
-            for (int64_t k = 0; k < it->lX; k++) ch[k] = g_upperOf[(unsigned char)it->sX[k]];
-            pr->charY = pr->charX + it->lX;
-            pr->minus = it->minus;
-            if (it->minus) {
-                static const char from[] = "ACGT", to[] = "TGCA";
-                for (int64_t k = 0; k < it->lY; k++) {
-                    const uint8_t c = g_upperOf[(unsigned char)it->sY[it->lY - 1 - k]];
-                    const char *f = c ? strchr(from, c) : NULL;
-                    ch[it->lX + k] = f ? (uint8_t)to[f - from] : c;
-                }
-            } else {
-                for (int64_t k = 0; k < it->lY; k++) ch[it->lX + k] = g_upperOf[(unsigned char)it->sY[k]];
-            }
-            int64_t next = 0, symAt = offs[4 * i + 1], anchorAt = offs[4 * i + 2]; /* anchors go to regions in order, :1296-1308 */
-            int64_t runValAt = keepRuns ? runAt[i] : 0;
-            for (int64_t k = 0; k < nRects; k++) {
-                const int64_t x1 = rects[4 * k], y1 = rects[4 * k + 1], x2 = rects[4 * k + 2], y2 = rects[4 * k + 3];
-                HostRegion *r = &b->regions[offs[4 * i] + k];
-                memset(r, 0, sizeof *r);
-                r->problem = firstProblem + i;
-                r->x1 = x1;
-                r->y1 = y1;
-                r->lX = x2 - x1;
-                r->lY = y2 - y1;
-                r->raggedLeft = (it->raggedLeft || k > 0) ? 1 : 0;
-                r->raggedRight = (it->raggedRight || k < nRects - 1) ? 1 : 0;
-                r->seqXOff = symAt;
-                symAt = put_symbols(b->symbols, symAt, it->sX + x1, r->lX);
-                r->seqYOff = symAt;
-                symAt = it->minus ? put_symbols_rc(b->symbols, symAt, it->sY, it->lY - y1, r->lY)
-                                  : put_symbols(b->symbols, symAt, it->sY + y1, r->lY);
-                r->anchorOff = anchorAt / b->anchorStride;
-                if (keepRuns) { /* the runs stay runs: 16 bytes each, whatever their length */
-                    r->runOff = runValAt / 4;
-                    for (; next < it->nAnchors; next++) {
-                        const int64_t ax = it->runs ? it->anchors[4 * next] : it->anchors[3 * next];
-                        const int64_t ay = it->runs ? it->anchors[4 * next + 1] : it->anchors[3 * next + 1];
-                        if (ax + ay >= x2 + y2) break;
-                        const int64_t len = it->runs ? it->anchors[4 * next + 2] : 1;
-                        int32_t *q = b->runs + runValAt;
-                        q[0] = (int32_t)(ax - x1);
-                        q[1] = (int32_t)(ay - y1);
-                        q[2] = (int32_t)len;
-                        q[3] = (int32_t)(anchorAt / 2); /* its first anchor among the batch's (expanded on the device) */
-                        runValAt += 4;
-                        anchorAt += 2 * len;
-                        r->nAnchors += len;
-                        r->nRuns++;
-                    }
-                    continue;
-                }
-                if (it->runs) { /* a run becomes its anchors: the batch's own 8 (12) bytes each, never the API's 24 */
-                    for (; next < it->nAnchors && it->anchors[4 * next] + it->anchors[4 * next + 1] < x2 + y2; next++) {
-                        const int32_t rx = (int32_t)(it->anchors[4 * next] - x1), ry = (int32_t)(it->anchors[4 * next + 1] - y1);
-                        const int64_t len = it->anchors[4 * next + 2];
-                        int32_t *a = b->anchors + anchorAt;
-                        if (b->anchorStride == 3) {
-                            const int32_t e = (int32_t)it->anchors[4 * next + 3];
-                            for (int64_t q = 0; q < len; q++, a += 3) {
-                                a[0] = rx + (int32_t)q;
-                                a[1] = ry + (int32_t)q;
-                                a[2] = e;
-                            }
-                        } else {
-                            for (int64_t q = 0; q < len; q++, a += 2) {
-                                a[0] = rx + (int32_t)q;
-                                a[1] = ry + (int32_t)q;
-                            }
-                        }
-                        anchorAt += b->anchorStride * len;
-                        r->nAnchors += len;
-                    }
-                    continue;
-                }
-                while (next < it->nAnchors && it->anchors[3 * next] + it->anchors[3 * next + 1] < x2 + y2) {
-                    int32_t *a = b->anchors + anchorAt;
-                    a[0] = (int32_t)(it->anchors[3 * next] - x1);
-                    a[1] = (int32_t)(it->anchors[3 * next + 1] - y1);
-                    if (b->anchorStride == 3) a[2] = (int32_t)it->anchors[3 * next + 2];
-                    anchorAt += b->anchorStride;
-                    r->nAnchors++;
-                    next++;
-                }
-            }
-        }
-        free(rects);
-    }
-    free(cnt);
-    free(offs);
-    free(runAt);
-    if (oom) return CPECAN_ENOMEM;
-    b->nProblems += n;
-    b->nRegions = nRegions;
-    b->nSymbols = nSymbols;
-    b->nAnchorVals = nAnchorVals;
-    b->nRunVals = nRunVals;
-    b->nChars = nChars;
-    return firstProblem;
+    free(slots);
+    return rc;
 }
 
 int64_t cpecan_batch_add_many(cpecan_batch *b, const cpecan_problem *items, int64_t n) { return add_many(b, items, 0, NULL, n); }
@@ -1641,8 +1624,20 @@ static int layout_device_order(cpecan_batch *b, HostPlan *hp, CpkGeometry *geo) 
     return CPECAN_OK;
 }
 
+/* The planned batch as the device layer is told about it (CpkBatchPlan, cpecan_internal.h): the one place that spells the
+ * batch's fields out.  The arrays stay where they are -- the batch's and, until host_plan_commit, the plan's. */
+static CpkBatchPlan batch_plan_record(const cpecan_batch *b, const HostPlan *hp, const CpkGeometry *geo) {
+    const int runs = b->runForm == 1;
+    return (CpkBatchPlan){.geo = *geo, .regions = hp->devRegions, .segs = hp->segs, .nSegs = hp->nSegs, .nDiags = hp->totalDiags,
+                          .anchors = runs ? NULL : b->anchors, .anchorStride = b->anchorStride, .nAnchors = b->nAnchorVals / b->anchorStride,
+                          .runs = runs ? b->runs : NULL, .nRuns = runs ? b->nRunVals / 4 : 0, .expansion = b->params.diagonalExpansion,
+                          .dynamic = hp->dynamic, .symbols = b->symbols, .nSymbolBytes = b->nSymbols, .outTriplesPerList = hp->outTriples,
+                          .nLists = b->nLists, .dbgCells = hp->dbgCells, .dbgDiags = hp->dbgDiags, .modelSlots = b->modelSlots};
+}
+
 /* Everything an upload decides before a device is involved; integers only.  On failure the caller frees hp all the same. */
-static int batch_plan(cpecan_batch *b, HostPlan *hp, CpkGeometry *geo, CpkModel *km) {
+static int batch_plan(cpecan_batch *b, HostPlan *hp, CpkBatchPlan *plan, CpkModel *km) {
+    CpkGeometry geo;
     const double t0 = now_ms();
     int rc = host_plan_init(b, hp);
     if (rc == CPECAN_OK) rc = plan_regions(b, hp);
@@ -1652,8 +1647,9 @@ static int batch_plan(cpecan_batch *b, HostPlan *hp, CpkGeometry *geo, CpkModel 
     const double t2 = now_ms();
     sort_cost_keys(hp->keys, b->nRegions);
     const double t3 = now_ms();
-    rc = layout_device_order(b, hp, geo);
+    rc = layout_device_order(b, hp, &geo);
     if (rc != CPECAN_OK) return rc;
+    *plan = batch_plan_record(b, hp, &geo);
     kernel_model(&b->model, b->params.threshold, km);
     const double t4 = now_ms();
     if (trace_host())
@@ -1678,18 +1674,45 @@ int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = seed;
     if (b->nRegions == 0) return CPECAN_OK;
     HostPlan hp;
-    CpkGeometry geo;
+    CpkBatchPlan plan;
     CpkModel km;
-    const int rc = batch_plan(b, &hp, &geo, &km);
+    const int rc = batch_plan(b, &hp, &plan, &km);
     if (rc == CPECAN_OK) {
         const int64_t totals[4] = {hp.outTriples, hp.totalDiags, hp.dbgCells, hp.dbgDiags};
         out[0] = fnv1a64(hp.devRegions, sizeof(CpkRegion) * (size_t)b->nRegions, seed);
         out[1] = fnv1a64(hp.devToHost, sizeof(int64_t) * (size_t)b->nRegions, seed);
         out[2] = fnv1a64(hp.segs, sizeof(CpkSegment) * (size_t)hp.nSegs, seed);
-        out[3] = fnv1a64(totals, sizeof totals, fnv1a64(&geo, sizeof geo, seed));
+        out[3] = fnv1a64(totals, sizeof totals, fnv1a64(&plan.geo, sizeof plan.geo, seed));
     }
     host_plan_free(&hp);
     return rc;
+}
+
+/* For tests: what the add calls packed into the batch (cpecan_internal.h), field by field where a record holds pointers or
+ * padding; reads only. */
+int cpk_batch_intake_digest(const cpecan_batch *b, uint64_t out[5]) {
+    if (!b || !out || dl_busy(b)) return CPECAN_ESTATE;
+    const uint64_t seed = 0xcbf29ce484222325ull;
+    const int64_t form[2] = {b->runForm, b->anchorStride};
+    const int keepRuns = b->runForm == 1;
+    out[0] = out[1] = seed;
+    out[3] = fnv1a64(form, sizeof form, seed);
+    for (int64_t i = 0; i < b->nProblems; i++) {
+        const HostProblem *pr = &b->problems[i];
+        const int64_t f[7] = {pr->firstRegion, pr->nRegions, pr->lX, pr->lY, pr->charX, pr->charY, pr->minus};
+        out[0] = fnv1a64(f, sizeof f, out[0]);
+    }
+    for (int64_t i = 0; i < b->nRegions; i++) {
+        const HostRegion *r = &b->regions[i];
+        const int64_t f[11] = {r->problem, r->x1, r->y1, r->lX, r->lY, r->seqXOff, r->seqYOff, r->anchorOff, r->nAnchors, r->raggedLeft, r->raggedRight};
+        const int64_t runs[2] = {r->runOff, r->nRuns};
+        out[1] = fnv1a64(f, sizeof f, out[1]);
+        if (keepRuns) out[3] = fnv1a64(runs, sizeof runs, out[3]);
+    }
+    out[2] = fnv1a64(b->symbols, (size_t)b->nSymbols, seed);
+    out[3] = fnv1a64(keepRuns ? b->runs : b->anchors, sizeof(int32_t) * (size_t)(keepRuns ? b->nRunVals : b->nAnchorVals), out[3]);
+    out[4] = fnv1a64(b->chars, (size_t)b->nChars, seed);
+    return CPECAN_OK;
 }
 
 /* For tests, no device needed: the launches cpecan_batch_upload would plan on a device of numCUs compute units.
@@ -1700,12 +1723,10 @@ int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t
     if (!b || !out || b->frozen || dl_busy(b) || !cpk_plan_describe) return CPECAN_ESTATE;
     if (b->nRegions == 0) return 0;
     HostPlan hp;
-    CpkGeometry geo;
+    CpkBatchPlan plan;
     CpkModel km;
-    int rc = batch_plan(b, &hp, &geo, &km);
-    if (rc == CPECAN_OK)
-        rc = cpk_plan_describe(&geo, hp.devRegions, hp.segs, hp.dynamic, hp.totalDiags, hp.nSegs, b->nSymbols, b->nAnchorVals / b->anchorStride,
-                               hp.outTriples, b->nLists, b->modelSlots, numCUs, memBytes, out, maxClasses);
+    int rc = batch_plan(b, &hp, &plan, &km);
+    if (rc == CPECAN_OK) rc = cpk_plan_describe(&plan, numCUs, memBytes, out, maxClasses);
     host_plan_free(&hp);
     return rc;
 }
@@ -1717,12 +1738,10 @@ int cpk_batch_chain_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t 
     if (nItems) *nItems = 0;
     if (b->nRegions == 0) return 0;
     HostPlan hp;
-    CpkGeometry geo;
+    CpkBatchPlan plan;
     CpkModel km;
-    int rc = batch_plan(b, &hp, &geo, &km);
-    if (rc == CPECAN_OK)
-        rc = cpk_plan_chains(&geo, hp.devRegions, hp.segs, hp.dynamic, hp.totalDiags, hp.nSegs, b->nSymbols, b->nAnchorVals / b->anchorStride,
-                             hp.outTriples, b->nLists, b->modelSlots, numCUs, memBytes, chainsOut, maxClasses, itemsOut, maxItems, nItems);
+    int rc = batch_plan(b, &hp, &plan, &km);
+    if (rc == CPECAN_OK) rc = cpk_plan_chains(&plan, numCUs, memBytes, chainsOut, maxClasses, itemsOut, maxItems, nItems);
     host_plan_free(&hp);
     return rc;
 }
@@ -1748,29 +1767,22 @@ int cpecan_batch_upload(cpecan_batch *b) {
         return CPECAN_OK;
     }
     HostPlan hp;
-    CpkGeometry geo;
+    CpkBatchPlan plan;
     CpkModel km;
-    int rc = batch_plan(b, &hp, &geo, &km);
+    int rc = batch_plan(b, &hp, &plan, &km);
     if (rc == CPECAN_OK) {
         b->stats.problems = b->nProblems;
         b->stats.regions = b->nRegions;
         b->stats.cells = hp.totalCells;
         b->stats.diagonals = hp.totalDiags;
         if (!b->dev) rc = cpk_device_create(&b->dev, b->device); /* fails with CPECAN_ENODEVICE when there is no GPU */
-        if (rc == CPECAN_OK) rc = cpk_device_reserve_models(b->dev, b->modelSlots);
     }
-    if (rc == CPECAN_OK) {
-        const int runs = b->runForm == 1;
-        rc = cpk_device_upload(b->dev, &geo, &km, hp.devRegions, runs ? NULL : b->anchors, b->anchorStride,
-                               b->nAnchorVals / b->anchorStride, runs ? b->runs : NULL, runs ? b->nRunVals / 4 : 0, hp.totalDiags,
-                               b->params.diagonalExpansion, hp.dynamic, hp.segs, hp.nSegs, b->symbols, b->nSymbols, hp.outTriples,
-                               b->nLists, hp.dbgCells, hp.dbgDiags, &b->stats.h2dMs);
-    }
+    if (rc == CPECAN_OK) rc = cpk_device_upload(b->dev, &plan, &km, &b->stats.h2dMs);
     if (rc == CPECAN_OK) {
         b->stats.deviceBytes = cpk_device_bytes(b->dev);
         b->stats.wavesPerLaunch = cpk_device_waves(b->dev);
         b->stats.launchForm = cpk_device_form(b->dev);
-        host_plan_commit(b, &hp, &geo);
+        host_plan_commit(b, &hp, &plan.geo);
         b->frozen = 1;
     }
     host_plan_free(&hp);
@@ -2221,6 +2233,50 @@ int cpecan_batch_scores(const cpecan_batch *b, int64_t problem, double *byPoster
     return CPECAN_OK;
 }
 
+int cpk_overflow_scan(CpkRegion *regions, int64_t nRegions, CpkSegment *segs, int64_t nSegs, int nLists, int32_t *counts,
+                      const int32_t *segCounts, int64_t *outTriples) {
+    int overflow = 0;
+    int64_t outAt = 0;
+    for (int64_t di = 0; di < nRegions; di++) {
+        CpkRegion *g = &regions[di];
+        if (g->split) {
+            /* the segments were written apart: a region's count is the sum, and each segment has its own capacity */
+            int64_t at = 0;
+            for (int l = 0; l < nLists; l++) counts[(size_t)l * nRegions + di] = 0;
+            for (int32_t si = 0; si < g->nSeg; si++) {
+                CpkSegment *sg = &segs[g->segOff + si];
+                int32_t need = 0;
+                for (int l = 0; l < nLists; l++) {
+                    const int32_t c = segCounts[(size_t)l * nSegs + g->segOff + si];
+                    need = c > need ? c : need;
+                    counts[(size_t)l * nRegions + di] += c < sg->outCap ? c : sg->outCap;
+                }
+                if (need > sg->outCap) {
+                    overflow = 1;
+                    sg->outCap = need;
+                }
+                sg->outOff = (int32_t)at;
+                at += sg->outCap;
+            }
+            if (at > g->outCap) g->outCap = (int32_t)at;
+        } else {
+            int32_t need = 0;
+            for (int l = 0; l < nLists; l++) {
+                const int32_t c = counts[(size_t)l * nRegions + di];
+                need = c > need ? c : need;
+            }
+            if (need > g->outCap) {
+                overflow = 1;
+                g->outCap = need;
+            }
+        }
+        g->outOff = outAt;
+        outAt += g->outCap;
+    }
+    *outTriples = outAt;
+    return overflow;
+}
+
 int cpecan_batch_download(cpecan_batch *b) {
     if (dl_busy(b)) return CPECAN_ESTATE;
     if (!b || !b->ran) return CPECAN_ESTATE;
@@ -2267,44 +2323,8 @@ int cpecan_batch_download(cpecan_batch *b) {
         tD1 = now_ms();
         if (b->emit == CPECAN_EMIT_FORWARD || b->emit == CPECAN_EMIT_EXPECT) break; /* these emitters produce no lists */
         /* did any region overflow its output slice?  If so enlarge exactly and run once more. */
-        int overflow = 0;
         int64_t outAt = 0;
-        for (int64_t di = 0; di < b->nRegions; di++) {
-            CpkRegion *g = &b->devRegions[di];
-            if (g->split) {
-                /* the segments were written apart: a region's count is the sum, and each segment has its own capacity */
-                int64_t at = 0;
-                for (int l = 0; l < b->nLists; l++) counts[(size_t)l * b->nRegions + di] = 0;
-                for (int32_t si = 0; si < g->nSeg; si++) {
-                    CpkSegment *sg = &b->segs[g->segOff + si];
-                    int32_t need = 0;
-                    for (int l = 0; l < b->nLists; l++) {
-                        const int32_t c = segCounts[(size_t)l * b->nSegs + g->segOff + si];
-                        need = c > need ? c : need;
-                        counts[(size_t)l * b->nRegions + di] += c < sg->outCap ? c : sg->outCap;
-                    }
-                    if (need > sg->outCap) {
-                        overflow = 1;
-                        sg->outCap = need;
-                    }
-                    sg->outOff = (int32_t)at;
-                    at += sg->outCap;
-                }
-                if (at > g->outCap) g->outCap = (int32_t)at;
-            } else {
-                int32_t need = 0;
-                for (int l = 0; l < b->nLists; l++) {
-                    const int32_t c = counts[(size_t)l * b->nRegions + di];
-                    need = c > need ? c : need;
-                }
-                if (need > g->outCap) {
-                    overflow = 1;
-                    g->outCap = need;
-                }
-            }
-            g->outOff = outAt;
-            outAt += g->outCap;
-        }
+        const int overflow = cpk_overflow_scan(b->devRegions, b->nRegions, b->segs, b->nSegs, b->nLists, counts, segCounts, &outAt);
         if (!overflow) break;
         b->outTriples = outAt;
         rc = cpk_device_update_regions(b->dev, b->devRegions, b->segs, b->outTriples);

@@ -156,26 +156,35 @@ int cpk_current_device(void); /* the calling thread's current HIP device (0 when
 const char *cpk_last_error(void);
 int cpk_device_create(CpkDevice **out, int device);
 void cpk_device_destroy(CpkDevice *dev);
-/* Copies the packed inputs to the GPU and sizes every scratch buffer. */
-/* The per-diagonal table (nDiags entries) is built on the device from the anchors (cpecan_band.inl). */
-/* Regions of a class that is split (see CpkItem) get ringCap / ringBase / split set here, in the caller's array. */
-int cpk_device_upload(CpkDevice *dev, const CpkGeometry *geo, const CpkModel *model, CpkRegion *regions,
-                      const int32_t *anchors /* cpk_anchor_t, cpecan_band.inl */, int anchorStride, int64_t nAnchors,
-                      const int32_t *runs /* or: (x, y, length, first anchor) per run, expanded on the device; anchors NULL */, int64_t nRuns,
-                      int64_t nDiags,
-                      int64_t expansion, int dynamic,
-                      const CpkSegment *segs, int64_t nSegs, const uint8_t *symbols, int64_t nSymbolBytes,
-                      int64_t outTriplesPerList, int nLists, int64_t dbgCells, int64_t dbgDiags, double *h2dMs);
+/* A planned batch as the device layer is told about it: built in one place (cpecan_host.c, batch_plan_record) from the
+ * batch, its plan and the geometry; read by cpk_device_upload and, without a device, by cpk_plan_describe / cpk_plan_chains. */
+typedef struct {
+    CpkGeometry geo;
+    CpkRegion *regions;     /* device order.  Regions of a class that is split (see CpkItem) get ringCap / ringBase / split set
+                             * here, in the caller's array, by cpk_device_upload and cpk_plan_chains */
+    const CpkSegment *segs; /* the regions' traceback segments (CpkRegion::segOff) */
+    int64_t nSegs, nDiags;  /* nDiags: entries of the per-diagonal table, built on the device from the anchors (cpecan_band.inl) */
+    const int32_t *anchors; /* cpk_anchor_t (cpecan_band.inl), anchorStride values each; NULL for a batch that holds runs */
+    const int32_t *runs;    /* or: (x, y, length, first anchor) per run, expanded on the device */
+    int64_t nAnchors, nRuns; /* nAnchors: one per column, whichever form they are held in */
+    int64_t expansion;
+    const uint8_t *symbols;
+    int64_t nSymbolBytes, outTriplesPerList, dbgCells, dbgDiags;
+    int32_t anchorStride, nLists;
+    int32_t dynamic;        /* per-anchor expansions are in force */
+    int32_t modelSlots;     /* models reserved per run (cpecan_batch_reserve_models); 0: a plain batch -- expectation and forward
+                             * emitters only; wave counts and everything per wave are planned for that many times the regions */
+} CpkBatchPlan;
+/* Plans the launches of the batch (cpk_plan.inl), copies the packed inputs to the GPU and sizes every scratch buffer. */
+int cpk_device_upload(CpkDevice *dev, const CpkBatchPlan *plan, const CpkModel *model, double *h2dMs);
 double cpk_device_h2d_ms(CpkDevice *dev); /* the upload's copy time; waits for the copies */
 int cpk_device_update_regions(CpkDevice *dev, const CpkRegion *regions, const CpkSegment *segs, int64_t outTriplesPerList);
 /* Replaces the model the next cpk_device_run uses (kernel-argument transitions and the device CpkModel); the copy is
  * ordered behind the last run on the batch's own stream and in front of the next sweep. */
 int cpk_device_set_model(CpkDevice *dev, const CpkModel *model);
-/* Model slots.  Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch; expectation
- * and forward emitters only) -- wave counts and everything per wave are planned for nSlots times the regions.  After it:
- * the n models of the next run, 1 <= n <= nSlots, ordered on the stream as cpk_device_set_model orders its one.
- * cpk_device_download then fills `expect` per slot: [n][106] sums, or [n][nRegions] forward probabilities. */
-int cpk_device_reserve_models(CpkDevice *dev, int nSlots);
+/* Model slots (CpkBatchPlan::modelSlots = nSlots > 0): the n models of the next run, 1 <= n <= nSlots, ordered on the stream
+ * as cpk_device_set_model orders its one.  cpk_device_download then fills `expect` per slot: [n][106] sums, or [n][nRegions]
+ * forward probabilities. */
 int cpk_device_set_models(CpkDevice *dev, const CpkModel *models, int n);
 int cpk_device_run(CpkDevice *dev, void *stream);
 int cpk_device_form(const CpkDevice *dev); /* CPECAN_FORM_* of the batch's last (widest) size class */
@@ -251,6 +260,17 @@ int cpk_host_threads(void); /* threads of the host's parallel loops (cpecan_host
  * CpkRegion array in device order, devToHost, the CpkSegment slots, CpkGeometry with the output and debug totals.  For
  * tests: the plan is dropped again (cpecan_host.c). */
 int cpk_batch_plan_digest(cpecan_batch *b, uint64_t out[4]);
+/* For tests: what the add calls packed into a batch, as FNV-1a hashes; reads only.  out[0]: per problem firstRegion, nRegions,
+ * lX, lY, charX, charY, minus; out[1]: per region every field an add call fills that does not depend on the form the anchors
+ * are held in; out[2]: the symbols; out[3]: runForm, anchorStride and the anchor values, or every region's runOff and nRuns
+ * and the run values; out[4]: the raw letters (cpecan_host.c). */
+int cpk_batch_intake_digest(const cpecan_batch *b, uint64_t out[5]);
+/* The overflow scan of a download, on arrays: counts [nLists][nRegions] and segCounts [nLists][nSegs] as the device left them
+ * against the capacities of the device-order regions and their segments.  A split region's count per list becomes the sum of
+ * its segments' counts, each clamped with the segment's capacity as it stood; capacities grow to what was needed and every
+ * outOff follows.  Returns whether anything overflowed; *outTriples: the new total per list. */
+int cpk_overflow_scan(CpkRegion *regions, int64_t nRegions, CpkSegment *segs, int64_t nSegs, int nLists, int32_t *counts,
+                      const int32_t *segCounts, int64_t *outTriples);
 /* After the download of a batch with cpecan_batch_set_quintuples: hands the three arrays of cpecan_batch_quintuples over to
  * the caller -- quints goes back with cpk_host_free, offsets and sums with free -- with the stage's kernel time; the batch
  * forgets them (cpecan_sets.c keeps them as its result). */
@@ -264,9 +284,7 @@ int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offse
  * of the queue itself is what cpk_batch_chain_plan returns in *nItems (and per class by counting its item records). */
 #define CPK_LAUNCH_PLAN_FIELDS 25
 int cpk_batch_launch_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *out, int maxClasses);
-int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
-                      int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
-                      int64_t memBytes, int64_t *out, int maxClasses);
+int cpk_plan_describe(const CpkBatchPlan *plan, int numCUs, int64_t memBytes, int64_t *out, int maxClasses);
 /* The chains of the same plan (cpk_plan.inl, plan_chains), beside cpk_batch_launch_plan, whose record keeps its layout:
  * chainsOut receives CPK_CHAIN_PLAN_FIELDS numbers per launch class, in launch order -- the first segment of the class's
  * chains (0: it has none) and their number.  itemsOut (may be null) receives the traceback queues built from the plan,
@@ -278,9 +296,8 @@ int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, const Cp
 #define CPK_CHAIN_ITEM_FIELDS 6
 int cpk_batch_chain_plan(cpecan_batch *b, int numCUs, int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut,
                          int64_t maxItems, int64_t *nItems);
-int cpk_plan_chains(const CpkGeometry *geo, CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
-                    int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
-                    int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut, int64_t maxItems, int64_t *nItems);
+int cpk_plan_chains(const CpkBatchPlan *plan, int numCUs, int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut,
+                    int64_t maxItems, int64_t *nItems);
 /* The plan an uploaded batch really got (valid after cpecan_batch_upload): the launch classes of its device, planned with
  * the registers and static LDS the loaded kernels report -- the same CPK_LAUNCH_PLAN_FIELDS numbers per class, in the same
  * order; returns the number of classes (0: a batch without regions), or an error code (< 0).  For tests.  The classes

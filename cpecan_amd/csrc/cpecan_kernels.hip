@@ -638,7 +638,7 @@ struct CpkDevice {
     // cpk_device_set_model: the pinned source of the last model copy and the event that says it has been read
     CpkModel *hModel = nullptr;
     hipEvent_t evModel = nullptr;
-    // Model slots (cpk_device_reserve_models): the reserved count (0: a plain batch), the models of the next run, the
+    // Model slots (CpkBatchPlan::modelSlots): the reserved count (0: a plain batch), the models of the next run, the
     // device table the SLOTS kernels read and its pinned source, and the doubles of dExpect ([slot][wave][128] per class)
     int modelSlots = 0, activeModels = 1;
     CpkSlotModel *dSlots = nullptr, *hSlots = nullptr;
@@ -958,24 +958,17 @@ static int describe_classes(const std::vector<LaunchClass> &classes, int64_t *ou
 }
 
 // The launches of a batch on a device that is not there (tests of the plan): CPK_LAUNCH_PLAN_FIELDS numbers per class.
-static int plan_without_device(const CpkGeometry *geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
-                               int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
-                               int64_t memBytes, std::vector<LaunchClass> *classes) {
+static int plan_without_device(const CpkBatchPlan *plan, int numCUs, int64_t memBytes, std::vector<LaunchClass> *classes) {
     const PlanKnobs knobs;  // (reads the environment)
     PlanDevice dev;
     dev.numCUs = numCUs;
     dev.freeBytes = dev.totalBytes = (size_t)memBytes;
     dev.queryKernels = false;
-    const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
-    return plan_batch(*geo, regions, segs, dynamic, sizes, dev, knobs, modelSlots, classes);
+    return plan_batch(*plan, dev, knobs, classes);
 }
-extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags,
-                                 int64_t nSegs, int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots,
-                                 int numCUs, int64_t memBytes, int64_t *out, int maxClasses) {
+extern "C" int cpk_plan_describe(const CpkBatchPlan *plan, int numCUs, int64_t memBytes, int64_t *out, int maxClasses) {
     std::vector<LaunchClass> classes;
-    if (int rc = plan_without_device(geo, regions, segs, dynamic, nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists, modelSlots,
-                                     numCUs, memBytes, &classes))
-        return rc;
+    if (int rc = plan_without_device(plan, numCUs, memBytes, &classes)) return rc;
     return describe_classes(classes, out, maxClasses);
 }
 // The chains of the same plan (plan_chains) and the item queues built from it, for tests.  chainsOut: CPK_CHAIN_PLAN_FIELDS
@@ -983,14 +976,13 @@ extern "C" int cpk_plan_describe(const CpkGeometry *geo, const CpkRegion *region
 // null): CPK_CHAIN_ITEM_FIELDS numbers per queue item of every split class, in queue order -- class, device region, segment
 // (-K: a chain from segment K), cost, segments of the region, leading segments of the region that the class's forward launch
 // sweeps (forward_launch_segments; the whole region where the forward sweep is not a launch of its own); *nItems receives their
-// number (no more than maxItems are written).  Returns the number of classes.  `regions` gets its rings set as an upload sets them.
-extern "C" int cpk_plan_chains(const CpkGeometry *geo, CpkRegion *regions, const CpkSegment *segs, int dynamic, int64_t nDiags, int64_t nSegs,
-                               int64_t nSymbolBytes, int64_t nAnchors, int64_t outTriplesPerList, int nLists, int modelSlots, int numCUs,
-                               int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut, int64_t maxItems, int64_t *nItems) {
+// number (no more than maxItems are written).  Returns the number of classes.  The plan's regions get their rings set as an upload sets them.
+extern "C" int cpk_plan_chains(const CpkBatchPlan *plan, int numCUs, int64_t memBytes, int64_t *chainsOut, int maxClasses, int64_t *itemsOut,
+                               int64_t maxItems, int64_t *nItems) {
+    CpkRegion *regions = plan->regions;
+    const CpkSegment *segs = plan->segs;
     std::vector<LaunchClass> classes;
-    if (int rc = plan_without_device(geo, regions, segs, dynamic, nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists, modelSlots,
-                                     numCUs, memBytes, &classes))
-        return rc;
+    if (int rc = plan_without_device(plan, numCUs, memBytes, &classes)) return rc;
     if ((int)classes.size() > maxClasses) return CPECAN_EINVAL;
     for (size_t i = 0; i < classes.size(); i++) {
         chainsOut[i * CPK_CHAIN_PLAN_FIELDS] = classes[i].chainFrom;
@@ -999,7 +991,7 @@ extern "C" int cpk_plan_chains(const CpkGeometry *geo, CpkRegion *regions, const
     if (itemsOut && nItems) {
         std::vector<CpkItem> items;
         std::vector<int64_t> costs;
-        build_item_queue(classes, regions, segs, geo->nStates, &items, &costs);
+        build_item_queue(classes, regions, segs, plan->geo.nStates, &items, &costs);
         *nItems = (int64_t)items.size();
         for (size_t ci = 0; ci < classes.size(); ci++) {
             const LaunchClass &c = classes[ci];
@@ -1035,35 +1027,24 @@ extern "C" int cpk_kernel_table_forms(int64_t *out, int maxEntries) {
     return n;
 }
 
-// Before cpk_device_upload: the batch will run up to nSlots models per launch (0: a plain batch).
-extern "C" int cpk_device_reserve_models(CpkDevice *d, int nSlots) {
-    if (nSlots < 0 || nSlots > CPECAN_MAX_MODEL_SLOTS) return CPECAN_EINVAL;
-    d->modelSlots = nSlots;
-    d->activeModels = 1;
-    return CPECAN_OK;
-}
-
-extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const CpkModel *model, CpkRegion *regions,
-                                 const cpk_anchor_t *anchors, int anchorStride, int64_t nAnchors, const int32_t *runs, int64_t nRuns,
-                                 int64_t nDiags, int64_t expansion, int dynamic,
-                                 const CpkSegment *segs, int64_t nSegs, const uint8_t *symbols, int64_t nSymbolBytes,
-                                 int64_t outTriplesPerList, int nLists, int64_t dbgCells, int64_t dbgDiags,
-                                 double *h2dMs) {
+extern "C" int cpk_device_upload(CpkDevice *d, const CpkBatchPlan *plan, const CpkModel *model, double *h2dMs) {
+    if (plan->modelSlots < 0 || plan->modelSlots > CPECAN_MAX_MODEL_SLOTS) return CPECAN_EINVAL;
     CPK_ON_DEVICE(d->device);
     free_all(d);
     d->kernelMsAccum = 0.0;
     d->fusedRetried = false;
-    d->geo = *geo;
+    d->geo = plan->geo;
     d->kc = kconsts_of(model);
+    d->modelSlots = plan->modelSlots;
     d->activeModels = 1;
-    d->nLists = nLists;
-    d->nSegs = nSegs;
-    d->nDiags = nDiags;
-    d->outTriplesPerList = outTriplesPerList;
-    d->dbgCells = dbgCells;
-    d->dbgDiags = dbgDiags;
+    d->nLists = plan->nLists;
+    d->nSegs = plan->nSegs;
+    d->nDiags = plan->nDiags;
+    d->outTriplesPerList = plan->outTriplesPerList;
+    d->dbgCells = plan->dbgCells;
+    d->dbgDiags = plan->dbgDiags;
     ran_set(d, false);
-    const int S = geo->nStates;
+    const int S = plan->geo.nStates;
 
     // ---- the launches of a run: planned (cpk_plan.inl), then carried out ----
     const PlanKnobs knobs;  // (reads the environment)
@@ -1072,8 +1053,7 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     HIP_TRY(hipMemGetInfo(&dev.freeBytes, &dev.totalBytes));
     dev.idleCachedBytes = cache_bytes(d->device);
     dev.othersAlive = d->device >= 0 && d->device < kMaxDevices && g_ranAlive[d->device] > 0;  // (this batch no longer counts: ran_set above)
-    const PlanFixedSizes sizes{nDiags, nSegs, nSymbolBytes, nAnchors, outTriplesPerList, nLists};
-    if (int rc = plan_batch(*geo, regions, segs, dynamic, sizes, dev, knobs, d->modelSlots, &d->classes)) return rc;
+    if (int rc = plan_batch(*plan, dev, knobs, &d->classes)) return rc;
     const int slotCount = d->modelSlots > 0 ? d->modelSlots : 1;
     {
         // (the rings start 64 doubles into their block and the block ends 256 doubles behind them: the streamed traceback's
@@ -1118,22 +1098,22 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         count_waves(d);
     }
 
-    if (int rc = dev_alloc(d, &d->dRegions, (size_t)geo->nRegions)) return rc;
-    if (int rc = dev_alloc(d, &d->dDiags, (size_t)nDiags)) return rc;
+    if (int rc = dev_alloc(d, &d->dRegions, (size_t)plan->geo.nRegions)) return rc;
+    if (int rc = dev_alloc(d, &d->dDiags, (size_t)plan->nDiags)) return rc;
     {
         bool anyAbs = false;
         for (const LaunchClass &c : d->classes) anyAbs = anyAbs || c.abs;
         if (anyAbs)
-            if (int rc = dev_alloc(d, &d->dDiagPos, (size_t)nDiags)) return rc;
+            if (int rc = dev_alloc(d, &d->dDiagPos, (size_t)plan->nDiags)) return rc;
     }
-    if (int rc = dev_alloc(d, &d->dSegs, (size_t)nSegs)) return rc;
-    if (int rc = dev_alloc(d, &d->dSymbols, (size_t)nSymbolBytes)) return rc;
+    if (int rc = dev_alloc(d, &d->dSegs, (size_t)plan->nSegs)) return rc;
+    if (int rc = dev_alloc(d, &d->dSymbols, (size_t)plan->nSymbolBytes)) return rc;
     if (int rc = dev_alloc(d, &d->dModel, 1)) return rc;
-    if (int rc = dev_alloc(d, &d->dForward, (size_t)slotCount * geo->nRegions)) return rc;
+    if (int rc = dev_alloc(d, &d->dForward, (size_t)slotCount * plan->geo.nRegions)) return rc;
     if (d->modelSlots > 0)
         if (int rc = dev_alloc(d, &d->dSlots, (size_t)d->modelSlots)) return rc;
     {
-        const size_t nC = (size_t)nLists * geo->nRegions, nS = (size_t)nLists * (nSegs ? nSegs : 1);
+        const size_t nC = (size_t)plan->nLists * plan->geo.nRegions, nS = (size_t)plan->nLists * (plan->nSegs ? plan->nSegs : 1);
         const size_t words = (nC + 63) / 64 * 64 + 2 * ((nS + 63) / 64 * 64);
         const size_t bytes = sizeof(int32_t) * words;
         d->hostCounts = host_alloc_impl(bytes, true);
@@ -1147,23 +1127,23 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         d->dSegCounts = d->dSegStarts + (nS + 63) / 64 * 64;
     }
     std::vector<CpkItem> items;
-    build_item_queue(d->classes, regions, segs, S, &items);
+    build_item_queue(d->classes, plan->regions, plan->segs, S, &items);
     if (int rc = dev_alloc(d, &d->dItems, items.empty() ? 1 : items.size())) return rc;
     {
         bool anyFused = false;
         for (const LaunchClass &c : d->classes) anyFused = anyFused || c.fused();
         if (anyFused)
-            if (int rc = dev_alloc(d, &d->dProgress, (size_t)geo->nRegions + 1)) return rc;
+            if (int rc = dev_alloc(d, &d->dProgress, (size_t)plan->geo.nRegions + 1)) return rc;
     }
-    if (int rc = dev_alloc(d, &d->dTriples, (size_t)nLists * outTriplesPerList * 3)) return rc;
+    if (int rc = dev_alloc(d, &d->dTriples, (size_t)plan->nLists * plan->outTriplesPerList * 3)) return rc;
     if (int rc = dev_alloc(d, &d->dQueue, (size_t)2 * kMaxClasses)) return rc;
     hipStream_t io = d->io;
 
-    if (geo->debug) {
-        if (int rc = dev_alloc(d, &d->dDbgFb, (size_t)dbgCells)) return rc;
-        if (int rc = dev_alloc(d, &d->dDbgTotals, (size_t)dbgDiags)) return rc;
-        HIP_TRY(hipMemsetAsync(d->dDbgFb, 0xff, sizeof(double) * (size_t)dbgCells, io));      // NaN pattern
-        HIP_TRY(hipMemsetAsync(d->dDbgTotals, 0xff, sizeof(double) * (size_t)dbgDiags, io));
+    if (plan->geo.debug) {
+        if (int rc = dev_alloc(d, &d->dDbgFb, (size_t)plan->dbgCells)) return rc;
+        if (int rc = dev_alloc(d, &d->dDbgTotals, (size_t)plan->dbgDiags)) return rc;
+        HIP_TRY(hipMemsetAsync(d->dDbgFb, 0xff, sizeof(double) * (size_t)plan->dbgCells, io));      // NaN pattern
+        HIP_TRY(hipMemsetAsync(d->dDbgTotals, 0xff, sizeof(double) * (size_t)plan->dbgDiags, io));
     }
 
     // Everything below is ordered on the batch's own stream and the call returns WITHOUT waiting for it: the sources are
@@ -1172,36 +1152,36 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
     // the copy engine works: 19 ms per config-4 batch.)  The anchor block stays with the batch until it is destroyed.
     size_t stageAt = 0;
     // (anchors as runs: 16 bytes per run cross the bus and cpecan_expand_runs writes the anchors the table builders read)
-    const size_t anchorBytes = runs ? sizeof(int32_t) * 4 * (size_t)(nRuns > 0 ? nRuns : 1)
-                                    : sizeof(cpk_anchor_t) * (size_t)anchorStride * (size_t)(nAnchors > 0 ? nAnchors : 1);
+    const size_t anchorBytes = plan->runs ? sizeof(int32_t) * 4 * (size_t)(plan->nRuns > 0 ? plan->nRuns : 1)
+                                    : sizeof(cpk_anchor_t) * (size_t)plan->anchorStride * (size_t)(plan->nAnchors > 0 ? plan->nAnchors : 1);
     {
         auto staged = [](const void *p, size_t bytes) { return (bytes > kStageMaxCopy || host_is_pinned(p, bytes)) ? (size_t)0 : bytes + 256; };
-        if (int rc = stage_reserve(d, staged(regions, sizeof(CpkRegion) * (size_t)geo->nRegions) + staged(runs ? (const void *)runs : (const void *)anchors, anchorBytes) +
-                                      staged(segs, sizeof(CpkSegment) * (size_t)nSegs) + staged(symbols, (size_t)nSymbolBytes) +
+        if (int rc = stage_reserve(d, staged(plan->regions, sizeof(CpkRegion) * (size_t)plan->geo.nRegions) + staged(plan->runs ? (const void *)plan->runs : (const void *)plan->anchors, anchorBytes) +
+                                      staged(plan->segs, sizeof(CpkSegment) * (size_t)plan->nSegs) + staged(plan->symbols, (size_t)plan->nSymbolBytes) +
                                       sizeof(CpkModel) + sizeof(CpkSlotModel) + sizeof(CpkItem) * items.size() + 9 * 256))
             return rc;
     }
     if (!items.empty())
         if (int rc = staged_h2d(d, d->dItems, items.data(), sizeof(CpkItem) * items.size(), &stageAt)) return rc;
     HIP_TRY(hipEventRecord(d->evUp0, io));
-    if (int rc = staged_h2d(d, d->dRegions, regions, sizeof(CpkRegion) * (size_t)geo->nRegions, &stageAt)) return rc;
+    if (int rc = staged_h2d(d, d->dRegions, plan->regions, sizeof(CpkRegion) * (size_t)plan->geo.nRegions, &stageAt)) return rc;
     {
         // anchors -> per-diagonal table, on the device (the anchors are only needed for this)
         cpk_anchor_t *dAnchors = nullptr;
-        if (int rc = dev_alloc(d, &dAnchors, (size_t)anchorStride * (size_t)(nAnchors > 0 ? nAnchors : 1))) return rc;
-        if (runs && nRuns > 0) {
+        if (int rc = dev_alloc(d, &dAnchors, (size_t)plan->anchorStride * (size_t)(plan->nAnchors > 0 ? plan->nAnchors : 1))) return rc;
+        if (plan->runs && plan->nRuns > 0) {
             int32_t *dRuns = nullptr;
-            if (int rc = dev_alloc(d, &dRuns, (size_t)4 * (size_t)nRuns)) return rc;
-            if (int rc = staged_h2d(d, dRuns, runs, sizeof(int32_t) * 4 * (size_t)nRuns, &stageAt)) return rc;
-            const int64_t blocks = (nRuns + 255) / 256;
+            if (int rc = dev_alloc(d, &dRuns, (size_t)4 * (size_t)plan->nRuns)) return rc;
+            if (int rc = staged_h2d(d, dRuns, plan->runs, sizeof(int32_t) * 4 * (size_t)plan->nRuns, &stageAt)) return rc;
+            const int64_t blocks = (plan->nRuns + 255) / 256;
             hipLaunchKernelGGL(cpecan_expand_runs, dim3((unsigned)(blocks < 65535 * 16 ? blocks : 65535 * 16)), dim3(256), 0, io,
-                               reinterpret_cast<const int4 *>(dRuns), nRuns, dAnchors);
+                               reinterpret_cast<const int4 *>(dRuns), plan->nRuns, dAnchors);
             HIP_TRY(hipGetLastError());
-        } else if (nAnchors > 0)
-            if (int rc = staged_h2d(d, dAnchors, anchors, sizeof(cpk_anchor_t) * (size_t)anchorStride * (size_t)nAnchors, &stageAt)) return rc;
-        if (int rc = staged_h2d(d, d->dSegs, segs, sizeof(CpkSegment) * (size_t)nSegs, &stageAt)) return rc;  // the builder reads the schedule
+        } else if (plan->nAnchors > 0)
+            if (int rc = staged_h2d(d, dAnchors, plan->anchors, sizeof(cpk_anchor_t) * (size_t)plan->anchorStride * (size_t)plan->nAnchors, &stageAt)) return rc;
+        if (int rc = staged_h2d(d, d->dSegs, plan->segs, sizeof(CpkSegment) * (size_t)plan->nSegs, &stageAt)) return rc;  // the builder reads the schedule
         // (the symbols and the model go first: nothing but the table build is then between the last copy and the sweep)
-        if (int rc = staged_h2d(d, d->dSymbols, symbols, (size_t)nSymbolBytes, &stageAt)) return rc;
+        if (int rc = staged_h2d(d, d->dSymbols, plan->symbols, (size_t)plan->nSymbolBytes, &stageAt)) return rc;
         if (int rc = staged_h2d(d, d->dModel, model, sizeof(CpkModel), &stageAt)) return rc;
         if (d->dSlots) {  // a reserved batch starts with its own model in slot 0
             const CpkSlotModel s0{d->kc, *model};
@@ -1215,14 +1195,14 @@ extern "C" int cpk_device_upload(CpkDevice *d, const CpkGeometry *geo, const Cpk
         for (const LaunchClass &c : d->classes)
             if (c.split() && tableWave) {
                 hipLaunchKernelGGL(cpecan_build_diag_table_wave, dim3((unsigned)c.regionCount), dim3(64), 0, io, d->dRegions, c.regionBase,
-                                   dAnchors, anchorStride, d->dSegs, geo->nStates, d->dDiags, d->dDiagPos, expansion, dynamic);
+                                   dAnchors, plan->anchorStride, d->dSegs, plan->geo.nStates, d->dDiags, d->dDiagPos, plan->expansion, plan->dynamic);
                 HIP_TRY(hipGetLastError());
                 nSplitRegions += c.regionCount;
             }
-        if (nSplitRegions < geo->nRegions) {
-            hipLaunchKernelGGL(cpecan_build_diag_table, dim3((unsigned)((geo->nRegions + 63) / 64)), dim3(64), 0, io,
-                               d->dRegions, geo->nRegions, dAnchors, anchorStride, d->dSegs, geo->nStates, d->dDiags, d->dDiagPos, expansion,
-                               dynamic, tableWave ? 1 : 0);
+        if (nSplitRegions < plan->geo.nRegions) {
+            hipLaunchKernelGGL(cpecan_build_diag_table, dim3((unsigned)((plan->geo.nRegions + 63) / 64)), dim3(64), 0, io,
+                               d->dRegions, plan->geo.nRegions, dAnchors, plan->anchorStride, d->dSegs, plan->geo.nStates, d->dDiags, d->dDiagPos, plan->expansion,
+                               plan->dynamic, tableWave ? 1 : 0);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(d->evUp1, io));

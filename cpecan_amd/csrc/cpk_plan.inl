@@ -135,19 +135,11 @@ struct PlanDevice {
     // it -- 512 / WPS, in granules -- and no static LDS, instead of what the loaded code object reports
     bool queryKernels = true;
 };
-// The sizes of a batch that no plan changes: what its tables, strings and results take on the device.
-struct PlanFixedSizes {
-    int64_t nDiags = 0, nSegs = 0, nSymbolBytes = 0, nAnchors = 0, outTriplesPerList = 0;
-    int nLists = 1;
-};
+// What a plan is made from: the planned batch as the host hands it over (CpkBatchPlan, cpecan_internal.h), the device and the knobs.
 struct PlanInputs {
-    const CpkGeometry &geo;
-    const CpkRegion *regions;
-    int dynamic;
+    const CpkBatchPlan &batch;
     const PlanDevice &dev;
     const PlanKnobs &knobs;
-    int modelSlots = 0;  // models reserved with cpecan_batch_reserve_models; 0: a plain batch
-    const CpkSegment *segs = nullptr;  // the regions' traceback segments (CpkRegion::segOff); null: a plan without chains
 };
 
 // Resident workgroups of `wavesPerWorkgroup` waves per CU.  hipOccupancyMaxActiveBlocksPerMultiprocessor answers 3 for
@@ -199,14 +191,14 @@ static int64_t even_rounds(int64_t n, int64_t waves) {
 // first `cut` of them as a split part, the rest as whole regions.
 static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vector<LaunchClass> *packedSplit,
                              std::vector<LaunchClass> *packedWhole) {
-    const CpkGeometry &geo = in.geo;
-    const CpkRegion *regions = in.regions;
+    const CpkGeometry &geo = in.batch.geo;
+    const CpkRegion *regions = in.batch.regions;
     const int S = geo.nStates;
     const bool expect = geo.emit == CPECAN_EMIT_EXPECT;
     LaunchClass c;
     c.packed = true;
     c.k = k;
-    c.form = packed_form(geo, k, in.dynamic != 0, in.modelSlots > 0);
+    c.form = packed_form(geo, k, in.batch.dynamic != 0, in.batch.modelSlots > 0);
     if (!c.fn()) {
         cpk_set_error("no packed kernel for emitter %d", geo.emit);
         return CPECAN_EINVAL;
@@ -251,7 +243,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
         }
         const Knob<int> &env = in.knobs.packedSplit;
         const Knob<int64_t> &fromEnv = in.knobs.packedSplitFrom;
-        const bool eligible = geo.emit == CPECAN_EMIT_MATCH && !in.dynamic && !geo.debug;
+        const bool eligible = geo.emit == CPECAN_EMIT_MATCH && !in.batch.dynamic && !geo.debug;
         // (the steps of a wave if the class's steps were dealt out evenly over every wave slot of the chip)
         const int64_t balanced = stepsAll / (G * slots) + 1;
         // ... and only for a batch that has the device to itself: with other batches of the process in flight (a
@@ -275,7 +267,7 @@ static int plan_packed_class(const PlanInputs &in, int k, int64_t base, std::vec
         int64_t waves = (pCount + G - 1) / G;
         if (cc.slots()) {  // t models: t times the groups, up to the wave slots of the chip
             const int64_t groups = waves;
-            for (int t = 1; t <= in.modelSlots; t++) {
+            for (int t = 1; t <= in.batch.modelSlots; t++) {
                 cc.wavesFor[t] = (int)(groups * t < slots ? groups * t : slots);
                 if (cc.wavesFor[t] > waves) waves = cc.wavesFor[t];
             }
@@ -411,7 +403,7 @@ static int gang_waves(const PlanInputs &in, const LaunchClass &c, KernelForm f, 
 // A team of waves per region, or one wave per region -- then, maybe, the build for three waves per SIMD.  Sets the
 // class's kernel and *perCUOut, its resident workgroups per CU.
 static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut) {
-    const CpkGeometry &geo = in.geo;
+    const CpkGeometry &geo = in.batch.geo;
     const int S = geo.nStates, k = c.k;
     const bool expect = geo.emit == CPECAN_EMIT_EXPECT;
     int perCU = 0;
@@ -473,12 +465,12 @@ static int plan_team_or_solo(const PlanInputs &in, LaunchClass &c, int *perCUOut
 // `perCU`: the resident waves per CU of the class's one-wave-per-region kernel; nSegClass: its traceback segments.
 static void plan_chains(const PlanInputs &in, LaunchClass &c, int64_t nSegClass);  // (below)
 static int plan_split_form(const PlanInputs &in, LaunchClass &c, int64_t nSegClass, int perCU) {
-    const CpkGeometry &geo = in.geo;
+    const CpkGeometry &geo = in.batch.geo;
     const int S = geo.nStates, numCUs = in.dev.numCUs;
     const int64_t n = c.regionCount;
     int64_t maxRing = 0;
     for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) {
-        const int64_t rd = split_ring_doubles(in.regions[di], S);
+        const int64_t rd = split_ring_doubles(in.batch.regions[di], S);
         if (rd > maxRing) maxRing = rd;
     }
     const Knob<int> &env = in.knobs.split;
@@ -634,30 +626,30 @@ static void plan_chains(const PlanInputs &in, LaunchClass &c, int64_t nSegClass)
     c.chainFrom = 0;
     c.chains = c.chainedSegs = 0;
     c.chainsNeedGang = false;
-    if (!in.segs || env.off() || c.gangTrace <= 1 || in.modelSlots > 0 || c.geo.emit != CPECAN_EMIT_MATCH) return;
+    if (env.off() || c.gangTrace <= 1 || in.batch.modelSlots > 0 || c.geo.emit != CPECAN_EMIT_MATCH) return;
     if (c.gang <= 1) {  // the CHAIN builds are gangs in both launches
         c.chainsNeedGang = env.set || c.regionCount > c.waves;
         return;
     }
     const bool forced = env.set;
     if (!forced && c.regionCount <= c.waves) return;  // every region has a wave of its own: nothing is quantised
-    const CpkRegion *first = in.regions + c.regionBase, *end = first + c.regionCount;
+    const CpkRegion *first = in.batch.regions + c.regionBase, *end = first + c.regionCount;
     int32_t segMax = 0;
     int64_t plainAll = 0;
     for (const CpkRegion *rg = first; rg < end; rg++) {
         segMax = rg->nSeg > segMax ? rg->nSeg : segMax;
-        for (int32_t si = 0; si < rg->nSeg; si++) plainAll += item_cost(*rg, in.segs[rg->segOff + si]);
+        for (int32_t si = 0; si < rg->nSeg; si++) plainAll += item_cost(*rg, in.batch.segs[rg->segOff + si]);
     }
     for (int K = forced ? env.v : 1; K >= 1 && K < segMax; K++) {
         int64_t chains = 0, chained = 0, longest = 0, total = plainAll;
         for (const CpkRegion *rg = first; rg < end; rg++) {
             if (rg->nSeg <= K) continue;
-            const int64_t cost = chain_cost(*rg, in.segs, K);
+            const int64_t cost = chain_cost(*rg, in.batch.segs, K);
             chains++;
             chained += rg->nSeg - K;
             longest = cost > longest ? cost : longest;
             // (the tracebacks of the chained segments are in plainAll already: what a chain adds is its forward sweep)
-            total += (int64_t)(in.segs[rg->segOff + rg->nSeg - 1].dTop - in.segs[rg->segOff + K - 1].dTop) * rg->maxWidth;
+            total += (int64_t)(in.batch.segs[rg->segOff + rg->nSeg - 1].dTop - in.batch.segs[rg->segOff + K - 1].dTop) * rg->maxWidth;
         }
         const int64_t wt = c.wavesTrace > 0 ? c.wavesTrace : 1;
         if (forced || (chains + wt - 1) / wt * longest * wt <= total) {
@@ -683,7 +675,7 @@ static std::string gang_words(const LaunchClass &c) {
 
 // The wide class k (the sweep kernel, one region per wave or team at a time), its regions from `base` in the device order.
 static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *out) {
-    const CpkGeometry &geo = in.geo;
+    const CpkGeometry &geo = in.batch.geo;
     const int S = geo.nStates;
     const bool expect = geo.emit == CPECAN_EMIT_EXPECT;
     LaunchClass c;
@@ -700,10 +692,10 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     // the rolling rows by absolute position (cpk_sweep.inl): the rows need a few positions of slack.
     // CPECAN_ABS=0: never (A/B runs, tests of the other form).
     int64_t nSegClass = 0;
-    bool absOk = geo.emit == CPECAN_EMIT_MATCH && !in.dynamic;
+    bool absOk = geo.emit == CPECAN_EMIT_MATCH && !in.batch.dynamic;
     for (int64_t di = base; di < base + geo.nWide[k]; di++) {
-        nSegClass += in.regions[di].nSeg;
-        absOk = absOk && in.regions[di].absOk;
+        nSegClass += in.batch.regions[di].nSeg;
+        absOk = absOk && in.batch.regions[di].absOk;
     }
     const Knob<int> &splitEnv = in.knobs.split;
     const bool splitLikely = geo.emit == CPECAN_EMIT_MATCH && (!geo.debug || splitEnv.set) && nSegClass > 0 &&
@@ -718,7 +710,7 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
     c.geo.useGlobalRoll = c.ldsBytes + 16 > kLdsPathMaxBytes;
     set_row_form(c, absWanted && !c.geo.useGlobalRoll, in.knobs);  // absolute positions are a form of the LDS rows
     plan_expect_in_sweep(c, in.knobs);
-    c.form = wide_form(c.geo, in.modelSlots > 0);
+    c.form = wide_form(c.geo, in.batch.modelSlots > 0);
     if (!c.fn()) {
         cpk_set_error("no kernel for emitter %d", geo.emit);
         return CPECAN_EINVAL;
@@ -737,7 +729,7 @@ static int plan_wide_class(const PlanInputs &in, int k, int base, LaunchClass *o
         // t models: t x n virtual regions -- an under-subscribed class gets more waves, a saturated one none.  (Rounds are
         // evened out per t, so the count is not monotone in t: the scratch is sized for the most.)
         const int64_t cap = (int64_t)perCU * in.dev.numCUs;
-        for (int t = 1; t <= in.modelSlots; t++) {
+        for (int t = 1; t <= in.batch.modelSlots; t++) {
             const int64_t v = n * t;
             c.wavesFor[t] = (int)even_rounds(v, cap < v ? cap : v);
             if (c.wavesFor[t] > waves) waves = c.wavesFor[t];
@@ -798,18 +790,20 @@ static void tally(const std::vector<LaunchClass> &classes, double fixed, double 
 // candidates, refresh series).  One unanchored 3000 x 3000 region (a single segment: 360 MB of ring) in a class of
 // its own is one wave's worth; where a class still asks for more than the device has free, it keeps as many
 // waves as fit and the rest of its regions queue behind them.
-static int fit_to_memory(const PlanInputs &in, const PlanFixedSizes &sz, std::vector<LaunchClass> &classes) {
-    const CpkGeometry &geo = in.geo;
-    const double fixed = (double)sizeof(CpkRegion) * geo.nRegions + (double)(sizeof(CpkDiag) + sizeof(int32_t)) * sz.nDiags +
-                         (double)sizeof(CpkSegment) * sz.nSegs + (double)sz.nSymbolBytes + 24.0 * sz.nAnchors +
-                         2.0 * 12.0 * sz.nLists * sz.outTriplesPerList /* the triples and their compact copy */;
+static int fit_to_memory(const PlanInputs &in, std::vector<LaunchClass> &classes) {
+    const CpkGeometry &geo = in.batch.geo;
+    const CpkBatchPlan &batch = in.batch;
+    // the sizes of a batch that no plan changes: what its tables, strings and results take on the device
+    const double fixed = (double)sizeof(CpkRegion) * geo.nRegions + (double)(sizeof(CpkDiag) + sizeof(int32_t)) * batch.nDiags +
+                         (double)sizeof(CpkSegment) * batch.nSegs + (double)batch.nSymbolBytes + 24.0 * batch.nAnchors +
+                         2.0 * 12.0 * batch.nLists * batch.outTriplesPerList /* the triples and their compact copy */;
     double budget = 0.9 * ((double)in.dev.freeBytes + (double)in.dev.idleCachedBytes);  // idle cached blocks are ours to reuse or drop
     if (in.knobs.memBudgetMb.set) budget = 1048576.0 * in.knobs.memBudgetMb.v;
     // split classes keep one ring per REGION (it holds every segment of the region), nothing per slot
     for (LaunchClass &c : classes) {
         if (!c.split()) continue;
         c.ringTotal = 0;
-        for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) c.ringTotal += split_ring_doubles(in.regions[di], geo.nStates);
+        for (int64_t di = c.regionBase; di < c.regionBase + c.regionCount; di++) c.ringTotal += split_ring_doubles(in.batch.regions[di], geo.nStates);
         c.ringEl = 0;
     }
     // The rings of whole regions are a fixed share of the device at most (CPECAN_SPLIT_BUDGET_FRAC, default 0.45: two
@@ -847,10 +841,10 @@ static int fit_to_memory(const PlanInputs &in, const PlanFixedSizes &sz, std::ve
 
 // The launches of a run: one per size class that has regions -- the split parts of the narrow classes, their whole
 // parts, then the wide classes -- fitted to the device's memory.
-static int plan_batch(const CpkGeometry &geo, const CpkRegion *regions, const CpkSegment *segs, int dynamic, const PlanFixedSizes &sizes,
-                      const PlanDevice &dev, const PlanKnobs &knobs, int modelSlots, std::vector<LaunchClass> *out) {
-    const PlanInputs in{geo, regions, dynamic, dev, knobs, modelSlots, segs};
-    if (modelSlots > 0 && geo.emit != CPECAN_EMIT_EXPECT && geo.emit != kEmitForward) {
+static int plan_batch(const CpkBatchPlan &batch, const PlanDevice &dev, const PlanKnobs &knobs, std::vector<LaunchClass> *out) {
+    const PlanInputs in{batch, dev, knobs};
+    const CpkGeometry &geo = batch.geo;
+    if (batch.modelSlots > 0 && geo.emit != CPECAN_EMIT_EXPECT && geo.emit != kEmitForward) {
         cpk_set_error("model slots: expectation and forward emitters only");
         return CPECAN_EINVAL;
     }
@@ -877,5 +871,5 @@ static int plan_batch(const CpkGeometry &geo, const CpkRegion *regions, const Cp
         cpk_set_error("internal: the size classes do not cover the regions (%d of %d)", regionAt, geo.nRegions);
         return CPECAN_ESTATE;
     }
-    return fit_to_memory(in, sizes, *out);
+    return fit_to_memory(in, *out);
 }
