@@ -11,6 +11,7 @@
 
 #include "cpecan_dropin.h"
 #include "cpecan_sets.h"
+#include "cpecan_dense.h"
 
 static void die(const char *fmt, ...) {
     va_list ap;
@@ -1246,6 +1247,57 @@ static void append_reversed(stList *to, const int32_t *tr, int64_t n) {
     for (int64_t i = n - 1; i >= 0; i--) stList_append(to, stIntTuple_construct3(tr[3 * i], tr[3 * i + 1], tr[3 * i + 2]));
 }
 
+/* ---- foreign per-diagonal emitters: a replay over dense rows (include/cpecan_dense.h) ----
+ * An emitter that is none of the three tokens is called as the reference calls it (impl/pairwiseAligner.c:813-851): tracebacks
+ * in ascending order, inside a traceback (tbPrev, dTop, tbFrom) from tbFrom down to tbPrev + 1, with the total used on that
+ * diagonal.  The two DpMatrix objects are this layer's containers, filled from the rows the GPU computed; rows are created and
+ * deleted between the calls, so that at the call for xay = d
+ *   forward   holds rows tbPrev .. d and, unless dTop == N, rows tbFrom .. dTop -- the reference's live set (:843-855); row
+ *             d - 2 is ABSENT at d == tbPrev + 1 for tbPrev >= 1 (the reference has freed it: SURVEY 8a row a11);
+ *   backward  holds rows d - 1, d and d + 1 where they lie in tbPrev + 1 .. dTop, all with their final values (row d + 1 at
+ *             d == tbFrom is the traceback's own: Bnext).  Row d - 2, which the reference holds half-accumulated at that
+ *             moment, is not there.
+ * cpecan_dense_schedule returns exactly this sequence and these rows. */
+typedef void (*DiagonalEmitter)(StateMachine *, int64_t, DpMatrix *, DpMatrix *, const SymbolString, const SymbolString, double,
+                                PairwiseAlignmentParameters *, void *);
+static void replay_put(DpMatrix *m, const cpecan_dense_rows_t *r, int64_t d, const double *cells, int64_t S) {
+    if (dpMatrix_getDiagonal(m, d) != NULL) return;
+    const cpecan_dense_diag g = r->diags[d];
+    DpDiagonal *row = dpMatrix_createDiagonal(m, diagonal_construct(d, g.xmyL, g.xmyL + 2 * ((int64_t)g.width - 1)));
+    memcpy(row->cells, cells, sizeof(double) * (size_t)(g.width * S));
+}
+static void replay_problem(StateMachine *sM, const cpecan_dense *dn, int64_t problem, const SymbolString sX, const SymbolString sY,
+                           PairwiseAlignmentParameters *p, DiagonalEmitter fn, void *extraArgs) {
+    cpecan_dense_info_t info;
+    cpecan_dense_rows_t r;
+    check(cpecan_dense_info(dn, problem, &info), "cpecan_dense_info");
+    if (info.nDiagonals == 0) return; /* lX + lY == 0: no rows, no call (:767-770) */
+    check(cpecan_dense_rows(dn, problem, &r), "cpecan_dense_rows");
+    const int64_t N = info.nDiagonals - 1, S = info.nStates;
+    DpMatrix *forward = dpMatrix_construct(N, S), *backward = dpMatrix_construct(N, S);
+    for (int64_t k = 0; k < info.nSegments; k++) {
+        const cpecan_dense_seg g = r.segs[k];
+        const int atEnd = g.dTop == N;
+        for (int64_t d = g.tbPrev; d <= g.dTop; d++) replay_put(forward, &r, d, r.F + r.cellOff[d] * S, S); /* the sweep has reached dTop */
+        for (int64_t d = g.tbFrom; d > g.tbPrev; d--) {
+            const int64_t lo = d - 1 > g.tbPrev ? d - 1 : g.tbPrev + 1, hi = d + 1 < g.dTop ? d + 1 : g.dTop;
+            for (int64_t b = hi; b >= lo; b--)
+                replay_put(backward, &r, b, b <= g.tbFrom ? r.B + r.cellOff[b] * S : r.Bnext + r.bnextOff[k] * S, S);
+            fn(sM, d, forward, backward, sX, sY, r.totalUsed[d], p, extraArgs);
+            if (d < g.tbFrom || atEnd) dpMatrix_deleteDiagonal(forward, d); /* :843-845 */
+            if (d + 1 <= N) dpMatrix_deleteDiagonal(backward, d + 1);       /* :847-849 */
+        }
+        dpMatrix_deleteDiagonal(backward, g.tbPrev + 1); /* :854 */
+        dpMatrix_deleteDiagonal(forward, g.tbPrev);      /* :855 */
+        if (dpMatrix_getActiveDiagonalNumber(backward) != 0 ||
+            (!atEnd && dpMatrix_getActiveDiagonalNumber(forward) != g.dTop - g.tbFrom + 1)) /* :857-861 */
+            die("cpecan_hip: foreign emitter replay: rows left over after traceback %lld", (long long)k);
+    }
+    if (dpMatrix_getActiveDiagonalNumber(forward) != 0) die("cpecan_hip: foreign emitter replay: forward rows left over"); /* :871 */
+    dpMatrix_destruct(forward);
+    dpMatrix_destruct(backward);
+}
+
 /* getPosteriorProbsWithBanding, impl/pairwiseAligner.c:756-877 (inc/pairwiseAligner.h:245-248): one region, no splitting. */
 void getPosteriorProbsWithBanding(StateMachine *sM, stList *anchorPairs, const SymbolString sX, const SymbolString sY,
                                   PairwiseAlignmentParameters *p, bool alignmentHasRaggedLeftEnd, bool alignmentHasRaggedRightEnd,
@@ -1293,11 +1345,14 @@ void getPosteriorProbsWithBanding(StateMachine *sM, stList *anchorPairs, const S
         check(cpecan_batch_expectations(b, &acc), "cpecan_batch_expectations");
         from_flat(&acc, (Hmm *)extraArgs);
         cpecan_batch_destroy(b);
-    } else {
-        /* a foreign per-diagonal callback would have to be fed DpMatrix rows diagonal by diagonal from the host: that is
-         * the CPU algorithm, which this library does not contain */
-        die("cpecan_hip: getPosteriorProbsWithBanding: the emitter must be one of diagonalCalculationPosteriorMatchProbs, "
-            "diagonalCalculationPosteriorProbs, diagonalCalculationExpectations (routed to the device emitters)");
+    } else { /* a foreign emitter: the dense rows of the region, then the replay */
+        cpecan_dense *dn = NULL;
+        check(cpecan_dense_create(&dn, flat_or_die(sM), &q, cpecan_current_device()), "cpecan_dense_create");
+        if (cpecan_dense_add(dn, cX, sX.length, cY, sY.length, anchors, n, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd) < 0)
+            die("cpecan_hip: %s", cpecan_last_error());
+        check(cpecan_dense_run(dn), "cpecan_dense_run");
+        replay_problem(sM, dn, 0, sX, sY, p, diagonalPosteriorProbFn, extraArgs);
+        cpecan_dense_destroy(dn);
     }
     free(cX);
     free(cY);
@@ -1321,11 +1376,7 @@ void getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps(
     if (diagonalPosteriorProbFn == diagonalCalculationPosteriorMatchProbs) emit = CPECAN_EMIT_MATCH;
     else if (diagonalPosteriorProbFn == diagonalCalculationPosteriorProbs) emit = CPECAN_EMIT_INDEL;
     else if (diagonalPosteriorProbFn == diagonalCalculationExpectations) emit = CPECAN_EMIT_EXPECT;
-    else {
-        die("cpecan_hip: getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps: the emitter must be one of "
-            "diagonalCalculationPosteriorMatchProbs, diagonalCalculationPosteriorProbs, diagonalCalculationExpectations");
-        return;
-    }
+    else emit = -1; /* a foreign emitter: the rectangles become the problems of one dense object and one run */
     cpecan_params q;
     flatten_params(p, &q);
     const int64_t maxMatrixSize = q.splitMatrixBiggerThanThis;
@@ -1337,7 +1388,9 @@ void getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps(
     const int64_t nRect = cpecan_split_points(anchors, n, lX, lY, maxMatrixSize, alignmentHasRaggedLeftEnd, alignmentHasRaggedRightEnd, rect);
     if (nRect < 0) die("cpecan_hip: getSplitPoints: invalid anchors");
     cpecan_batch *b = NULL;
-    check(cpecan_batch_create(&b, flat_or_die(sM), &q, emit, cpecan_current_device()), "cpecan_batch_create");
+    cpecan_dense *dn = NULL;
+    if (emit >= 0) check(cpecan_batch_create(&b, flat_or_die(sM), &q, emit, cpecan_current_device()), "cpecan_batch_create");
+    else check(cpecan_dense_create(&dn, flat_or_die(sM), &q, cpecan_current_device()), "cpecan_dense_create");
     int64_t j = 0;
     int64_t *sub = malloc(sizeof(int64_t) * 3 * (size_t)(n ? n : 1));
     if (!sub) die("cpecan_hip: out of memory");
@@ -1351,9 +1404,26 @@ void getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps(
             m++;
             j++;
         }
-        if (cpecan_batch_add(b, sX + x1, x2 - x1, sY + y1, y2 - y1, sub, m, alignmentHasRaggedLeftEnd || i > 0,
-                             alignmentHasRaggedRightEnd || i < nRect - 1) < 0)
+        const int raggedLeft = alignmentHasRaggedLeftEnd || i > 0, raggedRight = alignmentHasRaggedRightEnd || i < nRect - 1;
+        if ((emit >= 0 ? cpecan_batch_add(b, sX + x1, x2 - x1, sY + y1, y2 - y1, sub, m, raggedLeft, raggedRight)
+                       : cpecan_dense_add(dn, sX + x1, x2 - x1, sY + y1, y2 - y1, sub, m, raggedLeft, raggedRight)) < 0)
             die("cpecan_hip: %s", cpecan_last_error());
+    }
+    if (emit < 0) { /* one run; then the replay rectangle by rectangle, the correction after each, in the reference's order */
+        if (nRect > 0) check(cpecan_dense_run(dn), "cpecan_dense_run");
+        for (int64_t i = 0; i < nRect; i++) {
+            const int64_t x1 = rect[4 * i], y1 = rect[4 * i + 1], x2 = rect[4 * i + 2], y2 = rect[4 * i + 3];
+            SymbolString subX = symbolString_construct(sX + x1, x2 - x1), subY = symbolString_construct(sY + y1, y2 - y1);
+            replay_problem(sM, dn, i, subX, subY, p, diagonalPosteriorProbFn, extraArgs);
+            free(subX.sequence);
+            free(subY.sequence);
+            if (coordinateCorrectionFn != NULL) ((void (*)(int64_t, int64_t, void *))coordinateCorrectionFn)(x1, y1, extraArgs);
+        }
+        cpecan_dense_destroy(dn);
+        free(sub);
+        free(rect);
+        free(anchors);
+        return;
     }
     if (nRect > 0) {
         check(cpecan_batch_upload(b), "cpecan_batch_upload");

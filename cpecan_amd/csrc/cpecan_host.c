@@ -286,6 +286,7 @@ static void kernel_model(const cpecan_model *m, double threshold, CpkModel *k) {
             k->matchEm[x * 5 + y] = (x == CPK_SYM_N || y == CPK_SYM_N) ? -2.772588722 : m->emissionMatch[x * 4 + y];
     }
 }
+void cpk_kernel_model(const cpecan_model *m, double threshold, CpkModel *k) { kernel_model(m, threshold, k); } /* cpecan_dense.c */
 
 /* ------------------------------------------------------------------------------------------------
  * band and split geometry (integers only)
@@ -778,6 +779,7 @@ __attribute__((constructor)) static void init_byte_tables(void) {
     g_symbolOf['G'] = g_symbolOf['g'] = 2;
     g_symbolOf['T'] = g_symbolOf['t'] = 3;
 }
+uint8_t cpk_symbol_of(unsigned char c) { return g_symbolOf[c]; } /* cpecan_dense.c */
 
 /* Writes N + symbols + N at dst[at..] (so that index x addresses base x-1 and x = 0 / x = l+1 read as N); returns the
  * offset behind them. */

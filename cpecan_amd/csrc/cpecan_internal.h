@@ -446,6 +446,43 @@ int cpk_anchor_gaps(const CpkAnchorCall *c, const CpkAnchorList *top, const int3
 int cpk_anchor_splice(const CpkAnchorCall *c, const CpkAnchorList *top, const int32_t *topRuns, const CpkAnchorList *sub,
                       const int32_t *subRuns, double kernelMs);
 
+/* ---- dense forward / backward rows (cpk_dense.inl; host side in cpecan_dense.c) ---- */
+/* One anti-diagonal of a dense problem: its band and the band cells on the problem's earlier diagonals. */
+typedef struct {
+    int32_t xmyL, width;
+    int64_t cellOff;
+} CpkDenseDiag;
+/* One problem = one region (the dense path never splits). */
+typedef struct {
+    int64_t symX, symY; /* first byte of the padded symbol strings (symbol[0] = N, symbol[i] = base i - 1, symbol[l + 1] = N) */
+    int64_t diagOff;    /* first of the problem's lX + lY + 1 CpkDenseDiag, and of its totalUsed entries */
+    int64_t cellBase;   /* first cell of the problem in F and B */
+    int32_t lX, lY;
+    int32_t raggedLeft, raggedRight;
+} CpkDenseProblem;
+/* One traceback (pairwiseAligner.c:791-862) of a problem: the work item of the backward kernel.  The backward rows of
+ * diagonals tbFrom + 1 .. dTop, which the traceback computes and does not emit, go to `side`: the first of them is Bnext. */
+typedef struct {
+    int32_t tbPrev, dTop, tbFrom, problem;
+    int64_t sideBase; /* first cell of the traceback's rows in the side array */
+} CpkDenseSeg;
+/* All problems of a cpecan_dense object in one launch sequence: the forward kernel over the problems, then the backward
+ * kernel over the tracebacks.  F and B: totalCells * S doubles; side: sideCells * S; totals: nDiags.  Host arrays in, host
+ * arrays out; *kernelMs (or NULL): HIP-event time of the two kernels. */
+typedef struct {
+    const CpkDenseProblem *problems;
+    const CpkDenseDiag *diags;
+    const CpkDenseSeg *segs;
+    const uint8_t *symbols;
+    int64_t nProblems, nDiags, nSegs, nSymbolBytes, totalCells, sideCells;
+    double *F, *B, *side, *totals;
+} CpkDenseJob;
+int64_t cpk_dense_device_bytes(const CpkDenseJob *job, int nStates);
+int cpk_dense_run(int device, const CpkModel *model, const CpkDenseJob *job, double *kernelMs);
+/* cpecan_host.c: the kernels' view of a model, and the symbol of a sequence byte */
+void cpk_kernel_model(const cpecan_model *m, double threshold, CpkModel *k);
+uint8_t cpk_symbol_of(unsigned char c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,7 @@ extern "C" const char *cpk_last_error(void) { return g_err; }
 #include "cpk_post.inl"
 #include "cpk_cells.inl"
 #include "cpk_anchor.inl"
+#include "cpk_dense.inl"
 
 // ------------------------------------------------------------------------------------------------
 // host side of the HIP TU: memory, launch, timing
@@ -1827,6 +1828,59 @@ extern "C" int cpk_ref_cells(int device, const CpkModel *model, int mode, const 
     cache_free(device, dOps, opBytes);
     cache_free(device, dBuf, bufBytes);
     return rc;
+}
+
+// Dense rows (cpk_dense.inl): device bytes of a job, and the job itself -- blocking copies around two launches on the null stream.
+extern "C" int64_t cpk_dense_device_bytes(const CpkDenseJob *j, int S) {
+    return (int64_t)sizeof(double) * ((2 * j->totalCells + j->sideCells) * S + j->nDiags) + (int64_t)sizeof(CpkDenseDiag) * j->nDiags +
+           (int64_t)sizeof(CpkDenseProblem) * j->nProblems + (int64_t)sizeof(CpkDenseSeg) * j->nSegs + j->nSymbolBytes;
+}
+extern "C" int cpk_dense_run(int device, const CpkModel *model, const CpkDenseJob *j, double *kernelMs) {
+    const int nDev = cpk_device_count();
+    if (nDev <= 0 || device < 0 || device >= nDev) {
+        cpk_set_error("no usable HIP device (count=%d, requested=%d): the HIP path has no CPU fallback", nDev, device);
+        return CPECAN_ENODEVICE;
+    }
+    if (kernelMs) *kernelMs = 0.0;
+    if (j->nDiags <= 0) return CPECAN_OK;  // nothing but problems without rows
+    CPK_ON_DEVICE(device);
+    const int S = model->nStates;
+    const size_t cellBytes = sizeof(double) * (size_t)j->totalCells * S, sideBytes = sizeof(double) * (size_t)j->sideCells * S;
+    const size_t bytes[8] = {sizeof(CpkDenseProblem) * (size_t)j->nProblems, sizeof(CpkDenseDiag) * (size_t)j->nDiags,
+                             sizeof(CpkDenseSeg) * (size_t)j->nSegs, (size_t)j->nSymbolBytes, cellBytes, cellBytes, sideBytes,
+                             sizeof(double) * (size_t)j->nDiags};
+    const void *src[4] = {j->problems, j->diags, j->segs, j->symbols};
+    void *dst[4] = {j->F, j->B, j->side, j->totals};
+    void *dp[8] = {};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 8 && e == hipSuccess; i++) e = cache_alloc(device, &dp[i], bytes[i]);
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMemcpy(dp[i], src[i], bytes[i], hipMemcpyHostToDevice);
+    hipEvent_t ev[2] = {};
+    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) {
+        const DenseArgs a = {(const CpkDenseProblem *)dp[0], (const CpkDenseDiag *)dp[1], (const CpkDenseSeg *)dp[2], (const uint8_t *)dp[3],
+                             (double *)dp[4], (double *)dp[5], (double *)dp[6], (double *)dp[7]};
+        (void)hipEventRecord(ev[0], nullptr);
+        hipLaunchKernelGGL(cpecan_dense_forward, dim3((unsigned)j->nProblems), dim3(CPK_WAVE), 0, nullptr, *model, a);
+        hipLaunchKernelGGL(cpecan_dense_backward, dim3((unsigned)j->nSegs), dim3(CPK_WAVE), 0, nullptr, *model, a);
+        e = hipGetLastError();
+        (void)hipEventRecord(ev[1], nullptr);
+    }
+    for (int i = 0; i < 4 && e == hipSuccess; i++)  // waits for the kernels (null stream)
+        if (bytes[4 + i]) e = hipMemcpy(dst[i], dp[4 + i], bytes[4 + i], hipMemcpyDeviceToHost);
+    if (e == hipSuccess && kernelMs) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *kernelMs = ms;
+    }
+    for (int i = 0; i < 2; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    for (int i = 0; i < 8; i++) cache_free(device, dp[i], bytes[i]);
+    if (e != hipSuccess) {
+        cpk_set_error("cpk_dense_run: %s", hipGetErrorString(e));
+        return CPECAN_EHIP;
+    }
+    return CPECAN_OK;
 }
 
 extern "C" int64_t cpk_device_bytes(const CpkDevice *d) { return d->bytes; }

@@ -23,8 +23,11 @@
  * of operations -- the library holds no CPU implementation of the recurrences).  sM->cellCalculate, which takes an
  * arbitrary per-transition callback, hands that callback the model's ordered transition list (states, emission and
  * transition log-probabilities, absent neighbours skipped: impl/stateMachine.c:450-480, :689-714) -- the vtable's contract,
- * no arithmetic of its own (round 4; it aborted before); getPosteriorProbsWithBanding accepts the reference's three
- * emitters (recognised by address, see below) and refuses foreign diagonal callbacks.
+ * no arithmetic of its own (round 4; it aborted before); getPosteriorProbsWithBanding runs the reference's three
+ * emitters (recognised by address, see below) on their own kernels and replays every other diagonal callback over dense
+ * rows from the GPU (cpecan_dense.h), with the reference's calls, totals and live rows -- except backward row xay - 2,
+ * which the reference holds half-accumulated at the call for xay and this layer does not serve, and regions above
+ * CPECAN_DENSE_MAX_BYTES.
  */
 #ifndef CPECAN_DROPIN_H_
 #define CPECAN_DROPIN_H_
@@ -280,7 +283,12 @@ double logAdd(double x, double y);
  * The per-diagonal emitters of the reference read DpMatrix rows; the engine keeps its DP diagonals on the GPU, so as
  * arguments of getPosteriorProbsWithBanding the three emitters below are TOKENS: recognised by address and routed to the
  * device emitter (extraArgs as in the reference: {alignedPairs} / {alignedPairs, _, gapXPairs, _, gapYPairs} / Hmm*); any
- * other callback is refused (abort with a message).  Lists are appended in the reference emitter's own order.  Called
+ * other callback is replayed over dense rows from the GPU (cpecan_dense.h): called once per diagonal in the reference's
+ * order with the total used there; at the call for xay of a traceback (tbPrev, dTop, tbFrom) the forward matrix holds rows
+ * tbPrev .. xay and, unless dTop is the last diagonal, tbFrom .. dTop (so row xay - 2 is NULL at xay == tbPrev + 1 for
+ * tbPrev >= 1, as in the reference), the backward matrix rows xay - 1 .. xay + 1 inside tbPrev + 1 .. dTop with their final
+ * values; backward row xay - 2, which the reference holds half-accumulated at that moment, is absent.  A region whose
+ * rows exceed CPECAN_DENSE_MAX_BYTES on the device aborts with a message that names the bytes.  Lists are appended in the reference emitter's own order.  Called
  * directly on DpMatrix rows (as the reference's test_diagonalDPCalculations does) the two posterior emitters work on those
  * rows, their exp() on the GPU. */
 typedef struct _dpMatrix DpMatrix;
