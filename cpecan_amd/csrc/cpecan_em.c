@@ -252,6 +252,9 @@ struct cpecan_em_trainer {
     int nFastas;
     cpecan_em_timing timing;
     int concurrentTrials; /* cpecan_em_trainer_set_concurrent_trials: trials per launch (1: one after another) */
+    /* cpecan_em_trainer_alignments: the anchors of the last E-step of the last trial (malloc'd; NULL before a training) */
+    int64_t *lastRuns, *lastNRuns;
+    int64_t lastN;
 };
 
 static char *dup_str(const char *s) {
@@ -310,6 +313,8 @@ void cpecan_em_trainer_destroy(cpecan_em_trainer *t) {
     free(t->fastas);
     free(t->inputModel);
     free(t->blastFile);
+    free(t->lastRuns);
+    free(t->lastNRuns);
     free(t);
 }
 
@@ -341,6 +346,10 @@ int cpecan_em_trainer_set_concurrent_trials(cpecan_em_trainer *t, int n) {
         cpk_set_error("concurrent trials: %d, 1 to %d are possible", n, CPECAN_MAX_MODEL_SLOTS);
         return CPECAN_EINVAL;
     }
+    if (n > 1 && t->opt.updateTheBand) {
+        cpk_set_error("updateTheBand with %d concurrent trials: the trials' bands differ, one resident batch cannot serve them", n);
+        return CPECAN_EINVAL;
+    }
     t->concurrentTrials = n;
     return CPECAN_OK;
 }
@@ -368,31 +377,24 @@ static int start_model(cpecan_em_trainer *t, uint64_t *rng, cpecan_hmm *h) {
     return rc;
 }
 
-/* One trial: `iterations` E- and M-steps from h, the model file rewritten after every one (calculateMaximisation). */
-static int run_trial(cpecan_em_trainer *t, cpecan_expect_set *set, int64_t nJobs, cpecan_hmm *h, double *running,
-                     const char *path) {
-    int rc = cpecan_em_write_model(h, NULL, 0, path);
-    cpecan_model m;
-    if (rc == CPECAN_OK)
-        rc = t->opt.useDefaultModelAsStart ? cpecan_model_default(&m, t->type) : cpecan_model_from_hmm(&m, h);
-    for (int it = 0; rc == CPECAN_OK && it < t->opt.iterations; it++) {
-        cpecan_hmm acc;
-        /* one pseudo-count per job, as one cPecanRealign --outputExpectations run per job adds it */
-        rc = cpecan_hmm_init(&acc, t->type, EM_PSEUDO * (double)(nJobs > 0 ? nJobs : 1));
-        if (rc == CPECAN_OK) rc = cpecan_expect_set_run(set, &m, &acc);
-        if (rc != CPECAN_OK) break;
-        cpecan_hmm_normalise(&acc);
-        running[it] = acc.likelihood;
-        if (!t->opt.trainEmissions)
-            memcpy(acc.emissions, h->emissions, sizeof acc.emissions);
-        else if (t->opt.tieEmissions)
-            cpecan_hmm_tie_emissions(&acc);
-        *h = acc;
-        rc = cpecan_em_write_model(h, NULL, 0, path);
-        if (rc == CPECAN_OK) rc = cpecan_model_from_hmm(&m, h);
+int cpecan_em_trainer_alignments(const cpecan_em_trainer *t, const int64_t **runs, const int64_t **nRuns, int64_t *n) {
+    if (!t || !runs || !nRuns || !n) return CPECAN_EINVAL;
+    if (!t->lastRuns || !t->lastNRuns) {
+        cpk_set_error("no training with updateTheBand yet");
+        return CPECAN_ESTATE;
     }
-    if (rc == CPECAN_OK) rc = cpecan_em_write_model(h, running, t->opt.iterations, path);
-    return rc;
+    *runs = t->lastRuns;
+    *nRuns = t->lastNRuns;
+    *n = t->lastN;
+    return CPECAN_OK;
+}
+
+static void keep_alignments(cpecan_em_trainer *t, int64_t *runs, int64_t *nRuns, int64_t n) {
+    free(t->lastRuns);
+    free(t->lastNRuns);
+    t->lastRuns = runs;
+    t->lastNRuns = nRuns;
+    t->lastN = n;
 }
 
 /* The M-step of one trial from its E-step's counts (calculateMaximisation). */
@@ -404,6 +406,68 @@ static void m_step(const cpecan_em_trainer *t, cpecan_hmm *acc, cpecan_hmm *h, d
     else if (t->opt.tieEmissions)
         cpecan_hmm_tie_emissions(acc);
     *h = *acc;
+}
+
+/* One trial: `iterations` E- and M-steps from h, the model file rewritten after every one (calculateMaximisation).  With
+ * updateTheBand the sample is realigned between two iterations under the model of the M-step and the next E-step runs on
+ * an EXPECT set planned for the new anchors; without it nothing of that runs.  first: the set of the sampled cigars' own
+ * anchors, which every trial starts from. */
+static int run_trial(cpecan_em_trainer *t, cpecan_expect_set *first, const cpecan_cigar *sample, int64_t nSample,
+                     int64_t nJobs, cpecan_hmm *h, double *running, const char *path, int *reanchoredOut) {
+    int rc = cpecan_em_write_model(h, NULL, 0, path);
+    cpecan_model m;
+    if (rc == CPECAN_OK)
+        rc = t->opt.useDefaultModelAsStart ? cpecan_model_default(&m, t->type) : cpecan_model_from_hmm(&m, h);
+    cpecan_expect_set *own = NULL, *set = first;
+    int reanchored = 0;
+    int64_t *curRuns = NULL, *curNRuns = NULL; /* the anchors `set` runs on; NULL: the sampled cigars' own */
+    for (int it = 0; rc == CPECAN_OK && it < t->opt.iterations; it++) {
+        cpecan_hmm acc;
+        /* one pseudo-count per job, as one cPecanRealign --outputExpectations run per job adds it */
+        rc = cpecan_hmm_init(&acc, t->type, EM_PSEUDO * (double)(nJobs > 0 ? nJobs : 1));
+        if (rc == CPECAN_OK) rc = cpecan_expect_set_run(set, &m, &acc);
+        if (rc != CPECAN_OK) break;
+        m_step(t, &acc, h, &running[it]);
+        rc = cpecan_em_write_model(h, NULL, 0, path);
+        if (rc == CPECAN_OK) rc = cpecan_model_from_hmm(&m, h);
+        if (rc != CPECAN_OK || !t->opt.updateTheBand || it + 1 >= t->opt.iterations) continue;
+        int64_t *runs = NULL, *nRuns = NULL;
+        const double t0 = now_ms();
+        rc = cpecan_realigner_set_model(t->r, &m);
+        /* the realigned cigars replace the alignments (cPecanEm.py:212-215): from the second realignment on the band is
+         * that of the realignment before, not the sample's */
+        if (rc == CPECAN_OK) rc = cpecan_realigner_reanchor_runs(t->r, sample, nSample, curRuns, curNRuns, &runs, &nRuns);
+        const double t1 = now_ms();
+        if (rc == CPECAN_OK) {
+            cpecan_expect_set_destroy(own); /* (its memory goes back to the pool the new set is taken from) */
+            own = NULL;
+            rc = cpecan_expect_set_create_runs(&own, t->r, sample, nSample, runs, nRuns);
+            set = own;
+        }
+        t->timing.realignMs += t1 - t0;
+        t->timing.handoffMs += cpk_realigner_reanchor_ms(t->r);
+        t->timing.replanMs += now_ms() - t1;
+        if (rc == CPECAN_OK) {
+            free(curRuns);
+            free(curNRuns);
+            curRuns = runs;
+            curNRuns = nRuns;
+            reanchored = 1;
+        } else {
+            free(runs);
+            free(nRuns);
+        }
+    }
+    cpecan_expect_set_destroy(own);
+    if (rc == CPECAN_OK && reanchored) {
+        keep_alignments(t, curRuns, curNRuns, nSample);
+    } else {
+        free(curRuns);
+        free(curNRuns);
+    }
+    *reanchoredOut = reanchored; /* 0: the last E-step ran on the sample's own anchors */
+    if (rc == CPECAN_OK) rc = cpecan_em_write_model(h, running, t->opt.iterations, path);
+    return rc;
 }
 
 /* A round of n trials side by side: every iteration is ONE cpecan_expect_set_run_models over the round's models plus the
@@ -436,6 +500,12 @@ static int run_round(cpecan_em_trainer *t, cpecan_expect_set *set, int64_t nJobs
 int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, const char *outputModel, cpecan_hmm *best,
                     double *running) {
     if (!t || (!in && n > 0) || n < 0 || !outputModel) return CPECAN_EINVAL;
+    if (t->opt.updateTheBand && t->concurrentTrials > 1) {
+        cpk_set_error("updateTheBand with %d concurrent trials: the trials' bands differ, one resident batch cannot serve them",
+                      t->concurrentTrials);
+        return CPECAN_EINVAL;
+    }
+    keep_alignments(t, NULL, NULL, 0);
     const double t0 = now_ms();
     memset(&t->timing, 0, sizeof t->timing);
     const int iters = t->opt.iterations;
@@ -459,7 +529,7 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
     }
     uint64_t rng = t->opt.seed ^ 0x5DEECE66Dull; /* the random starts: a stream of their own, from the same seed */
     const double t1 = now_ms();
-    int bestTrial = 0;
+    int bestTrial = 0, reanchored = 0;
     if (conc > 1) {
         /* every start model first, in trial order, from the same generator state (the trials' iterations draw nothing):
          * trial k starts where it starts in a sequential run.  Then rounds of up to `conc` trials. */
@@ -484,9 +554,14 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
         if (trials == 1) strcpy(path, outputModel);
         else if (t->opt.outputTrialHmms) sprintf(path, "%s_%d", outputModel, k);
         else sprintf(path, "%s.trial_%d", outputModel, k);
-        rc = run_trial(t, set, nJobs, &hmms[k], runs + (size_t)k * (size_t)iters, path);
+        rc = run_trial(t, set, sample, nSample, nJobs, &hmms[k], runs + (size_t)k * (size_t)iters, path, &reanchored);
         if (trials > 1 && !t->opt.outputTrialHmms) remove(path);
         if (rc == CPECAN_OK && hmms[k].likelihood > hmms[bestTrial].likelihood) bestTrial = k;
+    }
+    if (rc == CPECAN_OK && t->opt.updateTheBand && !reanchored) { /* the last trial never left the sample's own anchors */
+        int64_t *sampleRuns = NULL, *sampleNRuns = NULL;
+        rc = cpk_realigner_cigar_runs(t->r, sample, nSample, &sampleRuns, &sampleNRuns);
+        if (rc == CPECAN_OK) keep_alignments(t, sampleRuns, sampleNRuns, nSample);
     }
     const double t2 = now_ms();
     if (rc == CPECAN_OK && trials > 1) /* expectationMaximisationTrials2: the trial with the highest likelihood */
@@ -503,6 +578,7 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
         if (rc == CPECAN_OK) rc = cpecan_em_blast_matrix(&hmms[bestTrial], (double)gc / (double)total, scores, &gapOpen, &gapExtend);
         if (rc == CPECAN_OK) rc = cpecan_em_write_lastz_matrix(t->blastFile, scores, gapOpen, gapExtend);
     }
+    if (rc != CPECAN_OK) keep_alignments(t, NULL, NULL, 0);
     if (rc == CPECAN_OK) {
         if (best) *best = hmms[bestTrial];
         if (running && iters > 0) memcpy(running, runs + (size_t)bestTrial * (size_t)iters, sizeof(double) * (size_t)iters);

@@ -20,6 +20,7 @@ static void usage(void) {
             "--concurrentTrials N (1; up to 8 trials per kernel launch, more trials run in rounds)\n"
             "--useDefaultModelAsStart  --setJukesCantorStartingEmissions F  --trainEmissions  --tieEmissions\n"
             "--maxAlignmentLengthPerJob N (1000000)  --maxAlignmentLengthToSample N (50000000)  --seed N (0)\n"
+            "--updateTheBand (realign the sample after every iteration; not with --concurrentTrials above 1)\n"
             "--blastScoringMatrixFile FILE  --optionsToRealign \"...\" (default \"--diagonalExpansion=10\n"
             "--splitMatrixBiggerThanThis=3000\"; -r/-o/-t/-l/-L and their long names)  --device N  --devices LIST\n"
             "--logLevel L (ignored)  -h --help\n");
@@ -218,7 +219,10 @@ int main(int argc, char **argv) {
             break;
         case kLogLevel: break;
         case kXml: fprintf(stderr, "cpecan_em: --outputXMLModelFile is not supported\n"); return 1;
-        case kUpdateBand: fprintf(stderr, "cpecan_em: --updateTheBand is not supported (it re-plans every iteration)\n"); return 1;
+        case kUpdateBand:
+            fprintf(stderr, "cpecan_em: --updateTheBand: the sampled alignments are realigned after every iteration\n");
+            o.updateTheBand = 1;
+            break;
         default: usage(); return 1;
         }
     }

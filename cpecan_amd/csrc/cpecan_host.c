@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "cpecan_internal.h"
+#include "cpecan_realign.h" /* cpecan_batch_set_next_runs / cpecan_batch_next_runs / cpecan_next_runs_of_pairs */
 #include "cpecan_sets.h" /* cpecan_batch_set_quintuples / cpecan_batch_quintuples */
 #include "cpecan_band.inl"
 
@@ -490,6 +491,12 @@ struct cpecan_batch {
     int32_t *quints;                 /* the downloaded run's records (host pool), its nProblems + 1 offsets and nProblems sums */
     int64_t *quintOffsets, *quintSums;
     double quintStageMs;
+    /* cpecan_batch_set_next_runs (include/cpecan_realign.h): the ordered alignment leaves the device as anchor runs */
+    int nextRuns;
+    int64_t nextTrim, nextExpansion;
+    int64_t *nextRunVals;    /* the downloaded run's quadruples (x, y, length, expansion), problem i at 4 * nextRunOffsets[i] */
+    int64_t *nextRunOffsets; /* [nProblems + 1], or NULL: the downloaded run was not asked for them */
+    double nextStageMs;
     cpecan_stats stats;
     /* cpecan_batch_download_begin / _end */
     pthread_t dlThread;
@@ -718,6 +725,9 @@ static void free_results(cpecan_batch *b) {
     b->edges = NULL;
     b->quints = NULL;
     b->quintOffsets = b->quintSums = NULL;
+    free(b->nextRunVals);
+    free(b->nextRunOffsets);
+    b->nextRunVals = b->nextRunOffsets = NULL;
 }
 
 void cpecan_batch_destroy(cpecan_batch *b) {
@@ -1955,6 +1965,8 @@ static void post_layout(CpkPostJob *job, CpkPostProblem *pp, int64_t i, const in
     job->chainSlots += n[0] + 1;
     job->meaCap += n[0];
     job->shiftCap += n[0] + imin(lX, lY) + 1;
+    pp->nextOff = job->nextSlots;
+    job->nextSlots += 2 * lX;
     (void)i;
 }
 
@@ -1985,7 +1997,7 @@ static int run_post(cpecan_batch *b) {
         /* identity scores and the left shift compare letters; neither exists without a consumer (cpecan_batch_identity_scores) */
         job.chars = job.flags ? b->chars : NULL;
         job.nChars = job.flags ? b->nChars : 0;
-        if (job.flags & (CPECAN_POST_MEA | CPECAN_POST_ORDERED)) {
+        if ((job.flags & (CPECAN_POST_MEA | CPECAN_POST_ORDERED)) && !b->nextRuns) { /* (with the next-runs stage list 3 stays on the device) */
             b->postMea = cpk_host_alloc(sizeof(int32_t) * 3 * (size_t)(job.meaCap ? job.meaCap : 1));
             job.mea = b->postMea;
             if (!b->postMea) rc = CPECAN_ENOMEM;
@@ -2007,7 +2019,29 @@ static int run_post(cpecan_batch *b) {
         job.sums = b->quintSums;
         job.stageMs = &b->quintStageMs;
     }
+    int32_t *runCounts = NULL, *runVals = NULL;
+    if (rc == CPECAN_OK && b->nextRuns) { /* the next-runs stage: list 3 of every problem as the anchor runs of the next E-step */
+        runCounts = malloc(sizeof(int32_t) * (size_t)(b->nProblems ? b->nProblems : 1));
+        b->nextRunOffsets = calloc((size_t)(b->nProblems + 1), sizeof(int64_t));
+        b->nextStageMs = 0.0;
+        if (!runCounts || !b->nextRunOffsets) rc = CPECAN_ENOMEM;
+        job.nextRuns = 1;
+        job.nextTrim = (int32_t)(b->nextTrim < ((int64_t)1 << 30) ? b->nextTrim : ((int64_t)1 << 30)); /* longer than any sequence */
+        job.nextExpansion = (int32_t)b->nextExpansion;
+        job.runCounts = runCounts;
+        job.runOffsets = b->nextRunOffsets;
+        job.runsOut = &runVals;
+        job.nextMs = &b->nextStageMs;
+    }
     if (rc == CPECAN_OK) rc = cpk_device_post(b->dev, &job);
+    if (rc == CPECAN_OK && b->nextRuns) { /* widened to what cpecan_batch_add_many_runs takes */
+        const int64_t total = 4 * b->nextRunOffsets[b->nProblems];
+        b->nextRunVals = malloc(sizeof(int64_t) * (size_t)(total ? total : 1));
+        if (!b->nextRunVals) rc = CPECAN_ENOMEM;
+        for (int64_t k = 0; rc == CPECAN_OK && k < total; k++) b->nextRunVals[k] = runVals[k];
+    }
+    cpk_host_free(runVals);
+    free(runCounts);
     if (rc == CPECAN_OK && b->quintNames) {
         for (int64_t i = 0; i < b->nProblems; i++) b->quintOffsets[i] = pp[i].meaOut;
         b->quintOffsets[b->nProblems] = job.meaCap;
@@ -2018,6 +2052,8 @@ static int run_post(cpecan_batch *b) {
         if (job.flags & CPECAN_POST_LEFT_SHIFT) {
             pr->triples[3] = b->postShift + 3 * pp[i].shiftOut;
             pr->nTriples[3] = counts[2 * i + 1];
+        } else if (b->nextRuns) {
+            pr->nTriples[3] = counts[2 * i];
         } else if (job.flags & (CPECAN_POST_MEA | CPECAN_POST_ORDERED)) {
             pr->triples[3] = b->postMea + 3 * pp[i].meaOut;
             pr->nTriples[3] = counts[2 * i];
@@ -2043,6 +2079,7 @@ int cpecan_batch_set_post(cpecan_batch *b, int flags, double gapGamma) {
     if (flags && (b->emit == CPECAN_EMIT_FORWARD || b->emit == CPECAN_EMIT_EXPECT)) return CPECAN_EINVAL;
     b->postFlags = flags;
     b->postGapGamma = gapGamma;
+    if (!(flags & CPECAN_POST_ORDERED)) b->nextRuns = 0; /* the next-runs stage goes with the list it reads */
     return CPECAN_OK;
 }
 
@@ -2095,6 +2132,107 @@ int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offse
     b->quintOffsets = b->quintSums = NULL;
     b->downloaded = 0; /* the run's results have left the batch */
     return CPECAN_OK;
+}
+
+/* ---- the next-runs stage (include/cpecan_realign.h) ---- */
+int cpecan_batch_set_next_runs(cpecan_batch *b, int64_t trim, int64_t expansion) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b) return CPECAN_EINVAL;
+    if (b->frozen) {
+        cpk_set_error("cpecan_batch_set_next_runs: before upload");
+        return CPECAN_EINVAL;
+    }
+    if (expansion == CPECAN_NEXT_RUNS_OFF) {
+        b->nextRuns = 0;
+        return CPECAN_OK;
+    }
+    if (!(b->postFlags & CPECAN_POST_ORDERED)) {
+        cpk_set_error("the next runs are made of the ordered alignment: select CPECAN_POST_ORDERED first");
+        return CPECAN_EINVAL;
+    }
+    if (trim < 0 || expansion < 0 || expansion > INT32_MAX) {
+        cpk_set_error("cpecan_batch_set_next_runs: trim %lld, expansion %lld", (long long)trim, (long long)expansion);
+        return CPECAN_EINVAL;
+    }
+    b->nextRuns = 1;
+    b->nextTrim = trim;
+    b->nextExpansion = expansion;
+    return CPECAN_OK;
+}
+
+int cpecan_batch_next_runs(const cpecan_batch *b, int64_t problem, const int64_t **runs, int64_t *nRuns) {
+    if (dl_busy(b)) return CPECAN_ESTATE;
+    if (!b || !b->downloaded) return CPECAN_ESTATE;
+    if (!b->nextRunOffsets) {
+        cpk_set_error("the next runs were not asked for: cpecan_batch_set_next_runs before the upload");
+        return CPECAN_ESTATE;
+    }
+    if (problem < 0 || problem >= b->nProblems || !runs || !nRuns) return CPECAN_EINVAL;
+    *runs = b->nextRunVals + 4 * b->nextRunOffsets[problem];
+    *nRuns = b->nextRunOffsets[problem + 1] - b->nextRunOffsets[problem];
+    return CPECAN_OK;
+}
+
+double cpk_batch_next_runs_ms(const cpecan_batch *b) { return b ? b->nextStageMs : 0.0; }
+
+static int cmp_pair_xy(const void *a, const void *b) {
+    const int64_t *p = a, *q = b;
+    if (p[0] != q[0]) return p[0] < q[0] ? -1 : 1;
+    return p[1] < q[1] ? -1 : (p[1] > q[1] ? 1 : 0);
+}
+
+/* The definition of the stage on the host: the pairs sorted, cut into blocks, trimmed, filtered, joined into runs. */
+int64_t cpecan_next_runs_of_pairs(const int32_t *triples, int64_t n, const char *sX, int64_t lX, const char *sY, int64_t lY,
+                                  int64_t trim, int64_t expansion, int64_t *runs, int64_t cap) {
+    if (n < 0 || (n > 0 && !triples) || lX < 0 || lY < 0 || (lX > 0 && !sX) || (lY > 0 && !sY) || trim < 0 || expansion < 0 ||
+        cap < 0 || (cap > 0 && !runs))
+        return CPECAN_EINVAL;
+    int64_t *xy = malloc(sizeof(int64_t) * 2 * (size_t)(n ? n : 1));
+    if (!xy) return CPECAN_ENOMEM;
+    for (int64_t i = 0; i < n; i++) {
+        xy[2 * i] = triples[3 * i + 1];
+        xy[2 * i + 1] = triples[3 * i + 2];
+        if (xy[2 * i] < 0 || xy[2 * i] >= lX || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= lY) {
+            free(xy);
+            cpk_set_error("cpecan_next_runs_of_pairs: pair %lld lies outside the sequences", (long long)i);
+            return CPECAN_EINVAL;
+        }
+    }
+    qsort(xy, (size_t)n, 2 * sizeof(int64_t), cmp_pair_xy);
+    for (int64_t i = 1; i < n; i++)
+        if (xy[2 * i] <= xy[2 * i - 2] || xy[2 * i + 1] <= xy[2 * i - 1]) {
+            free(xy);
+            cpk_set_error("cpecan_next_runs_of_pairs: the pairs are no chain");
+            return CPECAN_EINVAL;
+        }
+    int64_t count = 0;
+    for (int64_t i = 0; i < n;) {
+        int64_t len = 1; /* the block: pairs i .. i + len - 1 */
+        while (i + len < n && xy[2 * (i + len)] == xy[2 * i] + len && xy[2 * (i + len) + 1] == xy[2 * i + 1] + len) len++;
+        int64_t open = 0; /* columns of the run that is open */
+        for (int64_t l = trim; l < len - trim; l++) {
+            const int64_t x = xy[2 * i] + l, y = xy[2 * i + 1] + l;
+            const uint8_t a = g_upperOf[(unsigned char)sX[x]], c = g_upperOf[(unsigned char)sY[y]];
+            if (a != c || a == 'N') {
+                open = 0;
+                continue;
+            }
+            if (open == 0) {
+                if (count < cap) {
+                    runs[4 * count] = x;
+                    runs[4 * count + 1] = y;
+                    runs[4 * count + 2] = 0;
+                    runs[4 * count + 3] = expansion;
+                }
+                count++;
+            }
+            open++;
+            if (count <= cap) runs[4 * (count - 1) + 2] = open;
+        }
+        i += len;
+    }
+    free(xy);
+    return count;
 }
 
 int cpecan_batch_set_band_edge(cpecan_batch *b, int on) {
@@ -2294,6 +2432,11 @@ int cpecan_batch_download(cpecan_batch *b) {
             b->quintStageMs = 0.0;
             if (!b->quints || !b->quintOffsets || !b->quintSums) return CPECAN_ENOMEM;
         }
+        if (b->nextRuns) { /* no region, no pair, no run */
+            b->nextRunVals = malloc(sizeof(int64_t));
+            b->nextRunOffsets = calloc((size_t)(b->nProblems + 1), sizeof(int64_t));
+            if (!b->nextRunVals || !b->nextRunOffsets) return CPECAN_ENOMEM;
+        }
         b->downloaded = 1;
         return CPECAN_OK;
     }
@@ -2360,7 +2503,7 @@ int cpecan_batch_download(cpecan_batch *b) {
         if (rc == CPECAN_OK) rc = run_post(b); /* consumers of the lists, on the device, before they leave it */
         const double tD5 = now_ms();
         /* with the quintuple stage the records have left the device in run_post: the triples stay where they are */
-        if (rc == CPECAN_OK && !b->quintNames) rc = cpk_device_fetch(b->dev, b->results, total, &b->stats.d2hMs);
+        if (rc == CPECAN_OK && !b->quintNames && !b->nextRuns) rc = cpk_device_fetch(b->dev, b->results, total, &b->stats.d2hMs);
         b->stats.pairs = total;
         if (trace_host())
             fprintf(stderr, "cpecan download: wait + counts %.1f ms, overflow scan %.1f, list plan %.1f (%lld chunks), gather %.1f, consumers %.1f, fetch %.1f (%lld triples)\n",
@@ -2415,6 +2558,10 @@ int cpecan_batch_result(const cpecan_batch *b, int64_t problem, int which, const
     if (which >= b->nLists && !(which == 3 && (b->postFlags & (CPECAN_POST_MEA | CPECAN_POST_ORDERED)))) return CPECAN_EINVAL;
     if (which < 3 && b->quints) {
         cpk_set_error("the batch downloads quintuples (cpecan_batch_set_quintuples): its triples stayed on the device");
+        return CPECAN_ESTATE;
+    }
+    if (b->nextRunOffsets) {
+        cpk_set_error("the batch downloads anchor runs (cpecan_batch_set_next_runs): its triples stayed on the device");
         return CPECAN_ESTATE;
     }
     *triples = b->problems[problem].triples[which];

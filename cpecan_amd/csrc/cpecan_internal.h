@@ -216,6 +216,7 @@ typedef struct {
     int64_t charX, charY;    /* raw upper-case sequences (left shift) */
     int64_t meaOut;          /* first of n[0] output triples */
     int64_t shiftOut;        /* first of n[0] + min(lX, lY) + 1 output triples */
+    int64_t nextOff;         /* first of 2 lX scratch words of the next-runs stage (y of every column, distance to the block's start) */
 } CpkPostProblem;
 
 #define CPK_POST_SCORES 5
@@ -240,6 +241,15 @@ typedef struct {
     int32_t *quints;         /* host out: [meaCap*5], problem i at 5 * problems[i].meaOut */
     int64_t *sums;           /* host out: [nProblems] */
     double *stageMs;         /* host out, or NULL: HIP-event time of the stage's kernel */
+    /* the next-runs stage (cpecan_batch_set_next_runs, include/cpecan_realign.h), behind ORDERED; nextRuns 0: not selected,
+     * nothing of it is allocated or launched */
+    int nextRuns;
+    int32_t nextTrim, nextExpansion;
+    int64_t nextSlots;       /* total of the problems' 2 lX scratch words */
+    int32_t *runCounts;      /* host out: [nProblems] */
+    int64_t *runOffsets;     /* host out: [nProblems + 1] prefix sums of runCounts */
+    int32_t **runsOut;       /* host out: *runsOut is allocated by the stage (cpk_host_free), runOffsets[nProblems] quadruples */
+    double *nextMs;          /* host out, or NULL: HIP-event time of the stage's two kernels and the copy between them */
 } CpkPostJob;
 
 /* Runs the job on the batch's compact result buffer (after cpk_device_gather, before cpk_device_fetch). */
@@ -275,6 +285,17 @@ int cpk_overflow_scan(CpkRegion *regions, int64_t nRegions, CpkSegment *segs, in
  * the caller -- quints goes back with cpk_host_free, offsets and sums with free -- with the stage's kernel time; the batch
  * forgets them (cpecan_sets.c keeps them as its result). */
 int cpk_batch_take_quintuples(cpecan_batch *b, int32_t **quints, int64_t **offsets, int64_t **sums, double *stageMs);
+/* HIP-event time of the next-runs stage of the last download (cpecan_batch_set_next_runs): both kernels and the copy of
+ * the counts between them. */
+double cpk_batch_next_runs_ms(const cpecan_batch *b);
+struct cpecan_realigner;
+/* The same of the last cpecan_realigner_reanchor: the slowest shard's (cpecan_realign.c). */
+double cpk_realigner_reanchor_ms(const struct cpecan_realigner *r);
+struct cpecan_cigar;
+/* The exact-match anchor runs of n cigars as every realign and expectations call makes them (cPecanRealign.c:511-529), on the
+ * host: *nRuns n counts, *runs the quadruples one cigar after the other, both malloc'd (cpecan_realign.c). */
+int cpk_realigner_cigar_runs(const struct cpecan_realigner *r, const struct cpecan_cigar *in, int64_t n, int64_t **runs,
+                             int64_t **nRuns);
 /* Plans an unfrozen batch as cpecan_batch_upload would and then its launches (cpk_plan.inl, plan_batch) for a device of
  * numCUs compute units and memBytes of free memory that is not there: a kernel is taken to use the registers its build
  * allows.  out receives CPK_LAUNCH_PLAN_FIELDS numbers per launch class, in launch order (cpk_plan_describe); returns

@@ -1677,6 +1677,55 @@ static int post_core(PostScratch &sc, int32_t *dTriples, const CpkPostJob *job) 
             HIP_TRY(hipMemcpyAsync(job->quints, dQuints, sizeof(int32_t) * 5 * (size_t)job->meaCap, hipMemcpyDeviceToHost, st));
         if (job->sums) HIP_TRY(hipMemcpyAsync(job->sums, dSums, sizeof(long long) * (size_t)nP, hipMemcpyDeviceToHost, st));
     }
+    // the next-runs stage: the ordered alignment as the anchor runs of the next E-step; only counts and runs leave the device
+    hipEvent_t evNext[2] = {nullptr, nullptr};
+    StageEvents nextEvents{evNext};
+    if (job->nextRuns) {
+        if (!(job->flags & kPostOrdered) || !dChars || !dMea || !job->runCounts || !job->runOffsets || !job->runsOut) {
+            cpk_set_error("the next-runs stage needs the ordered alignment and the raw sequences");
+            return CPECAN_EINVAL;
+        }
+        int32_t *dNext = nullptr, *dRunCounts = nullptr;
+        int4 *dRuns = nullptr, *dPacked = nullptr;
+        int64_t *dPackedOff = nullptr;
+        if (int rc = sc.alloc(&dNext, (size_t)job->nextSlots)) return rc;
+        if (int rc = sc.alloc(&dRunCounts, (size_t)nP)) return rc;
+        if (int rc = sc.alloc(&dRuns, (size_t)job->meaCap)) return rc;
+        if (job->nextMs) {
+            HIP_TRY(hipEventCreate(&evNext[0]));
+            HIP_TRY(hipEventCreate(&evNext[1]));
+            HIP_TRY(hipEventRecord(evNext[0], st));
+        }
+        hipLaunchKernelGGL(cpecan_post_next_runs, dim3((unsigned)nP), dim3(64), 0, st, dProblems, dMea, dCounts, dChars, dNext,
+                           job->nextTrim, job->nextExpansion, dRuns, dRunCounts);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(job->runCounts, dRunCounts, sizeof(int32_t) * (size_t)nP, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        int64_t total = 0;
+        for (int64_t i = 0; i < nP; i++) {
+            if (job->runCounts[i] < 0 || job->runCounts[i] > job->problems[i].n[0]) {
+                cpk_set_error("internal: the next-runs stage counted %d runs for the %d pairs of problem %lld", job->runCounts[i],
+                              job->problems[i].n[0], (long long)i);
+                return CPECAN_ESTATE;
+            }
+            job->runOffsets[i] = total;
+            total += job->runCounts[i];
+        }
+        job->runOffsets[nP] = total;
+        int32_t *hostRuns = static_cast<int32_t *>(cpk_host_alloc(sizeof(int32_t) * 4 * (size_t)(total ? total : 1)));
+        if (!hostRuns) return CPECAN_ENOMEM;
+        *job->runsOut = hostRuns;
+        if (total > 0) {
+            if (int rc = sc.alloc(&dPackedOff, (size_t)nP)) return rc;
+            if (int rc = sc.alloc(&dPacked, (size_t)total)) return rc;
+            HIP_TRY(hipMemcpyAsync(dPackedOff, job->runOffsets, sizeof(int64_t) * (size_t)nP, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(cpecan_post_pack_runs, dim3((unsigned)nP), dim3(64), 0, st, dProblems, dRuns, dRunCounts, dPackedOff,
+                               dPacked);
+            HIP_TRY(hipGetLastError());
+        }
+        if (job->nextMs) HIP_TRY(hipEventRecord(evNext[1], st));
+        if (total > 0) HIP_TRY(hipMemcpyAsync(hostRuns, dPacked, sizeof(int4) * (size_t)total, hipMemcpyDeviceToHost, st));
+    }
     if (job->scores)
         HIP_TRY(hipMemcpyAsync(job->scores, dScores, sizeof(double) * (size_t)nP * kPostScores, hipMemcpyDeviceToHost, st));
     if (job->counts) HIP_TRY(hipMemcpyAsync(job->counts, dCounts, sizeof(int32_t) * (size_t)nP * 2, hipMemcpyDeviceToHost, st));
@@ -1689,6 +1738,11 @@ static int post_core(PostScratch &sc, int32_t *dTriples, const CpkPostJob *job) 
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, evStage[0], evStage[1]));
         *job->stageMs = ms;
+    }
+    if (job->nextRuns && job->nextMs) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, evNext[0], evNext[1]));
+        *job->nextMs = ms;
     }
     return CPECAN_OK;
 }

@@ -408,6 +408,7 @@ struct cpecan_realigner {
     int64_t minEdgeScore;
     int32_t *lastRounds;
     int64_t nLastRounds;
+    double lastReanchorMs; /* device time of the next-runs stage of the last cpecan_realigner_reanchor (the slowest shard's) */
 };
 
 void cpecan_realign_options_default(cpecan_realign_options *o) {
@@ -612,8 +613,8 @@ static void item_clear(Item *it) {
     memset(it, 0, sizeof *it);
 }
 
-/* cPecanRealign.c:511-529: sub-sequences on the forward strand from 0, anchors from the cigar's operations */
-static int item_prepare(const cpecan_realigner *r, const cpecan_cigar *pA, Item *it) {
+/* cPecanRealign.c:511-524: the sub-sequences on the forward strand from 0 */
+static int item_sequences(const cpecan_realigner *r, const cpecan_cigar *pA, Item *it) {
     memset(it, 0, sizeof *it);
     if (!pA->contig1 || !pA->contig2 || !cigar_consistent(pA)) {
         cpk_set_error("inconsistent pairwise alignment");
@@ -636,6 +637,13 @@ static int item_prepare(const cpecan_realigner *r, const cpecan_cigar *pA, Item 
     }
     it->lX = (int64_t)strlen(it->subX);
     it->lY = (int64_t)strlen(it->subY);
+    return CPECAN_OK;
+}
+
+/* cPecanRealign.c:511-529: the sub-sequences, and the anchors from the cigar's operations */
+static int item_prepare(const cpecan_realigner *r, const cpecan_cigar *pA, Item *it) {
+    const int rcSeq = item_sequences(r, pA, it);
+    if (rcSeq != CPECAN_OK) return rcSeq;
     int64_t matches = 0;
     for (int64_t i = 0; i < pA->nOps; i++)
         if (pA->ops[2 * i] == CPECAN_OP_MATCH) matches += pA->ops[2 * i + 1];
@@ -749,32 +757,43 @@ static int run_batch(cpecan_batch *b) {
 
 /* cPecanRealign.c:511-529 for every cigar, in parallel (the cigars are independent).  An error message belongs to the
  * thread that set it, so the first failing cigar is prepared once more on the calling thread. */
-static int prepare_range(const cpecan_realigner *r, const cpecan_cigar *in, int64_t from, int64_t to, Item *items) {
+/* Anchors that do not come from the cigars' operations (cpecan_expect_set_create_runs): cigar i takes the
+ * offsets[i + 1] - offsets[i] quadruples at vals + 4 * offsets[i]; vals NULL: the cigars' own. */
+typedef struct {
+    const int64_t *vals, *offsets;
+} GivenRuns;
+
+static int prepare_range(const cpecan_realigner *r, const cpecan_cigar *in, int64_t from, int64_t to, Item *items, int seqOnly) {
     int64_t firstBad = to;
 #pragma omp parallel for schedule(dynamic, 16) num_threads(cpk_host_threads())
     for (int64_t i = from; i < to; i++)
-        if (item_prepare(r, &in[i], &items[i]) != CPECAN_OK) {
+        if ((seqOnly ? item_sequences(r, &in[i], &items[i]) : item_prepare(r, &in[i], &items[i])) != CPECAN_OK) {
 #pragma omp critical(cpk_realign)
             if (i < firstBad) firstBad = i;
         }
     if (firstBad == to) return CPECAN_OK;
     item_clear(&items[firstBad]);
-    const int rc = item_prepare(r, &in[firstBad], &items[firstBad]);
+    const int rc = seqOnly ? item_sequences(r, &in[firstBad], &items[firstBad]) : item_prepare(r, &in[firstBad], &items[firstBad]);
     return rc != CPECAN_OK ? rc : CPECAN_ESTATE;
 }
 
 /* Prepares the cigars a slice at a time and adds each slice to the batch (both ends ragged, :537); the anchor lists of a
  * slice are released as soon as the batch holds them, so the next slice reuses their memory. */
-static int prepare_and_add(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, Item *items, cpecan_batch *b) {
+static int prepare_and_add_runs(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, Item *items, cpecan_batch *b,
+                                GivenRuns given) {
     const int64_t slice = 4096;
     for (int64_t from = 0; from < n; from += slice) {
         const int64_t to = from + slice < n ? from + slice : n;
-        int rc = prepare_range(r, in, from, to, items);
+        int rc = prepare_range(r, in, from, to, items, given.vals != NULL);
         cpecan_problem_runs *probs = rc == CPECAN_OK ? malloc(sizeof(cpecan_problem_runs) * (size_t)(to - from)) : NULL;
         if (rc == CPECAN_OK && !probs) rc = CPECAN_ENOMEM;
         for (int64_t i = from; rc == CPECAN_OK && i < to; i++) {
-            const cpecan_problem_runs p = {items[i].subX, items[i].lX, items[i].subY, items[i].lY, items[i].filtered,
-                                           items[i].nFiltered, 1, 1};
+            cpecan_problem_runs p = {items[i].subX, items[i].lX, items[i].subY, items[i].lY, items[i].filtered,
+                                     items[i].nFiltered, 1, 1};
+            if (given.vals) {
+                p.runs = given.vals + 4 * given.offsets[i];
+                p.nRuns = given.offsets[i + 1] - given.offsets[i];
+            }
             probs[i - from] = p;
         }
         if (rc == CPECAN_OK) {
@@ -789,6 +808,11 @@ static int prepare_and_add(const cpecan_realigner *r, const cpecan_cigar *in, in
         if (rc != CPECAN_OK) return rc;
     }
     return CPECAN_OK;
+}
+
+static int prepare_and_add(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, Item *items, cpecan_batch *b) {
+    const GivenRuns none = {NULL, NULL};
+    return prepare_and_add_runs(r, in, n, items, b, none);
 }
 
 /* The list a cigar is rebuilt from, and its four scores: the ordered alignment with the scores of the batch's consumer
@@ -954,6 +978,51 @@ static int realign_batch(const cpecan_realigner *r, const cpecan_cigar *in, int6
     cpecan_batch_destroy(b);
     for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
     free(items);
+    return rc;
+}
+
+/* The realign batch of realign_batch with the next-runs stage on (cpecan_batch_set_next_runs): no cigar is built, the
+ * ordered alignments leave the device as the exact-match anchor runs of the cigars realign_batch would have returned, in
+ * the coordinates of the cigars' sub-sequences.  vals: malloc'd, the quadruples of all n cigars one after the other;
+ * counts[i]: the runs of cigar i.  stageMs (may be NULL): the stage's device time. */
+static int reanchor_on_device(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, GivenRuns given, int64_t **vals,
+                              int64_t *counts, double *stageMs) {
+    const cpecan_realign_options *o = &r->opt;
+    *vals = NULL;
+    Item *items = calloc((size_t)(n ? n : 1), sizeof(Item));
+    cpecan_batch *b = NULL;
+    int rc = items ? CPECAN_OK : CPECAN_ENOMEM;
+    if (rc == CPECAN_OK) rc = cpecan_batch_create(&b, &r->model, &o->params, CPECAN_EMIT_MATCH, r->device);
+    if (rc == CPECAN_OK) rc = cpecan_batch_set_post(b, CPECAN_POST_REWEIGHT | CPECAN_POST_ORDERED, (double)o->gapGamma);
+    if (rc == CPECAN_OK) rc = cpecan_batch_set_match_gamma(b, o->matchGamma);
+    if (rc == CPECAN_OK) rc = cpecan_batch_set_next_runs(b, o->constraintDiagonalTrim, o->params.diagonalExpansion);
+    if (rc == CPECAN_OK) rc = prepare_and_add_runs(r, in, n, items, b, given);
+    if (rc == CPECAN_OK && n > 0) rc = run_batch(b);
+    int64_t total = 0;
+    for (int64_t i = 0; rc == CPECAN_OK && n > 0 && i < n; i++) {
+        const int64_t *q;
+        rc = cpecan_batch_next_runs(b, i, &q, &counts[i]);
+        total += rc == CPECAN_OK ? counts[i] : 0;
+    }
+    if (rc == CPECAN_OK) {
+        *vals = malloc(sizeof(int64_t) * 4 * (size_t)(total ? total : 1));
+        if (!*vals) rc = CPECAN_ENOMEM;
+    }
+    for (int64_t i = 0, at = 0; rc == CPECAN_OK && n > 0 && i < n; i++) {
+        const int64_t *q;
+        int64_t m;
+        rc = cpecan_batch_next_runs(b, i, &q, &m);
+        if (rc == CPECAN_OK && m > 0) memcpy(*vals + 4 * at, q, sizeof(int64_t) * 4 * (size_t)m);
+        at += m;
+    }
+    if (stageMs) *stageMs = cpk_batch_next_runs_ms(b);
+    cpecan_batch_destroy(b);
+    for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
+    free(items);
+    if (rc != CPECAN_OK) {
+        free(*vals);
+        *vals = NULL;
+    }
     return rc;
 }
 
@@ -1127,9 +1196,12 @@ typedef struct {
     cpecan_realigner shard; /* a shallow copy bound to one device: the sequences are shared, read only */
     const cpecan_cigar *in;
     int64_t n;
-    int expect;
+    int expect;  /* 0: realign, 1: expectations, 2: reanchor */
     int threads;
     int32_t *rounds; /* the shard's part of the realigner's lastRounds */
+    int64_t *runVals, *runCounts; /* reanchor: the shard's quadruples (malloc'd) and its part of the call's counts */
+    GivenRuns given;              /* reanchor: the shard's anchors, when they are not the cigars' own */
+    double stageMs;
     cpecan_cigar *out;
     int64_t nOut;
     cpecan_hmm acc;
@@ -1140,8 +1212,9 @@ typedef struct {
 static void *shard_main(void *arg) {
     ShardJob *j = arg;
     omp_set_num_threads(j->threads); /* this thread's parallel loops: its share of the host's cores */
-    j->rc = j->expect ? expectations_on_device(&j->shard, j->in, j->n, &j->acc)
-                      : realign_on_device(&j->shard, j->in, j->n, &j->out, &j->nOut, j->rounds);
+    j->rc = j->expect == 2 ? reanchor_on_device(&j->shard, j->in, j->n, j->given, &j->runVals, j->runCounts, &j->stageMs)
+            : j->expect  ? expectations_on_device(&j->shard, j->in, j->n, &j->acc)
+                         : realign_on_device(&j->shard, j->in, j->n, &j->out, &j->nOut, j->rounds);
     if (j->rc != CPECAN_OK) {
         strncpy(j->err, cpk_last_error(), sizeof j->err - 1);
         j->err[sizeof j->err - 1] = 0;
@@ -1150,7 +1223,8 @@ static void *shard_main(void *arg) {
 }
 
 /* runs the shards of a call on their devices; jobs[k].out / .acc hold the results */
-static int run_shards(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int expect, int32_t hmmType, ShardJob *jobs) {
+static int run_shards(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int expect, int32_t hmmType, ShardJob *jobs,
+                      int64_t *runCounts, GivenRuns given) {
     const int K = r->nDevices;
     int64_t bounds[CPK_REALIGN_MAX_DEVICES + 1];
     int rc = cpecan_realign_shard_bounds(in, n, r->opt.params.diagonalExpansion, K, bounds);
@@ -1172,7 +1246,10 @@ static int run_shards(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, in
         j->rounds = !expect && r->lastRounds ? r->lastRounds + bounds[k] : NULL; /* every shard adapts on its own */
         j->expect = expect;
         j->threads = threads;
-        if (expect && (rc = cpecan_hmm_init(&j->acc, hmmType, 0.0)) != CPECAN_OK) break;
+        j->runCounts = runCounts ? runCounts + bounds[k] : NULL;
+        j->given = given;
+        if (given.vals) j->given.offsets += bounds[k]; /* (the offsets stay those of the whole call: they index vals) */
+        if (expect == 1 && (rc = cpecan_hmm_init(&j->acc, hmmType, 0.0)) != CPECAN_OK) break;
         if (pthread_create(&tid[k], NULL, shard_main, j) != 0) {
             cpk_set_error("cannot start the thread of shard %d", k);
             rc = CPECAN_ENOMEM;
@@ -1191,6 +1268,8 @@ static int run_shards(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, in
             cpecan_cigars_free(jobs[k].out, jobs[k].nOut);
             jobs[k].out = NULL;
             jobs[k].nOut = 0;
+            free(jobs[k].runVals);
+            jobs[k].runVals = NULL;
         }
     return rc;
 }
@@ -1207,7 +1286,8 @@ int cpecan_realigner_realign(cpecan_realigner *r, const cpecan_cigar *in, int64_
     *nOut = 0;
     ShardJob *jobs = malloc(sizeof(ShardJob) * (size_t)r->nDevices);
     if (!jobs) return CPECAN_ENOMEM;
-    int rc = run_shards(r, in, n, 0, 0, jobs);
+    const GivenRuns none = {NULL, NULL};
+    int rc = run_shards(r, in, n, 0, 0, jobs, NULL, none);
     if (rc == CPECAN_OK) {
         int64_t total = 0;
         for (int k = 0; k < r->nDevices; k++) total += jobs[k].nOut;
@@ -1258,12 +1338,13 @@ void cpecan_expect_set_destroy(cpecan_expect_set *s) {
     free(s);
 }
 
-static int expect_shard_create(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int device, cpecan_batch **out) {
+static int expect_shard_create(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int device, GivenRuns given,
+                               cpecan_batch **out) {
     cpecan_batch *b = NULL;
     int rc = cpecan_batch_create(&b, &r->model, &r->opt.params, CPECAN_EMIT_EXPECT, device);
     Item *items = rc == CPECAN_OK ? calloc((size_t)n, sizeof(Item)) : NULL;
     if (rc == CPECAN_OK && !items) rc = CPECAN_ENOMEM;
-    if (rc == CPECAN_OK) rc = prepare_and_add(r, in, n, items, b);
+    if (rc == CPECAN_OK) rc = prepare_and_add_runs(r, in, n, items, b, given);
     for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
     free(items);
     if (rc == CPECAN_OK && r->expectModelSlots > 0) rc = cpecan_batch_reserve_models(b, r->expectModelSlots);
@@ -1285,8 +1366,7 @@ static int expect_shard_create(const cpecan_realigner *r, const cpecan_cigar *in
     return CPECAN_OK;
 }
 
-int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n) {
-    if (!out || !r || (!in && n > 0) || n < 0) return CPECAN_EINVAL;
+static int expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n, GivenRuns given) {
     *out = NULL;
     cpecan_expect_set *s = calloc(1, sizeof *s);
     if (!s) return CPECAN_ENOMEM;
@@ -1297,8 +1377,11 @@ int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const
     int rc = cpecan_realign_shard_bounds(in, n, r->opt.params.diagonalExpansion, s->nShards, bounds);
     for (int k = 0; rc == CPECAN_OK && k < s->nShards; k++) {
         s->devices[k] = r->nDevices > 1 ? r->devices[k] : r->device;
-        if (bounds[k + 1] > bounds[k])
-            rc = expect_shard_create(r, in + bounds[k], bounds[k + 1] - bounds[k], s->devices[k], &s->batches[k]);
+        if (bounds[k + 1] > bounds[k]) {
+            GivenRuns part = given;
+            if (part.vals) part.offsets += bounds[k]; /* (the offsets stay those of the whole call: they index vals) */
+            rc = expect_shard_create(r, in + bounds[k], bounds[k + 1] - bounds[k], s->devices[k], part, &s->batches[k]);
+        }
     }
     if (rc != CPECAN_OK) {
         cpecan_expect_set_destroy(s);
@@ -1306,6 +1389,143 @@ int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const
     }
     *out = s;
     return CPECAN_OK;
+}
+
+int cpecan_expect_set_create(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n) {
+    if (!out || !r || (!in && n > 0) || n < 0) return CPECAN_EINVAL;
+    const GivenRuns none = {NULL, NULL};
+    return expect_set_create(out, r, in, n, none);
+}
+
+/* nRuns per cigar -> offsets (malloc'd) of a GivenRuns; NULL: bad counts or no memory (*rc says which) */
+static int64_t *given_offsets(const int64_t *runs, const int64_t *nRuns, int64_t n, int *rc) {
+    int64_t *offsets = malloc(sizeof(int64_t) * (size_t)(n + 1));
+    *rc = offsets ? CPECAN_OK : CPECAN_ENOMEM;
+    if (!offsets) return NULL;
+    offsets[0] = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (nRuns[i] < 0) *rc = CPECAN_EINVAL;
+        offsets[i + 1] = offsets[i] + (nRuns[i] > 0 ? nRuns[i] : 0);
+    }
+    if (offsets[n] > 0 && !runs) *rc = CPECAN_EINVAL;
+    if (*rc != CPECAN_OK) {
+        free(offsets);
+        return NULL;
+    }
+    return offsets;
+}
+
+int cpecan_expect_set_create_runs(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n,
+                                  const int64_t *runs, const int64_t *nRuns) {
+    if (!out || !r || (!in && n > 0) || n < 0 || (n > 0 && !nRuns)) return CPECAN_EINVAL;
+    int rcOff = CPECAN_OK;
+    int64_t *offsets = given_offsets(runs, nRuns, n, &rcOff);
+    if (!offsets) return rcOff;
+    static const int64_t nothing[4] = {0, 0, 0, 0}; /* (a call without a run still says that the anchors are given) */
+    const GivenRuns given = {runs ? runs : nothing, offsets};
+    const int rc = expect_set_create(out, r, in, n, given);
+    free(offsets);
+    return rc;
+}
+
+int cpecan_realigner_set_model(cpecan_realigner *r, const cpecan_model *model) {
+    if (!r || !model) return CPECAN_EINVAL;
+    cpecan_model probe;
+    if (cpecan_model_default(&probe, model->type) != CPECAN_OK) {
+        cpk_set_error("unknown model type %d", model->type);
+        return CPECAN_EINVAL;
+    }
+    r->model = *model;
+    return CPECAN_OK;
+}
+
+int cpecan_realigner_reanchor(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int64_t **runs, int64_t **nRuns) {
+    return cpecan_realigner_reanchor_runs(r, in, n, NULL, NULL, runs, nRuns);
+}
+
+int cpecan_realigner_reanchor_runs(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, const int64_t *runsIn,
+                                   const int64_t *nRunsIn, int64_t **runs, int64_t **nRuns) {
+    if (!r || (!in && n > 0) || n < 0 || !runs || !nRuns) return CPECAN_EINVAL;
+    if (r->opt.rescoreOriginalAlignment || r->opt.splitIndelsLongerThanThis != -1) {
+        cpk_set_error("reanchor: rescoreOriginalAlignment and splitIndelsLongerThanThis change the cigars the realignment returns, "
+                      "and the anchors are made without them");
+        return CPECAN_EINVAL;
+    }
+    *runs = *nRuns = NULL;
+    int rc = CPECAN_OK;
+    static const int64_t nothing[4] = {0, 0, 0, 0};
+    GivenRuns given = {NULL, NULL};
+    int64_t *offsets = NULL;
+    if (nRunsIn) { /* the anchors are the caller's: those of an earlier call, as a rule */
+        offsets = given_offsets(runsIn, nRunsIn, n, &rc);
+        if (!offsets) return rc;
+        given.vals = runsIn ? runsIn : nothing;
+        given.offsets = offsets;
+    }
+    *nRuns = calloc((size_t)(n ? n : 1), sizeof(int64_t));
+    if (!*nRuns) {
+        free(offsets);
+        return CPECAN_ENOMEM;
+    }
+    r->lastReanchorMs = 0.0;
+    if (r->nDevices <= 1 || n < 2) {
+        rc = reanchor_on_device(r, in, n, given, runs, *nRuns, &r->lastReanchorMs);
+    } else {
+        ShardJob *jobs = malloc(sizeof(ShardJob) * (size_t)r->nDevices);
+        rc = jobs ? run_shards(r, in, n, 2, 0, jobs, *nRuns, given) : CPECAN_ENOMEM;
+        if (rc == CPECAN_OK) { /* shard order is input order */
+            int64_t total = 0;
+            for (int64_t i = 0; i < n; i++) total += (*nRuns)[i];
+            *runs = malloc(sizeof(int64_t) * 4 * (size_t)(total ? total : 1));
+            if (!*runs) rc = CPECAN_ENOMEM;
+            int64_t at = 0, cigar = 0;
+            for (int k = 0; k < r->nDevices; k++) {
+                int64_t m = 0;
+                for (int64_t i = 0; i < jobs[k].n; i++) m += (*nRuns)[cigar + i];
+                cigar += jobs[k].n;
+                if (rc == CPECAN_OK && m > 0) memcpy(*runs + 4 * at, jobs[k].runVals, sizeof(int64_t) * 4 * (size_t)m);
+                at += m;
+                free(jobs[k].runVals);
+                if (jobs[k].stageMs > r->lastReanchorMs) r->lastReanchorMs = jobs[k].stageMs;
+            }
+        }
+        free(jobs);
+    }
+    free(offsets);
+    if (rc != CPECAN_OK) {
+        free(*runs);
+        free(*nRuns);
+        *runs = *nRuns = NULL;
+    }
+    return rc;
+}
+
+double cpk_realigner_reanchor_ms(const cpecan_realigner *r) { return r ? r->lastReanchorMs : 0.0; }
+
+int cpk_realigner_cigar_runs(const cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int64_t **runs, int64_t **nRuns) {
+    *runs = *nRuns = NULL;
+    Item *items = calloc((size_t)(n ? n : 1), sizeof(Item));
+    int rc = items ? prepare_range(r, in, 0, n, items, 0) : CPECAN_ENOMEM;
+    int64_t total = 0;
+    for (int64_t i = 0; rc == CPECAN_OK && i < n; i++) total += items[i].nFiltered;
+    if (rc == CPECAN_OK) {
+        *runs = malloc(sizeof(int64_t) * 4 * (size_t)(total ? total : 1));
+        *nRuns = calloc((size_t)(n ? n : 1), sizeof(int64_t));
+        if (!*runs || !*nRuns) rc = CPECAN_ENOMEM;
+    }
+    for (int64_t i = 0, at = 0; rc == CPECAN_OK && i < n; i++) {
+        (*nRuns)[i] = items[i].nFiltered;
+        if (items[i].nFiltered > 0) memcpy(*runs + 4 * at, items[i].filtered, sizeof(int64_t) * 4 * (size_t)items[i].nFiltered);
+        at += items[i].nFiltered;
+    }
+    for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
+    free(items);
+    if (rc != CPECAN_OK) {
+        free(*runs);
+        free(*nRuns);
+        *runs = *nRuns = NULL;
+    }
+    return rc;
 }
 
 int cpecan_expect_set_run(cpecan_expect_set *s, const cpecan_model *m, cpecan_hmm *acc) {
@@ -1364,7 +1584,8 @@ int cpecan_realigner_expectations(cpecan_realigner *r, const cpecan_cigar *in, i
     if (r->nDevices <= 1 || n < 2) return expectations_on_device(r, in, n, acc);
     ShardJob *jobs = malloc(sizeof(ShardJob) * (size_t)r->nDevices);
     if (!jobs) return CPECAN_ENOMEM;
-    int rc = run_shards(r, in, n, 1, acc->type, jobs);
+    const GivenRuns none = {NULL, NULL};
+    int rc = run_shards(r, in, n, 1, acc->type, jobs, NULL, none);
     for (int k = 0; rc == CPECAN_OK && k < r->nDevices; k++) { /* the sum of cPecanEm.py:184-188, in shard order */
         for (int i = 0; i < 25; i++) acc->transitions[i] += jobs[k].acc.transitions[i];
         for (int i = 0; i < 80; i++) acc->emissions[i] += jobs[k].acc.emissions[i];

@@ -919,6 +919,103 @@ __global__ void __launch_bounds__(256) cpecan_post_quintuples(const CpkPostProbl
     }
 }
 
+// The hand-off of the trainer's --updateTheBand (include/cpecan_realign.h, cpecan_batch_set_next_runs; DESIGN.md section
+// 11): the ordered alignment of every problem becomes the exact-match anchor runs of the cigar that
+// convertAlignedPairsToPairwiseAlignment (cPecanRealign.c:50-92) would make of it, without the cigar.  Runs behind ORDERED,
+// on result list 3 as it lies on the device -- reverse input order, which is not sorted --, one WAVE per problem:
+//  0. the chain increases strictly in x, so column x of X holds at most one pair: y goes to yOf[x] (-1: none), and from
+//     here on the lanes run over the columns of X, 64 at a time, in ascending order whatever the list's was;
+//  1. a column BREAKS the block when it is empty or its left neighbour does not hold (x - 1, y - 1).  ds[x], the distance of
+//     column x to the first column of its block (-1: empty), is the lane minus the last break at or below it in the
+//     chunk's ballot mask, or the carry of the chunk before plus lane + 1 when the mask has none;
+//  2. column x is KEPT iff ds[x] >= trim, ds[x + trim] >= trim -- column x + trim lies in a block that began at or before
+//     x, that is in x's block: the distance to the block's last column is at least trim -- and the two letters are equal and
+//     not N (chars are upper case).  A kept column CONTINUES a run iff its left neighbour is kept and ds[x] > 0; the
+//     ballot masks of run starts and run ends give every end lane the start of its run (the last start bit at or below it,
+//     or the carry) and its place among the problem's runs (ends below it plus the carry), and it stores the run
+//     (x, y, length, expansion) as one 16-byte vector store at that place.
+// The problem's runs start at 4 * meaOut words: the list-0 lengths of the problems in front bound their pairs, and a run
+// holds at least one pair.  No atomics, no LDS; lane 0 stores the count.
+__global__ void __launch_bounds__(64) cpecan_post_next_runs(const CpkPostProblem *problems, const int32_t *ordered,
+                                                            const int32_t *counts, const uint8_t *chars, int32_t *scratch,
+                                                            int trim, int expansion, int4 *runs, int32_t *runCounts) {
+    const int lane = threadIdx.x;
+    const CpkPostProblem pb = problems[blockIdx.x];
+    const int32_t *list = ordered + 3 * pb.meaOut;
+    const int n = counts[2 * blockIdx.x], lX = pb.lX, lY = pb.lY;
+    int32_t *yOf = scratch + pb.nextOff, *ds = yOf + lX;
+    const uint8_t *sX = chars + pb.charX, *sY = chars + pb.charY;
+    int4 *out = runs + pb.meaOut;
+    const unsigned long long upTo = lane == CPK_WAVE - 1 ? ~0ull : (2ull << lane) - 1;  // bits 0 .. lane
+    for (int x = lane; x < lX; x += CPK_WAVE) yOf[x] = -1;
+    __syncthreads();
+    for (int i = lane; i < n; i += CPK_WAVE) {
+        const int x = list[3 * i + 1], y = list[3 * i + 2];
+        if (x >= 0 && x < lX && y >= 0 && y < lY) yOf[x] = y;  // (always, for a list the ordered filter wrote)
+    }
+    __syncthreads();
+    int carryY = -1, carryDs = -1;
+    for (int x0 = 0; x0 < lX; x0 += CPK_WAVE) {
+        const int x = x0 + lane;
+        const int y = x < lX ? yOf[x] : -1;
+        int yPrev = __shfl_up(y, 1);
+        if (lane == 0) yPrev = carryY;
+        const bool brk = y < 0 || !(yPrev >= 0 && yPrev + 1 == y);
+        const unsigned long long below = __ballot(brk) & upTo;
+        int d = -1;
+        if (y >= 0) d = below ? lane - (63 - __builtin_clzll(below)) : carryDs + lane + 1;
+        if (x < lX) ds[x] = d;
+        carryY = __shfl(y, CPK_WAVE - 1);
+        carryDs = __shfl(d, CPK_WAVE - 1);
+    }
+    __syncthreads();
+    auto kept = [&](int x) {
+        if (x >= lX || trim >= lX - x) return false;
+        if (ds[x] < trim || ds[x + trim] < trim) return false;
+        const uint8_t a = sX[x], b = sY[yOf[x]];
+        return a == b && a != 'N';
+    };
+    int count = 0, carryStart = 0;
+    bool carryKept = false;
+    for (int x0 = 0; x0 < lX; x0 += CPK_WAVE) {
+        const int x = x0 + lane;
+        const bool k = kept(x);
+        const int d = x < lX ? ds[x] : -1;
+        bool kPrev = __shfl_up((int)k, 1) != 0;
+        if (lane == 0) kPrev = carryKept;
+        bool kNext = __shfl_down((int)k, 1) != 0;
+        int dNext = __shfl_down(d, 1);
+        if (lane == CPK_WAVE - 1) {
+            kNext = kept(x + 1);
+            dNext = x + 1 < lX ? ds[x + 1] : -1;
+        }
+        const bool start = k && !(kPrev && d > 0), end = k && !(kNext && dNext > 0);
+        const unsigned long long startMask = __ballot(start), endMask = __ballot(end);
+        if (end) {
+            const unsigned long long sBelow = startMask & upTo;
+            const int sx = sBelow ? x0 + 63 - __builtin_clzll(sBelow) : carryStart;
+            const int len = x - sx + 1;
+            const int at = count + __popcll(endMask & (upTo >> 1));
+            out[at] = make_int4(sx, yOf[x] - (len - 1), len, expansion);
+        }
+        count += __popcll(endMask);
+        if (startMask) carryStart = x0 + 63 - __builtin_clzll(startMask);
+        carryKept = __shfl((int)k, CPK_WAVE - 1) != 0;
+    }
+    if (lane == 0) runCounts[blockIdx.x] = count;
+}
+
+// The runs of cpecan_post_next_runs, which lie at the problems' upper-bound offsets, moved to where the host's prefix sums of
+// the downloaded counts put them: only runs cross PCIe.  One wave per problem.
+__global__ void __launch_bounds__(64) cpecan_post_pack_runs(const CpkPostProblem *problems, const int4 *runs,
+                                                            const int32_t *runCounts, const int64_t *packedOff, int4 *packed) {
+    const CpkPostProblem pb = problems[blockIdx.x];
+    const int4 *src = runs + pb.meaOut;
+    int4 *dst = packed + packedOff[blockIdx.x];
+    const int n = runCounts[blockIdx.x];
+    for (int i = threadIdx.x; i < n; i += CPK_WAVE) dst[i] = src[i];
+}
+
 // ------------------------------------------------------------------------------------------------
 // Posterior mass on the band's edge (cpecan_band_edge_of_pairs is the host's statement of it).
 // Runs on the compact buffer behind cpecan_gather_lists and in front of every consumer, so the scores are the sweep's.

@@ -15,7 +15,7 @@ EXPORTS = [
     "cpecan_em_write_lastz_matrix", "cpecan_em_fasta_gc", "cpecan_em_write_model", "cpecan_em_trainer_create",
     "cpecan_em_trainer_destroy", "cpecan_em_trainer_read_fasta", "cpecan_em_trainer_add_sequence",
     "cpecan_em_trainer_set_devices", "cpecan_em_train", "cpecan_em_trainer_timing",
-    "cpecan_em_trainer_set_concurrent_trials",
+    "cpecan_em_trainer_set_concurrent_trials", "cpecan_em_trainer_alignments",
 ]
 
 MODEL_TYPES = {"fiveState": api.fiveState, "fiveStateAsymmetric": api.fiveStateAsymmetric,
@@ -28,12 +28,14 @@ class EmOptions(C.Structure):
                 ("useDefaultModelAsStart", C.c_int32), ("trainEmissions", C.c_int32), ("tieEmissions", C.c_int32),
                 ("outputTrialHmms", C.c_int32), ("setJukesCantorStartingEmissions", C.c_double),
                 ("maxAlignmentLengthPerJob", C.c_int64), ("maxAlignmentLengthToSample", C.c_int64),
-                ("seed", C.c_uint64), ("inputModel", C.c_char_p), ("blastScoringMatrixFile", C.c_char_p)]
+                ("seed", C.c_uint64), ("inputModel", C.c_char_p), ("blastScoringMatrixFile", C.c_char_p),
+                ("updateTheBand", C.c_int32)]
 
 
 class EmTiming(C.Structure):
     _fields_ = [("setupMs", C.c_double), ("iterationsMs", C.c_double), ("iterations", C.c_int64),
-                ("cigars", C.c_int64), ("jobs", C.c_int64)]
+                ("cigars", C.c_int64), ("jobs", C.c_int64), ("realignMs", C.c_double), ("replanMs", C.c_double),
+                ("handoffMs", C.c_double)]
 
 
 _bound = False
@@ -71,6 +73,7 @@ def _lib():
         L.cpecan_em_trainer_set_concurrent_trials.argtypes = [vp, C.c_int]
         L.cpecan_em_train.argtypes = [vp, C.POINTER(realign._Cigar), C.c_int64, C.c_char_p, hp, dp]
         L.cpecan_em_trainer_timing.argtypes = [vp, C.POINTER(EmTiming)]
+        L.cpecan_em_trainer_alignments.argtypes = [vp, C.POINTER(i64p), C.POINTER(i64p), i64p]
         _bound = True
     return L
 
@@ -218,6 +221,20 @@ class Trainer:
         api._check(_lib().cpecan_em_train(self._h, arr, len(cigars), _b(output_model), C.byref(best), running),
                    "cpecan_em_train")
         return best, list(running[:self.options.iterations])
+
+    def alignments(self):
+        """cpecan_em_trainer_alignments: per sampled cigar the anchor runs (x, y, length, expansion) the last E-step of the
+        last trial of an updateTheBand training ran on, as int64 arrays of shape (k, 4)."""
+        import numpy as np
+        runs, counts, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)(), C.c_int64()
+        api._check(_lib().cpecan_em_trainer_alignments(self._h, C.byref(runs), C.byref(counts), C.byref(n)),
+                   "cpecan_em_trainer_alignments")
+        out, at = [], 0
+        for i in range(n.value):
+            k = counts[i]
+            out.append(np.array(runs[4 * at:4 * (at + k)], dtype=np.int64).reshape(k, 4))
+            at += k
+        return out
 
     def timing(self):
         t = EmTiming()

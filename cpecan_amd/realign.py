@@ -4,6 +4,8 @@ Cigars are plain Python objects here (`Cigar`); text parsing, formatting and the
 """
 import ctypes as C
 
+import numpy as np
+
 from . import api
 
 # Every symbol include/cpecan_realign.h declares (checked by tests/test_abi.py).
@@ -17,7 +19,12 @@ EXPORTS = [
     "cpecan_expect_set_create", "cpecan_expect_set_run", "cpecan_expect_set_shards", "cpecan_expect_set_stats",
     "cpecan_expect_set_destroy", "cpecan_expect_set_reserve_models", "cpecan_expect_set_run_models",
     "cpecan_realigner_set_adaptive_band", "cpecan_realigner_adaptive_rounds",
+    "cpecan_batch_set_next_runs", "cpecan_batch_next_runs", "cpecan_next_runs_of_pairs",
+    "cpecan_realigner_set_model", "cpecan_realigner_reanchor", "cpecan_realigner_reanchor_runs",
+    "cpecan_expect_set_create_runs",
 ]
+
+NEXT_RUNS_OFF = -1  # CPECAN_NEXT_RUNS_OFF
 
 
 class _Cigar(C.Structure):
@@ -72,6 +79,21 @@ def _lib():
         L.cpecan_realign_shard_bounds.argtypes = [C.POINTER(_Cigar), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
         L.cpecan_realigner_set_adaptive_band.argtypes = [vp, C.c_int, C.c_int64]
         L.cpecan_realigner_adaptive_rounds.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64]
+        i64p = C.POINTER(C.c_int64)
+        L.cpecan_batch_set_next_runs.argtypes = [vp, C.c_int64, C.c_int64]
+        L.cpecan_batch_next_runs.argtypes = [vp, C.c_int64, C.POINTER(i64p), i64p]
+        L.cpecan_next_runs_of_pairs.argtypes = [C.POINTER(C.c_int32), C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64,
+                                                C.c_int64, C.c_int64, i64p, C.c_int64]
+        L.cpecan_next_runs_of_pairs.restype = C.c_int64
+        L.cpecan_realigner_set_model.argtypes = [vp, C.POINTER(api.StateMachine)]
+        L.cpecan_realigner_reanchor.argtypes = [vp, C.POINTER(_Cigar), C.c_int64, C.POINTER(i64p), C.POINTER(i64p)]
+        L.cpecan_realigner_reanchor_runs.argtypes = [vp, C.POINTER(_Cigar), C.c_int64, i64p, i64p, C.POINTER(i64p),
+                                                     C.POINTER(i64p)]
+        L.cpecan_expect_set_create.argtypes = [C.POINTER(vp), vp, C.POINTER(_Cigar), C.c_int64]
+        L.cpecan_expect_set_create_runs.argtypes = [C.POINTER(vp), vp, C.POINTER(_Cigar), C.c_int64, i64p, i64p]
+        L.cpecan_expect_set_run.argtypes = [vp, C.POINTER(api.StateMachine), C.POINTER(api.Hmm)]
+        L.cpecan_expect_set_destroy.argtypes = [vp]
+        L.cpecan_expect_set_destroy.restype = None
         _bound = True
     return L
 
@@ -244,6 +266,82 @@ class Realigner:
         api._check(_lib().cpecan_realigner_expectations(self._h, arr, len(cigars), C.byref(hmm)),
                    "cpecan_realigner_expectations")
         return hmm
+
+    def set_model(self, sM):
+        """cpecan_realigner_set_model: the model of every later call."""
+        api._check(_lib().cpecan_realigner_set_model(self._h, C.byref(sM)), "cpecan_realigner_set_model")
+        self._sm = sM
+
+    def reanchor(self, cigars, runs_in=None):
+        """cpecan_realigner_reanchor: per input cigar the exact-match anchor runs (x, y, length, expansion) of the cigar
+        realign() would return for it, in the coordinates of the cigar's sub-sequences, as one int64 array of shape (k, 4)
+        each; no cigar is built and no pair list leaves the device.  runs_in (cpecan_realigner_reanchor_runs): the anchors
+        of the realignment, per cigar, instead of those of the cigars' operations."""
+        arr, keep = self._pack(cigars)
+        runs, counts = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)()
+        if runs_in is None:
+            api._check(_lib().cpecan_realigner_reanchor(self._h, arr, len(cigars), C.byref(runs), C.byref(counts)),
+                       "cpecan_realigner_reanchor")
+        else:
+            n_in = (C.c_int64 * max(1, len(cigars)))(*[len(r) for r in runs_in])
+            flat = [int(v) for r in runs_in for q in r for v in q]
+            vals = (C.c_int64 * max(1, len(flat)))(*flat)
+            api._check(_lib().cpecan_realigner_reanchor_runs(self._h, arr, len(cigars), vals, n_in, C.byref(runs),
+                                                             C.byref(counts)), "cpecan_realigner_reanchor_runs")
+        try:
+            out, at = [], 0
+            for i in range(len(cigars)):
+                k = counts[i]
+                out.append(np.array(runs[4 * at:4 * (at + k)], dtype=np.int64).reshape(k, 4))
+                at += k
+            return out
+        finally:
+            api.lib().cpecan_free(C.cast(runs, C.c_void_p))
+            api.lib().cpecan_free(C.cast(counts, C.c_void_p))
+
+    def expectations_on_runs(self, cigars, runs, hmm):
+        """One E-step on the cigars' sub-sequences with the anchors taken from `runs` (as reanchor() returns them) instead
+        of from the cigars' operations: cpecan_expect_set_create_runs, one cpecan_expect_set_run under the realigner's
+        model, and the set is dropped again."""
+        arr, keep = self._pack(cigars)
+        counts = (C.c_int64 * max(1, len(cigars)))(*[len(r) for r in runs])
+        flat = [int(v) for r in runs for q in r for v in q]
+        vals = (C.c_int64 * max(1, len(flat)))(*flat)
+        s = C.c_void_p()
+        api._check(_lib().cpecan_expect_set_create_runs(C.byref(s), self._h, arr, len(cigars), vals, counts),
+                   "cpecan_expect_set_create_runs")
+        try:
+            api._check(_lib().cpecan_expect_set_run(s, C.byref(self._sm), C.byref(hmm)), "cpecan_expect_set_run")
+        finally:
+            _lib().cpecan_expect_set_destroy(s)
+        return hmm
+
+
+def batch_set_next_runs(batch, trim=0, expansion=0):
+    """cpecan_batch_set_next_runs on an api.Batch with POST_ORDERED, before upload: its downloads return anchor runs
+    (batch_next_runs) instead of pair lists.  expansion NEXT_RUNS_OFF switches the stage off again."""
+    api._check(_lib().cpecan_batch_set_next_runs(batch._h, int(trim), int(expansion)), "cpecan_batch_set_next_runs")
+
+
+def batch_next_runs(batch, problem):
+    """cpecan_batch_next_runs: the runs (x, y, length, expansion) of a problem of the downloaded run, int64, shape (k, 4)."""
+    ptr, n = C.POINTER(C.c_int64)(), C.c_int64()
+    api._check(_lib().cpecan_batch_next_runs(batch._h, int(problem), C.byref(ptr), C.byref(n)), "cpecan_batch_next_runs")
+    return np.array(ptr[:4 * n.value], dtype=np.int64).reshape(n.value, 4)
+
+
+def next_runs_of_pairs(triples, sX, sY, trim=0, expansion=0):
+    """cpecan_next_runs_of_pairs: the definition of the stage on the host; triples: (score, x, y) rows of a chain in any
+    order."""
+    t = np.ascontiguousarray(np.asarray(triples, dtype=np.int32).reshape(-1, 3))
+    sx, sy = api._bytes(sX), api._bytes(sY)
+    tp = t.ctypes.data_as(C.POINTER(C.c_int32))
+    n = api._check(_lib().cpecan_next_runs_of_pairs(tp, t.shape[0], sx, len(sx), sy, len(sy), int(trim), int(expansion), None, 0),
+                   "cpecan_next_runs_of_pairs")
+    out = np.zeros((max(1, n), 4), dtype=np.int64)
+    api._check(_lib().cpecan_next_runs_of_pairs(tp, t.shape[0], sx, len(sx), sy, len(sy), int(trim), int(expansion),
+                                                out.ctypes.data_as(C.POINTER(C.c_int64)), n), "cpecan_next_runs_of_pairs")
+    return out[:n]
 
 
 def shard_bounds(cigars, n_shards, expansion=4):

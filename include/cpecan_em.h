@@ -38,6 +38,8 @@ typedef struct cpecan_em_options {
     uint64_t seed;                          /* drives the shuffle of the jobs and randomise; 0 */
     const char *inputModel;                 /* NULL */
     const char *blastScoringMatrixFile;     /* NULL */
+    int32_t updateTheBand;                  /* 0; 1: after every M-step but the last the sample is realigned under the new
+                                             * model with the realign options, and the next E-step runs on the new anchors */
 } cpecan_em_options;
 void cpecan_em_options_default(cpecan_em_options *o);
 
@@ -86,6 +88,8 @@ int cpecan_em_trainer_set_devices(cpecan_em_trainer *t, const int *devices, int 
  * draws every start model first, in trial order (trial k starts from the model it starts from in a sequential run), and
  * runs the trials in rounds of up to n: an iteration of a round is one cpecan_expect_set_run_models plus the M-step of
  * each trial.  Trial files, outputTrialHmms, the choice of the best trial, running likelihoods and timing are the same. */
+/* With updateTheBand n > 1 is CPECAN_EINVAL with a message, here and in cpecan_em_train, before any device is looked
+ * for: the trials' bands differ, so one resident batch cannot serve them. */
 int cpecan_em_trainer_set_concurrent_trials(cpecan_em_trainer *t, int n);
 /* Samples the cigars, uploads them once and runs every trial's iterations.  Writes outputModel after every iteration
  * (with several trials: the trial's own file, <outputModel>_<i> with outputTrialHmms), then the trial with the highest
@@ -98,8 +102,26 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
 typedef struct cpecan_em_timing {
     double setupMs, iterationsMs;
     int64_t iterations, cigars, jobs;
+    /* updateTheBand, sums over the iterations of every trial and parts of iterationsMs: the realign batches
+     * (cpecan_realigner_reanchor), of which the hand-off stage on the device took handoffMs, and planning and uploading the
+     * new EXPECT sets (cpecan_expect_set_create_runs) */
+    double realignMs, replanMs, handoffMs;
 } cpecan_em_timing;
 int cpecan_em_trainer_timing(const cpecan_em_trainer *t, cpecan_em_timing *out);
+/* updateTheBand (cPecanEm.py:205-215).  A trial is then
+ *     anchors = those of the sampled cigars
+ *     for it in 0 .. iterations - 1:
+ *         E-step on anchors, M-step, model file written
+ *         if it + 1 < iterations: anchors = the sample realigned inside the band of `anchors` under the model of the
+ *                                 M-step (cpecan_realigner_reanchor_runs); a new EXPECT set
+ * The reference also realigns after the last iteration; nothing reads that run, so it is skipped.  Every trial starts again
+ * from the input sample, as the reference re-splits the alignments file per trial.
+ * cpecan_em_trainer_alignments: the anchors the last E-step of the last trial of the last cpecan_em_train with the option
+ * ran on -- *n sampled cigars in sample order (cpecan_em_sample), (*nRuns)[i] quadruples (x, y, length,
+ * expansion) each, one after the other in *runs, in the coordinates of the cigars' sub-sequences.  The trainer's memory,
+ * valid until the next cpecan_em_train or cpecan_em_trainer_destroy; CPECAN_ESTATE when the last training ran without
+ * the option, failed, or never happened. */
+int cpecan_em_trainer_alignments(const cpecan_em_trainer *t, const int64_t **runs, const int64_t **nRuns, int64_t *n);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,31 @@ int cpecan_cigar_from_aligned_pairs_stranded(const char *contig1, const char *co
  * that are cut and any indels at either end are dropped.  *out: malloc'd array of *nOut cigars (cpecan_cigars_free). */
 int cpecan_cigar_split(const cpecan_cigar *c, int64_t maxIndelLength, cpecan_cigar **out, int64_t *nOut);
 
+/* ---- the hand-off from one realignment to the anchors of the next (cPecanEm.py:205-215, --updateTheBand) ----
+ * A batch stage behind CPECAN_POST_ORDERED (cpecan_hip.h), defined for one problem as a pure integer function of result
+ * list 3, the ordered alignment: take its pairs (x, y) sorted ascending -- a chain, both coordinates increase strictly.  A
+ * BLOCK is a maximal run of consecutive pairs in which both coordinates step by one: the match operations
+ * convertAlignedPairsToPairwiseAlignment makes of the chain (cPecanRealign.c:50-92).  Drop `trim` columns at both ends of
+ * every block (convertPairwiseForwardStrandAlignmentToAnchorPairs), keep a column iff its two letters are equal, case-
+ * insensitive, and not N (matchFn, cPecanRealign.c:277-281); kept columns that follow each other inside a block form a run
+ * (x, y, length, expansion).  These are the runs cpecan_anchor_runs_from_alignment gives for the operations of the cigar
+ * cpecan_cigar_from_aligned_pairs builds from the same pairs, integer for integer, ready for cpecan_batch_add_many_runs.
+ *
+ * cpecan_batch_set_next_runs, before upload: downloads of the batch also run the stage, one wave per problem.  Only the runs
+ * and their counts are copied out: the triples of such a batch stay on the device, cpecan_batch_result refuses it, the
+ * scores remain.  CPECAN_EINVAL without CPECAN_POST_ORDERED, for a negative trim or expansion, or after upload; a later
+ * cpecan_batch_set_post without CPECAN_POST_ORDERED switches the stage off with the list it reads.  expansion
+ * CPECAN_NEXT_RUNS_OFF switches the stage off again: the batch then allocates and launches what it did before.
+ * cpecan_batch_next_runs, after download: the nRuns quadruples of problem i (the batch's memory). */
+#define CPECAN_NEXT_RUNS_OFF (-1)
+int cpecan_batch_set_next_runs(cpecan_batch *b, int64_t trim, int64_t expansion);
+int cpecan_batch_next_runs(const cpecan_batch *b, int64_t problem, const int64_t **runs, int64_t *nRuns);
+/* The same definition on the host, no device needed: n triples (score, x, y) of a chain in any order.  runs receives at most
+ * cap quadruples; returns the number of runs (which may exceed cap), or < 0: CPECAN_EINVAL for a pair outside the
+ * sequences or pairs that are no chain. */
+int64_t cpecan_next_runs_of_pairs(const int32_t *triples, int64_t n, const char *sX, int64_t lX, const char *sY, int64_t lY,
+                                  int64_t trim, int64_t expansion, int64_t *runs, int64_t cap);
+
 /* The options of cPecanRealign's command line with its defaults (cPecanRealign.c:354-370). */
 typedef struct cpecan_realign_options {
     cpecan_params params;           /* diagonalExpansion 4 (-r), splitMatrixBiggerThanThis 10 (-o takes the square root) */
@@ -137,6 +162,27 @@ int cpecan_expect_set_shards(const cpecan_expect_set *s);
 /* Statistics of shard k's batch (launch form, waves, cells, kernel time of the last run); zeros for an empty shard. */
 int cpecan_expect_set_stats(const cpecan_expect_set *s, int shard, cpecan_stats *st);
 void cpecan_expect_set_destroy(cpecan_expect_set *s);
+
+/* ---- realigning the band: the three steps of an --updateTheBand iteration (cPecanEm.py:205-215) ----
+ * cpecan_realigner_set_model: the model of every later call (cpecan_realigner_create's copy is replaced).
+ * cpecan_realigner_reanchor: the batch of cpecan_realigner_realign with the next-runs stage on
+ * (cpecan_batch_set_next_runs with the realigner's constraintDiagonalTrim and diagonalExpansion).  *nRuns: malloc'd, n counts;
+ * *runs: malloc'd, the quadruples of cigar 0, then cigar 1, ... (both cpecan_free) -- per input cigar the exact-match anchor
+ * runs of the cigar cpecan_realigner_realign would return for it, in the coordinates of the cigar's sub-sequences, that is
+ * what cpecan_anchor_runs_from_alignment gives for that cigar's operations from (0, 0).  Refuses rescoreOriginalAlignment
+ * and splitIndelsLongerThanThis != -1 with CPECAN_EINVAL before a device is looked for; the adaptive band does not apply.
+ * With cpecan_realigner_set_devices the shards are joined in input order.
+ * cpecan_realigner_reanchor_runs: the same with the anchors of cigar i taken from its nRunsIn[i] quadruples of runsIn (the
+ * layout _reanchor returns) instead of from the cigar's operations: feeding a call's result to the next one is realigning
+ * the realigned cigars, as cPecanEm.py:212-215 does when it moves the realigned file over the alignments file.
+ * cpecan_expect_set_create_runs: cpecan_expect_set_create with the anchors of cigar i taken from its nRuns[i] quadruples of
+ * `runs` (laid out as _reanchor returns them) instead of from the cigar's operations, which are not read. */
+int cpecan_realigner_set_model(cpecan_realigner *r, const cpecan_model *model);
+int cpecan_realigner_reanchor(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, int64_t **runs, int64_t **nRuns);
+int cpecan_realigner_reanchor_runs(cpecan_realigner *r, const cpecan_cigar *in, int64_t n, const int64_t *runsIn,
+                                   const int64_t *nRunsIn, int64_t **runs, int64_t **nRuns);
+int cpecan_expect_set_create_runs(cpecan_expect_set **out, cpecan_realigner *r, const cpecan_cigar *in, int64_t n,
+                                  const int64_t *runs, const int64_t *nRuns);
 
 #ifdef __cplusplus
 }
