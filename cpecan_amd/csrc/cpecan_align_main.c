@@ -15,6 +15,11 @@
  * (cpecan_band_edge); a pair whose edgeScoreSum reaches S runs again, up to N = 1..4 times, in a batch of the flagged pairs
  * with the expansion of their runs and of the parameters doubled per round.  Anchors are not searched again.  A pair's cigar
  * is that of its last run, and stderr names the round and the expansion every pair ended on.
+ * --local [--maxChains K] [--minChainScore S]: the reference's `lastz | cPecanRealign` pipeline in one process.  All pairs go
+ * through one cpecan_find_local_chains_many call (include/cpecan_local.h) with trim 0, every chain becomes a cigar, and all
+ * cigars go through one cpecan_realigner_realign with the realigner's default options, the gapGamma of this command line and
+ * its --diagonalExpansion and --loadHmm.  Output: queries outer, targets inner, the chains of a pair in round order; a pair
+ * may have no line or several.  Sequences are looked up by name, so target and query names must differ.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -23,6 +28,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "cpecan_local.h"
 #include "cpecan_realign.h"
 
 typedef struct {
@@ -44,7 +50,10 @@ static void usage(void) {
                     "-G --gapped (gapped extension of the chained HSPs)  -Y --yDrop N (with --gapped; default 9400)\n"
                     "-r --diagonalExpansion N (even; default 20)\n"
                     "--adaptiveBand N --minEdgeScore S (each needs the other): pairs whose posterior mass on the band's edge sums to S\n"
-                    "   or more (score units, 10000000 = probability 1) run again, up to N = 1..4 times, each with the expansion doubled\n");
+                    "   or more (score units, 10000000 = probability 1) run again, up to N = 1..4 times, each with the expansion doubled\n"
+                    "--local (local chains on the strands of --strand, each realigned; one cigar per chain)\n"
+                    "   --maxChains K (1..16, default 1)  --minChainScore S (default: the HSP threshold, 800); both need --local;\n"
+                    "   --local does not go with --gapped or --adaptiveBand\n");
 }
 
 static int fail(const char *what) {
@@ -183,6 +192,69 @@ static int align_pairs(const cpecan_model *model, const cpecan_params *params, d
     return status;
 }
 
+/* --local: chains -> cigars -> one realign call; prints the realigned cigars. */
+static int run_local(const cpecan_model *model, const cpecan_anchor_problem *ap, int64_t n, const Records *targets,
+                     const Records *queries, int64_t expansion, int64_t runExpansion, double gapGamma,
+                     const cpecan_anchor_params *anchorParams, const cpecan_anchor_options *anchorOptions,
+                     const cpecan_local_options *localOptions, int device, int strandMode) {
+    int status = 0;
+    cpecan_local_chain **chains = calloc((size_t)(n ? n : 1), sizeof *chains);
+    int64_t **runs = calloc((size_t)(n ? n : 1), sizeof *runs);
+    int64_t *nChains = calloc((size_t)(n ? n : 1), sizeof *nChains), *nRuns = calloc((size_t)(n ? n : 1), sizeof *nRuns);
+    cpecan_cigar *in = NULL, *out = NULL;
+    cpecan_realigner *r = NULL;
+    int64_t nIn = 0, nOut = 0, total = 0;
+    if (!chains || !runs || !nChains || !nRuns) status = 1;
+    else if (n > 0 && cpecan_find_local_chains_many(ap, n, 0, runExpansion, anchorParams, anchorOptions, localOptions, device,
+                                                    strandMode, chains, nChains, runs, nRuns, NULL) != CPECAN_OK)
+        status = fail("local chains");
+    for (int64_t i = 0; status == 0 && i < n; i++) total += nChains[i];
+    if (status == 0 && !(in = calloc((size_t)(total ? total : 1), sizeof *in))) status = 1;
+    for (int64_t i = 0; status == 0 && i < n; i++)
+        for (int64_t j = 0; status == 0 && j < nChains[i]; j++) {
+            if (chains[i][j].nRuns == 0) continue; /* trim is 0: does not happen */
+            if (cpecan_cigar_from_local_chain(targets->r[i % targets->n].name, queries->r[i / targets->n].name, ap[i].lY,
+                                              &chains[i][j], runs[i], &in[nIn]) != CPECAN_OK)
+                status = fail("cigar");
+            else nIn++;
+        }
+    if (status == 0 && nIn > 0) {
+        cpecan_realign_options ro;
+        cpecan_realign_options_default(&ro);
+        ro.gapGamma = (float)gapGamma;
+        if (expansion >= 0) ro.params.diagonalExpansion = expansion;
+        if (cpecan_realigner_create(&r, model, &ro, device) != CPECAN_OK) status = fail("realigner");
+        for (int64_t t = 0; status == 0 && t < targets->n; t++)
+            if (cpecan_realigner_add_sequence(r, targets->r[t].name, targets->r[t].seq, targets->r[t].length) != CPECAN_OK) status = fail("sequence");
+        for (int64_t q = 0; status == 0 && q < queries->n; q++)
+            if (cpecan_realigner_add_sequence(r, queries->r[q].name, queries->r[q].seq, queries->r[q].length) != CPECAN_OK) status = fail("sequence");
+        if (status == 0 && cpecan_realigner_realign(r, in, nIn, &out, &nOut) != CPECAN_OK) status = fail("realign");
+    }
+    for (int64_t k = 0; status == 0 && k < nOut; k++) {
+        const int64_t need = cpecan_cigar_format(&out[k], NULL, 0) + 1;
+        char *text = malloc((size_t)need);
+        if (!text) {
+            status = 1;
+            break;
+        }
+        cpecan_cigar_format(&out[k], text, need);
+        puts(text);
+        free(text);
+    }
+    if (r) cpecan_realigner_destroy(r);
+    cpecan_cigars_free(out, nOut);
+    cpecan_cigars_free(in, nIn);
+    for (int64_t i = 0; i < n; i++) {
+        if (chains) cpecan_free(chains[i]);
+        if (runs) cpecan_free(runs[i]);
+    }
+    free(chains);
+    free(runs);
+    free(nChains);
+    free(nRuns);
+    return status;
+}
+
 int main(int argc, char **argv) {
     const char *hmmFile = NULL;
     long long device = 0;
@@ -191,6 +263,8 @@ int main(int argc, char **argv) {
     int gapped = 0, haveYDrop = 0;
     long long expansion = -1, adaptiveBand = 0, minEdgeScore = 0;
     int haveAdaptive = 0, haveMinEdge = 0;
+    int localMode = 0, haveMaxChains = 0, haveMinChainScore = 0;
+    long long maxChains = 1, minChainScore = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
@@ -202,6 +276,9 @@ int main(int argc, char **argv) {
                                        {"diagonalExpansion", required_argument, 0, 'r'},
                                        {"adaptiveBand", required_argument, 0, 1000},
                                        {"minEdgeScore", required_argument, 0, 1001},
+                                       {"local", no_argument, 0, 1002},
+                                       {"maxChains", required_argument, 0, 1003},
+                                       {"minChainScore", required_argument, 0, 1004},
                                        {0, 0, 0, 0}};
     for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:GY:r:", longOpts, NULL)) != -1;) {
         switch (key) {
@@ -233,6 +310,9 @@ int main(int argc, char **argv) {
         case 'r': if (sscanf(optarg, "%lld", &expansion) != 1 || expansion < 0 || expansion % 2 != 0 || expansion > (1 << 20)) { usage(); return 1; } break;
         case 1000: if (sscanf(optarg, "%lld", &adaptiveBand) != 1 || adaptiveBand < 1 || adaptiveBand > 4) { usage(); return 1; } haveAdaptive = 1; break;
         case 1001: if (sscanf(optarg, "%lld", &minEdgeScore) != 1 || minEdgeScore < 1) { usage(); return 1; } haveMinEdge = 1; break;
+        case 1002: localMode = 1; break;
+        case 1003: if (sscanf(optarg, "%lld", &maxChains) != 1 || maxChains < 1 || maxChains > 16) { usage(); return 1; } haveMaxChains = 1; break;
+        case 1004: if (sscanf(optarg, "%lld", &minChainScore) != 1 || minChainScore < 1 || minChainScore > 0x7fffffffLL) { usage(); return 1; } haveMinChainScore = 1; break;
         default: usage(); return 1;
         }
     }
@@ -246,6 +326,14 @@ int main(int argc, char **argv) {
     }
     if (haveAdaptive != haveMinEdge) {
         fprintf(stderr, "cpecan_align: --adaptiveBand and --minEdgeScore need each other\n");
+        return 1;
+    }
+    if ((haveMaxChains || haveMinChainScore) && !localMode) {
+        fprintf(stderr, "cpecan_align: --maxChains and --minChainScore need --local\n");
+        return 1;
+    }
+    if (localMode && (gapped || haveAdaptive)) {
+        fprintf(stderr, "cpecan_align: --local does not go with --gapped or --adaptiveBand\n");
         return 1;
     }
     if (argc - optind != 2) { /* cPecanAlign.c:93-96 */
@@ -299,13 +387,21 @@ int main(int argc, char **argv) {
             ap[i].sY = queries.r[q].seq;
             ap[i].lY = queries.r[q].length;
         }
-    if (status == 0 && n > 0) {
+    if (status == 0 && localMode) {
+        cpecan_local_options localOptions;
+        cpecan_local_options_default(&localOptions);
+        localOptions.maxChains = (int32_t)maxChains;
+        localOptions.minChainScore = (int32_t)minChainScore;
+        status = run_local(&model, ap, n, &targets, &queries, expansion, params.diagonalExpansion, gapGamma, &anchorParams,
+                           haveThreshold ? &anchorOptions : NULL, &localOptions, (int)device, strandMode);
+    }
+    if (status == 0 && n > 0 && !localMode) {
         if (cpecan_find_anchor_runs_many_with_options(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix,
                                                       &anchorParams, (int)device, strandMode, runs, nRuns, NULL, strands,
                                                       haveThreshold || gapped ? &anchorOptions : NULL) != CPECAN_OK)
             status = fail("anchors");
     }
-    if (status == 0 && n > 0) {
+    if (status == 0 && n > 0 && !localMode) {
         for (int64_t i = 0; i < n; i++) {
             pr[i].sX = ap[i].sX;
             pr[i].lX = ap[i].lX;
@@ -333,7 +429,7 @@ int main(int argc, char **argv) {
         }
         status = align_pairs(&model, &wider, gapGamma, (int)device, pr, yMinus, &targets, &queries, idx, m, texts, edgeSum);
     }
-    for (int64_t i = 0; status == 0 && i < n; i++) {
+    for (int64_t i = 0; status == 0 && !localMode && i < n; i++) {
         puts(texts[i]); /* :149 */
         if (haveAdaptive)
             fprintf(stderr, "cpecan_align: %s %s: round %d, expansion %lld\n", targets.r[i % targets.n].name,

@@ -467,6 +467,59 @@ int cpk_anchor_gaps(const CpkAnchorCall *c, const CpkAnchorList *top, const int3
 int cpk_anchor_splice(const CpkAnchorCall *c, const CpkAnchorList *top, const int32_t *topRuns, const CpkAnchorList *sub,
                       const int32_t *subRuns, double kernelMs);
 
+/* ---- local chains (cpk_local.inl; host side in cpecan_local.c) ---- */
+#define CPK_LOCAL_MAX_CHAINS 16
+/* One caller problem of a local pass: the one problem of the pass list it stands for, or its pair of orientation twins
+ * (`first`, then the CPK_ANCHOR_SHARE_X twin).  The kernel leaves the counts. */
+typedef struct {
+    int64_t first;
+    int32_t twins;   /* 1 or 2 */
+    int32_t nChains; /* chains recorded, at most maxChains */
+    int32_t nRuns;   /* runs of all of them */
+    int32_t rounds;  /* rounds that found a chain: nChains, or one more for the chain under minChainScore that ended them */
+} CpkLocalProblem;
+/* One chain as the kernel records it: the rectangle and the runs in the coordinates of its orientation, relative to the
+ * problem; runOff counts triples from the problem's first. */
+typedef struct {
+    int32_t strand, score, nHsps, runOff, nRuns;
+    int32_t x0, x1, y0, y1, pad;
+} CpkLocalChain;
+typedef struct {
+    int32_t maxChains, minChainScore; /* minChainScore as the kernel compares it: never 0 for "the threshold" */
+} CpkLocalPass;
+/* Steps 0-3 of cpk_anchor_pass on the n problems, then the rounds of step 7 per caller problem.  *chains: malloc'd,
+ * maxChains records per caller problem, of which the first nChains hold; *runs: malloc'd triples, those of caller problem k
+ * from 3 * probs[lprobs[k].first].hspOff on.  Both NULL for n == 0.  probs gets hits, hsps and capped; *ms: kernel time added. */
+int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const CpkLocalPass *lp, CpkAnchorProblem *probs, int64_t n,
+                   CpkLocalProblem *lprobs, int64_t nLocal, CpkLocalChain **chains, int32_t **runs, double *ms);
+
+/* The stages of cpecan_find_local_chains_many (cpecan_local.c); none of them touches a device. */
+struct cpecan_local_options;
+struct cpecan_local_chain;
+struct cpecan_local_stats;
+typedef struct {
+    const char *who;
+    const cpecan_anchor_problem *problems;
+    int64_t n, expansion;
+    int32_t device, strandMode;
+    struct cpecan_local_chain **chains;
+    int64_t *nChains;
+    int64_t **runs;
+    int64_t *nRuns;
+    struct cpecan_local_stats *stats; /* or NULL */
+} CpkLocalCall;
+/* Check: arguments, params (NULL: the defaults), both option records (either NULL: its defaults) into *pass and *lp;
+ * outputs zeroed. */
+int cpk_local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                    const struct cpecan_local_options *localOptions, CpkAnchorPass *pass, CpkLocalPass *lp);
+/* Layout: cpk_anchor_layout's list with the whole of every non-empty pair in it, soft-masked, twins for BOTH; and the
+ * malloc'd record per caller problem that is in the list (*lprobs, *nLocal). */
+int cpk_local_layout(const CpkLocalCall *c, CpkAnchorList *top, uint8_t **bytes, int64_t *nBytes, int64_t *nExtra,
+                     CpkLocalProblem **lprobs, int64_t *nLocal);
+/* Assemble: what a pass left becomes the caller's arrays and statistics. */
+int cpk_local_assemble(const CpkLocalCall *c, const CpkAnchorList *top, const CpkLocalProblem *lprobs, int64_t nLocal,
+                       const CpkLocalChain *chains, const int32_t *runs, int32_t maxChains, double kernelMs);
+
 /* ---- dense forward / backward rows (cpk_dense.inl; host side in cpecan_dense.c) ---- */
 /* One anti-diagonal of a dense problem: its band and the band cells on the problem's earlier diagonals. */
 typedef struct {

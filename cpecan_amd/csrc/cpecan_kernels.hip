@@ -81,6 +81,7 @@ extern "C" const char *cpk_last_error(void) { return g_err; }
 #include "cpk_post.inl"
 #include "cpk_cells.inl"
 #include "cpk_anchor.inl"
+#include "cpk_local.inl"
 #include "cpk_dense.inl"
 
 // ------------------------------------------------------------------------------------------------
@@ -2210,20 +2211,28 @@ static int anchor_pass_gapped(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnc
     return CPECAN_OK;
 }
 
-extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int32_t **runsOut,
-                               double *ms) {
-    *runsOut = nullptr;
-    if (n <= 0) return CPECAN_OK;
+// The device lists of a pass once steps 1-3 are queued: the HSP slots of every problem as cpk_anchor_hits / cpk_anchor_extend
+// fill them, their counters, and the scratch words and run slots that the kernel behind them works in.
+struct AnchorPassLists {
+    CpkAnchorProblem *dProbs = nullptr;
+    int4 *dHsps = nullptr;
+    int32_t *dCount = nullptr, *dBest = nullptr, *dPred = nullptr, *dRuns = nullptr;
+    size_t nSlots = 0;
+};
+
+// Steps 0-3 of a pass (n > 0), the part every chain kernel shares (cpk_anchor_pass, cpk_local_pass): round 1 counts the
+// hits, the host sizes the lists, round 2 queues the extension.  On return the stream holds the launches that fill the HSP
+// lists, evA is recorded in front of them, and probs has the hit counts and the slots.  sc: the caller's, on c's stream.
+static int anchor_pass_lists(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, PostScratch &sc,
+                             AnchorPassLists *lists, double *ms) {
     CpkAnchorPlan plan;
     if (int rc = cpk_anchor_pass_plan(pass, probs, n, c->nSym, c->nForward, &plan)) return rc;
     const CpkAnchorParams &prm = pass->prm;
     CpkAnchorSeed seed;
     memcpy(&seed, &plan.seed, sizeof seed);
-    CPK_ON_DEVICE(c->device);
-    PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
     hipStream_t st = sc.stream;
     const size_t probBytes = sizeof(CpkAnchorProblem) * (size_t)n;
-    const dim3 perProblem((unsigned)n), perChunk((unsigned)n, (unsigned)std::min(64, (plan.maxCap + 1023) / 1024));
+    const dim3 perChunk((unsigned)n, (unsigned)std::min(64, (plan.maxCap + 1023) / 1024));
     CpkAnchorProblem *dProbs = nullptr;
     unsigned long long *dKeys = nullptr;
     if (int rc = sc.alloc(&dProbs, (size_t)n)) return rc;
@@ -2283,6 +2292,26 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAn
         hipLaunchKernelGGL(cpk_anchor_hits<true>, perChunk, dim3(256), 0, st, dProbs, c->dSym, dKeys, prm, seed.span, dHsps, dCount);
     }
     HIP_TRY(hipGetLastError());
+    *lists = AnchorPassLists{dProbs, dHsps, dCount, dBest, dPred, dRuns, nSlots};
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAnchorProblem *probs, int64_t n, int32_t **runsOut,
+                               double *ms) {
+    *runsOut = nullptr;
+    if (n <= 0) return CPECAN_OK;
+    CPK_ON_DEVICE(c->device);
+    PostScratch sc(c->sc->stream);  // this pass's blocks go back to the cache when it returns
+    hipStream_t st = sc.stream;
+    AnchorPassLists lists;
+    if (int rc = anchor_pass_lists(c, pass, probs, n, sc, &lists, ms)) return rc;
+    const CpkAnchorParams &prm = pass->prm;
+    const size_t probBytes = sizeof(CpkAnchorProblem) * (size_t)n, nSlots = lists.nSlots;
+    const dim3 perProblem((unsigned)n);
+    CpkAnchorProblem *dProbs = lists.dProbs;
+    int4 *dHsps = lists.dHsps;
+    int32_t *dCount = lists.dCount, *dBest = lists.dBest, *dPred = lists.dPred, *dRuns = lists.dRuns;
+    float part = 0.f;
     bool gapped = false;
     for (int64_t i = 0; i < n; i++) gapped = gapped || (probs[i].flags & CPK_ANCHOR_GAPPED);
     if (gapped) return anchor_pass_gapped(c, pass, probs, n, sc, dProbs, dHsps, dCount, dBest, dPred, dRuns, nSlots, runsOut, ms);
@@ -2304,6 +2333,70 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAn
         HIP_TRY(e);
     }
     *ms += part;
+    *runsOut = runs;
+    return CPECAN_OK;
+}
+
+// Local chains (cpk_local.inl): steps 0-3 as in cpk_anchor_pass, then cpk_local_peel with one workgroup per caller problem
+// over the pools of its twins.  *chains: malloc'd, lp->maxChains records per caller problem; *runs: malloc'd triples, the
+// runs of caller problem k from 3 * probs[lprobs[k].first].hspOff on, chain by chain.  lprobs gets the counts.
+extern "C" int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const CpkLocalPass *lp, CpkAnchorProblem *probs, int64_t n,
+                              CpkLocalProblem *lprobs, int64_t nLocal, CpkLocalChain **chainsOut, int32_t **runsOut, double *ms) {
+    *chainsOut = nullptr;
+    *runsOut = nullptr;
+    if (n <= 0 || nLocal <= 0) return CPECAN_OK;
+    if (lp->maxChains < 1 || lp->maxChains > CPK_LOCAL_MAX_CHAINS) {
+        cpk_set_error("local chains: maxChains is 1 .. %d", CPK_LOCAL_MAX_CHAINS);
+        return CPECAN_EINVAL;
+    }
+    for (int64_t k = 0; k < nLocal; k++) {  // the twins of a caller problem follow each other, so do their slots
+        const CpkLocalProblem &q = lprobs[k];
+        if (q.twins < 1 || q.twins > 2 || q.first < 0 || q.first + q.twins > n ||
+            (q.twins == 2 && !(probs[q.first + 1].flags & CPK_ANCHOR_SHARE_X))) {
+            cpk_set_error("local chains: problem %lld does not name one problem of the pass or a pair of twins", (long long)k);
+            return CPECAN_EINVAL;
+        }
+    }
+    CPK_ON_DEVICE(c->device);
+    PostScratch sc(c->sc->stream);
+    hipStream_t st = sc.stream;
+    AnchorPassLists lists;
+    if (int rc = anchor_pass_lists(c, pass, probs, n, sc, &lists, ms)) return rc;
+    const size_t probBytes = sizeof(CpkAnchorProblem) * (size_t)n, localBytes = sizeof(CpkLocalProblem) * (size_t)nLocal;
+    const size_t nChainSlots = (size_t)nLocal * (size_t)lp->maxChains, nSlots = lists.nSlots;
+    CpkLocalProblem *dLocal = nullptr;
+    CpkLocalChain *dChains = nullptr;
+    if (int rc = sc.alloc(&dLocal, (size_t)nLocal)) return rc;
+    if (int rc = sc.alloc(&dChains, nChainSlots)) return rc;
+    HIP_TRY(hipMemcpyAsync(dLocal, lprobs, localBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dChains, 0, sizeof(CpkLocalChain) * nChainSlots, st));
+    hipLaunchKernelGGL(cpk_local_peel, dim3((unsigned)nLocal), dim3(256), 0, st, lists.dProbs, dLocal, lists.dHsps, lists.dCount,
+                       lists.dBest, lists.dPred, lists.dRuns, dChains, pass->prm.maxHsps, pass->trim, lp->maxChains,
+                       lp->minChainScore);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evB, st));
+    CpkLocalChain *chains = (CpkLocalChain *)malloc(sizeof(CpkLocalChain) * nChainSlots);
+    int32_t *runs = (int32_t *)malloc(sizeof(int32_t) * 3 * nSlots);
+    float part = 0.f;
+    const bool noMemory = !chains || !runs;
+    hipError_t e = noMemory ? hipErrorOutOfMemory : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(probs, lists.dProbs, probBytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(lprobs, dLocal, localBytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(chains, dChains, sizeof(CpkLocalChain) * nChainSlots, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(runs, lists.dRuns, sizeof(int32_t) * 3 * nSlots, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&part, c->evA, c->evB);
+    if (e != hipSuccess) {
+        free(chains);
+        free(runs);
+        if (noMemory) {
+            cpk_set_error("out of memory");
+            return CPECAN_ENOMEM;
+        }
+        HIP_TRY(e);
+    }
+    *ms += part;
+    *chainsOut = chains;
     *runsOut = runs;
     return CPECAN_OK;
 }

@@ -341,17 +341,15 @@ __device__ __forceinline__ int anchor_gap_rows(int m, int n, bool right, bool le
     return (right ? rows : 0) + (left ? rows : 0);
 }
 
-template <bool UNTRIMMED>
-__device__ __forceinline__ void anchor_chain_body(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp, int32_t *bestAll,
-                                                  int32_t *predAll, int32_t *runsAll, int maxHsps, int trim, int32_t *gapRow) {
-    __shared__ long long red[16];
+// What comes before step 4 on one problem's list, by the whole workgroup: the slots behind the nIn filled ones padded, the
+// list sorted by place, exact duplicates dropped (step 2), the cap of step 3, sorted by place again.  hsp: the problem's
+// cap slots; pred: cap ints of scratch.  Returns the size of the pool; *nUnique: the HSPs before the cap; *capped: step 3
+// cut.  Every thread gets the same values, and the list is ready for all of them (cpk_anchor_chain and cpk_local_peel
+// share this).
+__device__ __forceinline__ int anchor_pool_prepare(int4 *hsp, int cap, int nIn, int maxHsps, int32_t *pred, int *nUnique, int *capped) {
     __shared__ int shCount;
-    const int p = blockIdx.x, tid = threadIdx.x, nT = blockDim.x;
-    const CpkAnchorProblem pr = probs[p];
-    int4 *hsp = hspsAll + pr.hspOff;
-    int32_t *best = bestAll + pr.hspOff, *pred = predAll + pr.hspOff, *runs = runsAll + 3 * pr.hspOff;
-    const int cap = pr.hspCap;
-    int n = min(nHsp[p], cap);
+    const int tid = threadIdx.x, nT = blockDim.x;
+    int n = min(nIn, cap);
     for (int i = n + tid; i < cap; i += nT) hsp[i] = CPK_ANCHOR_HSP_NONE;
     if (tid == 0) shCount = 0;
     anchor_bitonic(hsp, cap, AnchorHspByPlace());
@@ -369,18 +367,31 @@ __device__ __forceinline__ void anchor_chain_body(CpkAnchorProblem *probs, int4 
     for (int i = tid; i < n; i += nT)
         if (pred[i]) hsp[i] = CPK_ANCHOR_HSP_NONE;
     __syncthreads();
-    const int nUnique = shCount;
-    if (nUnique != n) anchor_bitonic(hsp, cap, AnchorHspByPlace());
-    n = nUnique;
-    int capped = 0;
+    *nUnique = shCount;
+    if (*nUnique != n) anchor_bitonic(hsp, cap, AnchorHspByPlace());
+    n = *nUnique;
+    *capped = 0;
     if (n > maxHsps) {  // step 3
-        capped = 1;
+        *capped = 1;
         anchor_bitonic(hsp, cap, AnchorHspByScore());
         for (int i = maxHsps + tid; i < n; i += nT) hsp[i] = CPK_ANCHOR_HSP_NONE;
         n = maxHsps;
         anchor_bitonic(hsp, cap, AnchorHspByPlace());
     }
     __syncthreads();
+    return n;
+}
+
+template <bool UNTRIMMED>
+__device__ __forceinline__ void anchor_chain_body(CpkAnchorProblem *probs, int4 *hspsAll, const int32_t *nHsp, int32_t *bestAll,
+                                                  int32_t *predAll, int32_t *runsAll, int maxHsps, int trim, int32_t *gapRow) {
+    __shared__ long long red[16];
+    const int p = blockIdx.x, tid = threadIdx.x, nT = blockDim.x;
+    const CpkAnchorProblem pr = probs[p];
+    int4 *hsp = hspsAll + pr.hspOff;
+    int32_t *best = bestAll + pr.hspOff, *pred = predAll + pr.hspOff, *runs = runsAll + 3 * pr.hspOff;
+    int nUnique, capped;
+    const int n = anchor_pool_prepare(hsp, pr.hspCap, nHsp[p], maxHsps, pred, &nUnique, &capped);
     // step 4: predecessors of i have a smaller x, so they come before i
     for (int i = 0; i < n; i++) {
         const int4 me = hsp[i];
