@@ -20,6 +20,9 @@
  * cigars go through one cpecan_realigner_realign with the realigner's default options, the gapGamma of this command line and
  * its --diagonalExpansion and --loadHmm.  Output: queries outer, targets inner, the chains of a pair in round order; a pair
  * may have no line or several.  Sequences are looked up by name, so target and query names must differ.
+ * --local --extendChains [--chainYDrop N]: the chains are extended into their gaps and outwards before they become cigars
+ * (cpecan_find_local_chains_many_gapped), as lastz's cigars are gapped; --chainYDrop sets what
+ * ends such an extension (default 9400).  Both need --local, --chainYDrop needs --extendChains.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -53,7 +56,9 @@ static void usage(void) {
                     "   or more (score units, 10000000 = probability 1) run again, up to N = 1..4 times, each with the expansion doubled\n"
                     "--local (local chains on the strands of --strand, each realigned; one cigar per chain)\n"
                     "   --maxChains K (1..16, default 1)  --minChainScore S (default: the HSP threshold, 800); both need --local;\n"
-                    "   --local does not go with --gapped or --adaptiveBand\n");
+                    "   --local does not go with --gapped or --adaptiveBand\n"
+                    "   --extendChains (with --local: gapped extension of every chain into its gaps and outwards, each chain kept clear\n"
+                    "   of the others)  --chainYDrop N (with --extendChains; default 9400)\n");
 }
 
 static int fail(const char *what) {
@@ -196,7 +201,7 @@ static int align_pairs(const cpecan_model *model, const cpecan_params *params, d
 static int run_local(const cpecan_model *model, const cpecan_anchor_problem *ap, int64_t n, const Records *targets,
                      const Records *queries, int64_t expansion, int64_t runExpansion, double gapGamma,
                      const cpecan_anchor_params *anchorParams, const cpecan_anchor_options *anchorOptions,
-                     const cpecan_local_options *localOptions, int device, int strandMode) {
+                     const cpecan_local_options *localOptions, int device, int strandMode, int extendChains) {
     int status = 0;
     cpecan_local_chain **chains = calloc((size_t)(n ? n : 1), sizeof *chains);
     int64_t **runs = calloc((size_t)(n ? n : 1), sizeof *runs);
@@ -205,8 +210,9 @@ static int run_local(const cpecan_model *model, const cpecan_anchor_problem *ap,
     cpecan_realigner *r = NULL;
     int64_t nIn = 0, nOut = 0, total = 0;
     if (!chains || !runs || !nChains || !nRuns) status = 1;
-    else if (n > 0 && cpecan_find_local_chains_many(ap, n, 0, runExpansion, anchorParams, anchorOptions, localOptions, device,
-                                                    strandMode, chains, nChains, runs, nRuns, NULL) != CPECAN_OK)
+    else if (n > 0 && (extendChains ? cpecan_find_local_chains_many_gapped : cpecan_find_local_chains_many)(
+                          ap, n, 0, runExpansion, anchorParams, anchorOptions, localOptions, device, strandMode, chains, nChains, runs,
+                          nRuns, NULL) != CPECAN_OK)
         status = fail("local chains");
     for (int64_t i = 0; status == 0 && i < n; i++) total += nChains[i];
     if (status == 0 && !(in = calloc((size_t)(total ? total : 1), sizeof *in))) status = 1;
@@ -264,7 +270,8 @@ int main(int argc, char **argv) {
     long long expansion = -1, adaptiveBand = 0, minEdgeScore = 0;
     int haveAdaptive = 0, haveMinEdge = 0;
     int localMode = 0, haveMaxChains = 0, haveMinChainScore = 0;
-    long long maxChains = 1, minChainScore = 0;
+    long long maxChains = 1, minChainScore = 0, chainYDrop = 0;
+    int extendChains = 0, haveChainYDrop = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
@@ -279,6 +286,8 @@ int main(int argc, char **argv) {
                                        {"local", no_argument, 0, 1002},
                                        {"maxChains", required_argument, 0, 1003},
                                        {"minChainScore", required_argument, 0, 1004},
+                                       {"extendChains", no_argument, 0, 1005},
+                                       {"chainYDrop", required_argument, 0, 1006},
                                        {0, 0, 0, 0}};
     for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:GY:r:", longOpts, NULL)) != -1;) {
         switch (key) {
@@ -313,6 +322,8 @@ int main(int argc, char **argv) {
         case 1002: localMode = 1; break;
         case 1003: if (sscanf(optarg, "%lld", &maxChains) != 1 || maxChains < 1 || maxChains > 16) { usage(); return 1; } haveMaxChains = 1; break;
         case 1004: if (sscanf(optarg, "%lld", &minChainScore) != 1 || minChainScore < 1 || minChainScore > 0x7fffffffLL) { usage(); return 1; } haveMinChainScore = 1; break;
+        case 1005: extendChains = 1; break;
+        case 1006: if (sscanf(optarg, "%lld", &chainYDrop) != 1 || chainYDrop < 1 || chainYDrop > 0x7fffffffLL) { usage(); return 1; } haveChainYDrop = 1; break;
         default: usage(); return 1;
         }
     }
@@ -330,6 +341,14 @@ int main(int argc, char **argv) {
     }
     if ((haveMaxChains || haveMinChainScore) && !localMode) {
         fprintf(stderr, "cpecan_align: --maxChains and --minChainScore need --local\n");
+        return 1;
+    }
+    if ((extendChains || haveChainYDrop) && !localMode) {
+        fprintf(stderr, "cpecan_align: --extendChains and --chainYDrop need --local\n");
+        return 1;
+    }
+    if (haveChainYDrop && !extendChains) {
+        fprintf(stderr, "cpecan_align: --chainYDrop needs --extendChains\n");
         return 1;
     }
     if (localMode && (gapped || haveAdaptive)) {
@@ -392,8 +411,12 @@ int main(int argc, char **argv) {
         cpecan_local_options_default(&localOptions);
         localOptions.maxChains = (int32_t)maxChains;
         localOptions.minChainScore = (int32_t)minChainScore;
+        if (extendChains) { /* --gapped is refused with --local: the two fields are free for the chains */
+            anchorOptions.gappedExtension = 1;
+            anchorOptions.yDrop = (int32_t)chainYDrop;
+        }
         status = run_local(&model, ap, n, &targets, &queries, expansion, params.diagonalExpansion, gapGamma, &anchorParams,
-                           haveThreshold ? &anchorOptions : NULL, &localOptions, (int)device, strandMode);
+                           haveThreshold || extendChains ? &anchorOptions : NULL, &localOptions, (int)device, strandMode, extendChains);
     }
     if (status == 0 && n > 0 && !localMode) {
         if (cpecan_find_anchor_runs_many_with_options(ap, n, trim, params.diagonalExpansion, anchorMatrix, repeatMaskMatrix,

@@ -467,7 +467,7 @@ int cpk_anchor_gaps(const CpkAnchorCall *c, const CpkAnchorList *top, const int3
 int cpk_anchor_splice(const CpkAnchorCall *c, const CpkAnchorList *top, const int32_t *topRuns, const CpkAnchorList *sub,
                       const int32_t *subRuns, double kernelMs);
 
-/* ---- local chains (cpk_local.inl; host side in cpecan_local.c; DESIGN.md section 7, step 7) ---- */
+/* ---- local chains (cpk_local.inl; host side in cpecan_local.c; DESIGN.md section 7, steps 7 and 7b) ---- */
 #define CPK_LOCAL_MAX_CHAINS 16
 /* One caller problem of a local pass: the one problem of the pass list it stands for, or its pair of orientation twins
  * (`first`, then the CPK_ANCHOR_SHARE_X twin).  The kernel leaves the counts. */
@@ -489,7 +489,10 @@ typedef struct {
 } CpkLocalPass;
 /* Steps 0-3 of cpk_anchor_pass on the n problems, then the rounds of step 7 per caller problem.  *chains: malloc'd,
  * maxChains records per caller problem, of which the first nChains hold; *runs: malloc'd triples, those of caller problem k
- * from 3 * probs[lprobs[k].first].hspOff on.  Both NULL for n == 0.  probs gets hits, hsps and capped; *ms: kernel time added. */
+ * from 3 * probs[lprobs[k].first].hspOff on.  Both NULL for n == 0.  probs gets hits, hsps and capped; *ms: kernel time added.
+ * Problems that carry CPK_ANCHOR_GAPPED (all of the pass or none; yDrop and the diagonals as for an anchor pass) have their
+ * chains extended behind the peel (step 7b): the records then hold the extended rectangle and runs, a chain may have more
+ * runs than HSPs, and hspOff of a problem's first twin has moved to a run list of its own. */
 int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const CpkLocalPass *lp, CpkAnchorProblem *probs, int64_t n,
                    CpkLocalProblem *lprobs, int64_t nLocal, CpkLocalChain **chains, int32_t **runs, double *ms);
 
@@ -512,6 +515,13 @@ typedef struct {
  * outputs zeroed. */
 int cpk_local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
                     const struct cpecan_local_options *localOptions, CpkAnchorPass *pass, CpkLocalPass *lp);
+/* The same with anchorOptions->gappedExtension = 1 admitted (cpecan_find_local_chains_many_gapped), and what carries the
+ * three gapped options of a checked call into the list of its layout: CPK_ANCHOR_GAPPED, the diagonals and yDrop of every
+ * problem, as an anchor pass takes them. */
+int cpk_local_check_gapped(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params,
+                           const cpecan_anchor_options *anchorOptions, const struct cpecan_local_options *localOptions,
+                           CpkAnchorPass *pass, CpkLocalPass *lp);
+void cpk_local_mark_gapped(CpkAnchorList *top, const cpecan_anchor_options *anchorOptions);
 /* Layout: cpk_anchor_layout's list with the whole of every non-empty pair in it, soft-masked, twins for BOTH; and the
  * malloc'd record per caller problem that is in the list (*lprobs, *nLocal). */
 int cpk_local_layout(const CpkLocalCall *c, CpkAnchorList *top, uint8_t **bytes, int64_t *nBytes, int64_t *nExtra,

@@ -2337,9 +2337,153 @@ extern "C" int cpk_anchor_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, CpkAn
     return CPECAN_OK;
 }
 
+// Step 7b, the host's part: where the gaps, scratch rows and runs of a pass that extends its chains lie.  Built from the
+// chain records and the HSP triples that came back behind the peel (trim 0: a problem's run slots hold its chains' HSPs).
+// Gaps are numbered problem by problem, chain by chain; rows round by round, so that a round's rows lie together and the
+// scratch of one round serves the next.  A gap has the rows of the unfenced rectangle (anchor_gap_rows): the fences only
+// shrink an extension.
+struct LocalGappedLayout {
+    std::vector<int64_t> gapBase;  // nLocal * maxChains + 1: first gap of every chain slot
+    std::vector<int64_t> gapRow;   // per gap: its first row, and the first row of its left extension
+    std::vector<int64_t> runBase;  // nLocal + 1: first run triple of every caller problem
+    std::vector<std::vector<int64_t>> bounds;  // per round: where the rows of its gaps start, ascending, then the round's end
+    std::vector<int> roundGaps;    // per round: most gaps of one chain
+    int64_t nRows = 0, maxRoundRows = 0;
+};
+
+static int local_gapped_layout(const CpkAnchorProblem *probs, const CpkLocalProblem *lprobs, int64_t nLocal,
+                               const CpkLocalChain *chains, const int32_t *hsps, int maxChains, LocalGappedLayout *out) {
+    LocalGappedLayout &L = *out;
+    L.gapBase.assign((size_t)nLocal * maxChains + 1, 0);
+    L.runBase.assign((size_t)nLocal + 1, 0);
+    L.bounds.assign((size_t)maxChains, {});
+    L.roundGaps.assign((size_t)maxChains, 0);
+    int64_t nGaps = 0;
+    for (int64_t k = 0; k < nLocal; k++)
+        for (int r = 0; r < maxChains; r++) {
+            L.gapBase[(size_t)(k * maxChains + r)] = nGaps;
+            if (r < lprobs[k].nChains) nGaps += chains[k * maxChains + r].nHsps + 1;
+        }
+    L.gapBase.back() = nGaps;
+    L.gapRow.assign(2 * (size_t)nGaps, 0);
+    std::vector<int64_t> rowsOf((size_t)nLocal * maxChains, 0);
+    for (int r = 0; r < maxChains; r++) {
+        const int64_t roundStart = L.nRows;
+        for (int64_t k = 0; k < nLocal; k++) {
+            if (r >= lprobs[k].nChains) continue;
+            const CpkAnchorProblem &p = probs[lprobs[k].first];
+            const CpkLocalChain &ch = chains[k * maxChains + r];
+            const int32_t *h = hsps + 3 * (p.hspOff + ch.runOff);
+            const int c = ch.nHsps, maxDiags = CPK_ANCHOR_DIAGS(p.flags);
+            if (c < 1 || ch.runOff < 0 || ch.runOff + c > lprobs[k].nRuns) {
+                cpk_set_error("local chains: a chain record does not name HSPs of its problem");
+                return CPECAN_EHIP;
+            }
+            L.roundGaps[(size_t)r] = std::max(L.roundGaps[(size_t)r], c + 1);
+            int pX = 0, pY = 0;
+            for (int g = 0; g <= c; g++) {
+                const int bX = g < c ? h[3 * g] : p.lX, bY = g < c ? h[3 * g + 1] : p.lY;
+                if (bX < pX || bY < pY) {
+                    cpk_set_error("local chains: the HSPs of a chain do not ascend");
+                    return CPECAN_EHIP;
+                }
+                const int rows = std::min(bX - pX + bY - pY, maxDiags);
+                const int64_t q = L.gapBase[(size_t)(k * maxChains + r)] + g;
+                L.gapRow[2 * (size_t)q] = L.nRows;
+                L.gapRow[2 * (size_t)q + 1] = L.nRows + (g >= 1 ? rows : 0);
+                L.bounds[(size_t)r].push_back(L.nRows);
+                L.nRows += (g >= 1 ? rows : 0) + (g < c ? rows : 0);
+                if (g < c) pX = bX + h[3 * g + 2], pY = bY + h[3 * g + 2];
+            }
+            rowsOf[(size_t)(k * maxChains + r)] = L.nRows - L.bounds[(size_t)r][L.bounds[(size_t)r].size() - (size_t)(c + 1)];
+        }
+        L.bounds[(size_t)r].push_back(L.nRows);
+        L.maxRoundRows = std::max(L.maxRoundRows, L.nRows - roundStart);
+    }
+    for (int64_t k = 0; k < nLocal; k++) {  // every block takes a row at least, and the chained HSPs come on top
+        int64_t cap = 0;
+        for (int r = 0; r < lprobs[k].nChains; r++) cap += rowsOf[(size_t)(k * maxChains + r)] + chains[k * maxChains + r].nHsps;
+        L.runBase[(size_t)k + 1] = L.runBase[(size_t)k] + cap;
+    }
+    return CPECAN_OK;
+}
+
+// The end of a local pass that extends its chains (step 7b); the peel's records are on the host and still on the device.
+// Per round one launch of cpk_local_gapped -- several, cut at gap boundaries, where the round's rows pass the scratch budget --
+// then the assembly.  *runsOut (the HSP triples on entry) is replaced by the runs, and hspOff of every problem's first twin
+// moves to them.
+static int local_pass_gapped(CpkAnchorCtx *c, const CpkAnchorPass *pass, const CpkLocalPass *lp, CpkAnchorProblem *probs,
+                             CpkLocalProblem *lprobs, int64_t nLocal, PostScratch &sc, const AnchorPassLists &lists,
+                             CpkLocalProblem *dLocal, CpkLocalChain *dChains, CpkLocalChain *chains, int32_t **runsOut, double *ms) {
+    hipStream_t st = sc.stream;
+    const int K = lp->maxChains;
+    LocalGappedLayout L;
+    if (int rc = local_gapped_layout(probs, lprobs, nLocal, chains, *runsOut, K, &L)) return rc;
+    const int64_t budget = CPK_ANCHOR_GAPPED_BUDGET_ROWS, nGaps = L.gapBase.back(), nRunsCap = std::max<int64_t>(L.runBase.back(), 1);
+    int64_t *dGapBase = nullptr, *dGapRow = nullptr, *dRunBase = nullptr;
+    uint8_t *dTrace = nullptr;
+    int32_t *dBlocks = nullptr, *dRunsOut = nullptr;
+    int2 *dCounts = nullptr;
+    const size_t nCounts = (size_t)std::max<int64_t>(nGaps, 1);
+    if (int rc = sc.alloc(&dGapBase, L.gapBase.size())) return rc;
+    if (int rc = sc.alloc(&dGapRow, std::max<size_t>(L.gapRow.size(), 2))) return rc;
+    if (int rc = sc.alloc(&dRunBase, L.runBase.size())) return rc;
+    if (int rc = sc.alloc(&dTrace, (size_t)std::max<int64_t>(std::min(L.maxRoundRows, budget), 1) * 64)) return rc;
+    if (int rc = sc.alloc(&dBlocks, (size_t)std::max<int64_t>(L.nRows, 1) * 3)) return rc;
+    if (int rc = sc.alloc(&dCounts, nCounts)) return rc;
+    if (int rc = sc.alloc(&dRunsOut, (size_t)nRunsCap * 3)) return rc;
+    HIP_TRY(hipMemcpyAsync(dGapBase, L.gapBase.data(), sizeof(int64_t) * L.gapBase.size(), hipMemcpyHostToDevice, st));
+    if (!L.gapRow.empty())
+        HIP_TRY(hipMemcpyAsync(dGapRow, L.gapRow.data(), sizeof(int64_t) * L.gapRow.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dRunBase, L.runBase.data(), sizeof(int64_t) * L.runBase.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dCounts, 0, sizeof(int2) * nCounts, st));
+    HIP_TRY(hipEventRecord(c->evA, st));
+    for (int r = 0; r < K; r++) {
+        const std::vector<int64_t> &bounds = L.bounds[(size_t)r];
+        const int64_t end = bounds.back();
+        for (int64_t lo = bounds.front(); lo < end;) {
+            const int64_t hi = end - lo <= budget ? end : cpk_anchor_gapped_slice_end(bounds.data(), (int64_t)bounds.size(), lo, budget);
+            if (hi <= lo) {
+                cpk_set_error("local chains: a gap's extensions do not fit the scratch budget");
+                return CPECAN_EINVAL;
+            }
+            hipLaunchKernelGGL(cpk_local_gapped, dim3((unsigned)nLocal, (unsigned)L.roundGaps[(size_t)r]), dim3(64), 0, st, lists.dProbs,
+                               dLocal, dChains, c->dSym, pass->prm, lists.dRuns, dGapBase, dGapRow, K, r, lo, hi, dTrace, dBlocks,
+                               dCounts);
+            HIP_TRY(hipGetLastError());
+            lo = hi;
+        }
+    }
+    hipLaunchKernelGGL(cpk_local_gapped_assemble, dim3((unsigned)nLocal), dim3(64), 0, st, lists.dProbs, dLocal, dChains, lists.dRuns,
+                       dGapBase, dGapRow, dRunBase, dBlocks, dCounts, dRunsOut, K, pass->trim);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->evB, st));
+    int32_t *runs = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)nRunsCap);
+    if (!runs) {
+        cpk_set_error("out of memory");
+        return CPECAN_ENOMEM;
+    }
+    float part = 0.f;
+    hipError_t e = hipMemcpyAsync(lprobs, dLocal, sizeof(CpkLocalProblem) * (size_t)nLocal, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(chains, dChains, sizeof(CpkLocalChain) * (size_t)nLocal * (size_t)K, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(runs, dRunsOut, sizeof(int32_t) * 3 * (size_t)nRunsCap, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&part, c->evA, c->evB);
+    if (e != hipSuccess) {
+        free(runs);
+        HIP_TRY(e);
+    }
+    *ms += part;
+    for (int64_t k = 0; k < nLocal; k++) probs[lprobs[k].first].hspOff = L.runBase[(size_t)k];
+    free(*runsOut);
+    *runsOut = runs;
+    return CPECAN_OK;
+}
+
 // Local chains (cpk_local.inl): steps 0-3 as in cpk_anchor_pass, then cpk_local_peel with one workgroup per caller problem
 // over the pools of its twins.  *chains: malloc'd, lp->maxChains records per caller problem; *runs: malloc'd triples, the
-// runs of caller problem k from 3 * probs[lprobs[k].first].hspOff on, chain by chain.  lprobs gets the counts.
+// runs of caller problem k from 3 * probs[lprobs[k].first].hspOff on, chain by chain.  lprobs gets the counts.  Where the
+// problems carry CPK_ANCHOR_GAPPED -- all of them or none -- the chains are then extended (step 7b, local_pass_gapped).
 extern "C" int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const CpkLocalPass *lp, CpkAnchorProblem *probs, int64_t n,
                               CpkLocalProblem *lprobs, int64_t nLocal, CpkLocalChain **chainsOut, int32_t **runsOut, double *ms) {
     *chainsOut = nullptr;
@@ -2357,6 +2501,13 @@ extern "C" int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const 
             return CPECAN_EINVAL;
         }
     }
+    int64_t nGapped = 0;
+    for (int64_t i = 0; i < n; i++) nGapped += (probs[i].flags & CPK_ANCHOR_GAPPED) != 0;
+    if (nGapped != 0 && nGapped != n) {
+        cpk_set_error("local chains: either every problem of a pass extends its chains or none does");
+        return CPECAN_EINVAL;
+    }
+    const bool gapped = nGapped != 0;
     CPK_ON_DEVICE(c->device);
     PostScratch sc(c->sc->stream);
     hipStream_t st = sc.stream;
@@ -2371,8 +2522,8 @@ extern "C" int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const 
     HIP_TRY(hipMemcpyAsync(dLocal, lprobs, localBytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(dChains, 0, sizeof(CpkLocalChain) * nChainSlots, st));
     hipLaunchKernelGGL(cpk_local_peel, dim3((unsigned)nLocal), dim3(256), 0, st, lists.dProbs, dLocal, lists.dHsps, lists.dCount,
-                       lists.dBest, lists.dPred, lists.dRuns, dChains, pass->prm.maxHsps, pass->trim, lp->maxChains,
-                       lp->minChainScore);
+                       lists.dBest, lists.dPred, lists.dRuns, dChains, pass->prm.maxHsps, gapped ? 0 : pass->trim, lp->maxChains,
+                       lp->minChainScore);  // trim 0: the run slots keep every chained HSP for step 7b, which trims behind it
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->evB, st));
     CpkLocalChain *chains = (CpkLocalChain *)malloc(sizeof(CpkLocalChain) * nChainSlots);
@@ -2396,6 +2547,13 @@ extern "C" int cpk_local_pass(CpkAnchorCtx *c, const CpkAnchorPass *pass, const 
         HIP_TRY(e);
     }
     *ms += part;
+    if (gapped) {
+        if (int rc = local_pass_gapped(c, pass, lp, probs, lprobs, nLocal, sc, lists, dLocal, dChains, chains, &runs, ms)) {
+            free(chains);
+            free(runs);
+            return rc;
+        }
+    }
     *chainsOut = chains;
     *runsOut = runs;
     return CPECAN_OK;

@@ -1,10 +1,11 @@
 /*
- * cpecan_local.c -- host side of the local chains (include/cpecan_local.h: cpecan_find_local_chains_many; DESIGN.md
- * section 7, step 7).  The kernels do steps 0-3 as for every anchor pass and then peel the chains (cpk_local.inl); this file
- * checks the call, lays the pairs out with the anchor finder's own layout stage (every pair whole, soft-masked, twins for
- * BOTH), and turns the device records into the caller's arrays.  A call is three stages -- check, layout, assemble -- around
- * one device function, cpk_local_pass; no stage touches a device (tests/test_local_cpu.py runs them with the model in the
- * pass's place, tests/c/test_local_plan.c over synthetic passes).
+ * cpecan_local.c -- host side of the local chains (include/cpecan_local.h: cpecan_find_local_chains_many and
+ * cpecan_find_local_chains_many_gapped).  The kernels do steps 0-3 as for every anchor
+ * pass, peel the chains and, where the problems ask for it, extend them (cpk_local.inl); this file checks the call, lays the
+ * pairs out with the anchor finder's own layout stage (every pair whole, soft-masked, twins for BOTH), and turns the device
+ * records into the caller's arrays.  A call is three stages -- check, layout, assemble -- around one device function,
+ * cpk_local_pass; no stage touches a device (tests/test_local_cpu.py and tests/test_local_gapped_cpu.py run them with the
+ * model in the pass's place, tests/c/test_local_plan.c and test_local_gapped_plan.c over synthetic passes).
  */
 #include <stdlib.h>
 #include <string.h>
@@ -25,8 +26,8 @@ static CpkAnchorCall anchor_call(const CpkLocalCall *c) {
     return a;
 }
 
-int cpk_local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
-                    const cpecan_local_options *localOptions, CpkAnchorPass *pass, CpkLocalPass *lp) {
+static int local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                       const cpecan_local_options *localOptions, CpkAnchorPass *pass, CpkLocalPass *lp, int admitGapped) {
     if (c->n < 0 || (c->n > 0 && (!c->chains || !c->nChains || !c->runs || !c->nRuns))) {
         cpk_set_error("%s: bad arguments", c->who);
         return CPECAN_EINVAL;
@@ -39,8 +40,8 @@ int cpk_local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_par
     const CpkAnchorCall a = anchor_call(c);
     const int rc = cpk_anchor_check(&a, trim, params, anchorOptions, pass); /* zeroes runs and nRuns */
     if (rc != CPECAN_OK) return rc;
-    if (anchorOptions && anchorOptions->gappedExtension) {
-        cpk_set_error("%s: gappedExtension is not built for local chains", c->who);
+    if (!admitGapped && anchorOptions && anchorOptions->gappedExtension) {
+        cpk_set_error("%s: gappedExtension wants cpecan_find_local_chains_many_gapped", c->who);
         return CPECAN_EINVAL;
     }
     cpecan_local_options def;
@@ -64,6 +65,30 @@ int cpk_local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_par
     lp->maxChains = localOptions->maxChains;
     lp->minChainScore = localOptions->minChainScore ? localOptions->minChainScore : pass->prm.hspThreshold;
     return CPECAN_OK;
+}
+
+int cpk_local_check(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                    const cpecan_local_options *localOptions, CpkAnchorPass *pass, CpkLocalPass *lp) {
+    return local_check(c, trim, params, anchorOptions, localOptions, pass, lp, 0);
+}
+
+/* The check of the entry point that extends chains: gappedExtension = 1 passes, with what cpk_anchor_check holds its yDrop
+ * and gappedMaxDiagonals to. */
+int cpk_local_check_gapped(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params,
+                           const cpecan_anchor_options *anchorOptions, const cpecan_local_options *localOptions, CpkAnchorPass *pass,
+                           CpkLocalPass *lp) {
+    return local_check(c, trim, params, anchorOptions, localOptions, pass, lp, 1);
+}
+
+/* Step 7b on every problem of the list, as step 5b reaches an anchor pass: the flag, and the options' values or what their
+ * zeros stand for, travel with the problems.  The options passed the check. */
+void cpk_local_mark_gapped(CpkAnchorList *top, const cpecan_anchor_options *o) {
+    if (!o || !o->gappedExtension) return;
+    const int32_t diags = o->gappedMaxDiagonals ? o->gappedMaxDiagonals : CPK_ANCHOR_GAPPED_MAX_DIAGS;
+    for (int64_t k = 0; k < top->n; k++) {
+        top->probs[k].flags |= CPK_ANCHOR_GAPPED | (diags << CPK_ANCHOR_DIAGS_SHIFT);
+        top->probs[k].yDrop = o->yDrop ? o->yDrop : CPK_ANCHOR_GAPPED_Y_DROP;
+    }
 }
 
 int cpk_local_layout(const CpkLocalCall *c, CpkAnchorList *top, uint8_t **bytes, int64_t *nBytes, int64_t *nExtra,
@@ -120,13 +145,13 @@ int cpk_local_assemble(const CpkLocalCall *c, const CpkAnchorList *top, const Cp
     return CPECAN_OK;
 }
 
-int cpecan_find_local_chains_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
-                                  const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
-                                  const cpecan_local_options *localOptions, int device, int strandMode,
-                                  cpecan_local_chain **chains, int64_t *nChains, int64_t **runs, int64_t *nRuns,
-                                  cpecan_local_stats *stats) {
-    const CpkLocalCall call = {"cpecan_find_local_chains_many", problems, n, expansion, device, strandMode, chains, nChains, runs, nRuns, stats};
-    const CpkLocalCall *c = &call;
+/* Both entry points: check, device, layout, open, pass, assemble, close. */
+static int find_chains(const CpkLocalCall *c, int64_t trim, const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                       const cpecan_local_options *localOptions, int admitGapped) {
+    const int64_t n = c->n;
+    const int device = c->device;
+    cpecan_local_chain **chains = c->chains;
+    int64_t **runs = c->runs, *nChains = c->nChains, *nRuns = c->nRuns;
     CpkAnchorPass pass;
     CpkLocalPass lp;
     CpkAnchorList top = {0};
@@ -137,7 +162,7 @@ int cpecan_find_local_chains_many(const cpecan_anchor_problem *problems, int64_t
     int32_t *foundRuns = NULL;
     int64_t nBytes = 0, nExtra = 0, nLocal = 0;
     double ms = 0.0;
-    int rc = cpk_local_check(c, trim, params, anchorOptions, localOptions, &pass, &lp);
+    int rc = local_check(c, trim, params, anchorOptions, localOptions, &pass, &lp, admitGapped);
     if (rc != CPECAN_OK) return rc;
     const int nDev = cpk_device_count();
     if (nDev <= 0 || device < 0 || device >= nDev) {
@@ -145,6 +170,7 @@ int cpecan_find_local_chains_many(const cpecan_anchor_problem *problems, int64_t
         return CPECAN_ENODEVICE;
     }
     if ((rc = cpk_local_layout(c, &top, &bytes, &nBytes, &nExtra, &lprobs, &nLocal)) != CPECAN_OK || top.n == 0) goto done;
+    cpk_local_mark_gapped(&top, anchorOptions);
     if ((rc = cpk_anchor_open(&ctx, device, bytes, nBytes, nExtra)) != CPECAN_OK) goto done;
     if ((rc = cpk_local_pass(ctx, &pass, &lp, top.probs, top.n, lprobs, nLocal, &found, &foundRuns, &ms)) != CPECAN_OK) goto done;
     rc = cpk_local_assemble(c, &top, lprobs, nLocal, found, foundRuns, lp.maxChains, ms);
@@ -164,6 +190,24 @@ done:
     free(found);
     free(foundRuns);
     return rc;
+}
+
+int cpecan_find_local_chains_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                  const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                                  const cpecan_local_options *localOptions, int device, int strandMode,
+                                  cpecan_local_chain **chains, int64_t *nChains, int64_t **runs, int64_t *nRuns,
+                                  cpecan_local_stats *stats) {
+    const CpkLocalCall call = {"cpecan_find_local_chains_many", problems, n, expansion, device, strandMode, chains, nChains, runs, nRuns, stats};
+    return find_chains(&call, trim, params, anchorOptions, localOptions, 0);
+}
+
+int cpecan_find_local_chains_many_gapped(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                         const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                                         const cpecan_local_options *localOptions, int device, int strandMode,
+                                         cpecan_local_chain **chains, int64_t *nChains, int64_t **runs, int64_t *nRuns,
+                                         cpecan_local_stats *stats) {
+    const CpkLocalCall call = {"cpecan_find_local_chains_many_gapped", problems, n, expansion, device, strandMode, chains, nChains, runs, nRuns, stats};
+    return find_chains(&call, trim, params, anchorOptions, localOptions, 1);
 }
 
 static int push_op(cpecan_cigar *c, int64_t type, int64_t len) {

@@ -171,3 +171,185 @@ __global__ void __launch_bounds__(256) cpk_local_peel(CpkAnchorProblem *probs, C
         lprobs[blockIdx.x].rounds = rounds;
     }
 }
+
+// ---- step 7b: gapped extension of the chains (include/cpecan_local.h: cpecan_find_local_chains_many_gapped) ----
+// A pass that extends chains runs the peel with trim 0, so the problem's run slots hold every chain's HSP triples in chain
+// order, chain r's at runOff .. runOff + nHsps - 1.  The host lays out the gaps: gapBase[k * maxChains + r] is the first gap
+// of chain r of caller problem k (nHsps + 1 of them; the gaps of a problem follow each other, chain by chain), and gap q has
+// the block slots gapRow[2 * q] onwards, of which those from gapRow[2 * q + 1] on are its left extension's -- the layout of
+// cpk_anchor_gapped, a triple per scratch row of the UNFENCED gap, which the fences only shrink.  The rows of a round lie
+// together, so a launch of round r takes the rows [lo, hi) of it and `trace` holds hi - lo rows.
+
+// One occupied element against the four fences of the gap from (aX, aY) to (bX, bY), in the orientation of the gap's chain.
+struct LocalFences {
+    int xR, yR, xL, yL;  // smallest occupied start in [a, b); largest occupied end in (a, b]
+};
+__device__ __forceinline__ void local_fence(LocalFences &f, int aX, int aY, int bX, int bY, int xs, int xe, int ys, int ye) {
+    if (xs >= aX && xs < bX) f.xR = min(f.xR, xs);
+    if (ys >= aY && ys < bY) f.yR = min(f.yR, ys);
+    if (xe > aX && xe <= bX) f.xL = max(f.xL, xe);
+    if (ye > aY && ye <= bY) f.yL = max(f.yL, ye);
+}
+
+// the chain (0 .. nChains - 1) that HSP t of the problem's list belongs to; nChains <= 16
+__device__ __forceinline__ int local_chain_of(const CpkLocalChain *chains, int nChains, int t) {
+    int j = 0;
+    while (j + 1 < nChains && t >= chains[j + 1].runOff) j++;
+    return j;
+}
+
+// One wave per (caller problem, gap of chain r).  The lanes scan the problem's occupied elements -- the HSPs of every other
+// chain, and the blocks the chains before r kept -- for the four fences, a wave minimum / maximum makes them uniform, and the
+// walks of step 5b run on the fenced sides.  Blocks and counts are this wave's alone; what it reads of other chains was
+// written by the peel or by the launches of earlier rounds on the same stream.
+__global__ void __launch_bounds__(64) cpk_local_gapped(const CpkAnchorProblem *probs, const CpkLocalProblem *lprobs,
+                                                       const CpkLocalChain *chainsAll, const uint8_t *sym, CpkAnchorParams prm,
+                                                       const int32_t *hspAll, const int64_t *gapBase, const int64_t *gapRow,
+                                                       int maxChains, int r, int64_t lo, int64_t hi, uint8_t *trace,
+                                                       int32_t *blocks, int2 *counts) {
+    __shared__ int sc[25];
+    if (threadIdx.x < 25) sc[threadIdx.x] = prm.scores[threadIdx.x];
+    __syncthreads();
+    const int k = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
+    const CpkLocalProblem lp = lprobs[k];
+    if (r >= lp.nChains) return;
+    const CpkLocalChain *chains = chainsAll + (int64_t)k * maxChains;
+    const CpkLocalChain me = chains[r];
+    const int c = me.nHsps;
+    if (g > c) return;
+    const bool minus = me.strand == CPECAN_STRAND_MINUS;
+    CpkAnchorProblem pr = probs[lp.first];
+    if (lp.twins == 2 && minus != ((pr.flags & CPK_ANCHOR_RC_Y) != 0)) pr = probs[lp.first + 1];
+    const int32_t *hsp = hspAll + 3 * probs[lp.first].hspOff, *chain = hsp + 3 * me.runOff;
+    const int lY = pr.lY;
+    const int aX = g ? chain[3 * (g - 1)] + chain[3 * (g - 1) + 2] : 0, aY = g ? chain[3 * (g - 1) + 1] + chain[3 * (g - 1) + 2] : 0;
+    const int bX = g < c ? chain[3 * g] : pr.lX, bY = g < c ? chain[3 * g + 1] : lY;
+    const int m = bX - aX, n = bY - aY;
+    const bool right = g >= 1, left = g < c;
+    const int maxDiags = CPK_ANCHOR_DIAGS(pr.flags);
+    const int rows = min(m + n, maxDiags), rowsR = right ? rows : 0, rowsL = left ? rows : 0;
+    const int64_t q = gapBase[(int64_t)k * maxChains + r] + g;
+    const int64_t row0 = gapRow[2 * q], mid = gapRow[2 * q + 1];
+    // A launch takes the gaps that lie inside its slice.  `mid - row0 != rowsR` is never expected to hold: the host laid the
+    // rows out from the same chain records; it only keeps a wave inside its slots if the two ever disagreed, and the gap then
+    // stays unextended, which the comparison with the model shows.
+    if (rows <= 0 || mid - row0 != rowsR || row0 < lo || row0 + rowsR + rowsL > hi) return;
+
+    LocalFences f = {bX, bY, aX, aY};
+    const CpkLocalChain lastChain = chains[lp.nChains - 1];
+    const int nHspAll = lastChain.runOff + lastChain.nHsps;
+    for (int t = lane; t < nHspAll; t += 64) {  // the chained HSPs of every other chain
+        const int j = local_chain_of(chains, lp.nChains, t);
+        if (j == r) continue;
+        const int x = hsp[3 * t], y = hsp[3 * t + 1], len = hsp[3 * t + 2];
+        const bool same = (chains[j].strand == CPECAN_STRAND_MINUS) == minus;
+        const int ys = same ? y : lY - y - len;
+        local_fence(f, aX, aY, bX, bY, x, x + len, ys, ys + len);
+    }
+    const int64_t gap0 = gapBase[(int64_t)k * maxChains], gapsBefore = gapBase[(int64_t)k * maxChains + r] - gap0;
+    for (int64_t t = lane; t < gapsBefore; t += 64) {  // the blocks kept by the chains before r, gap by gap
+        int j = 0;
+        while (j + 1 < r && gap0 + t >= gapBase[(int64_t)k * maxChains + j + 1]) j++;
+        const bool same = (chains[j].strand == CPECAN_STRAND_MINUS) == minus;
+        const int2 cnt = counts[gap0 + t];
+        const int32_t *b = blocks + 3 * gapRow[2 * (gap0 + t) + 1];
+        for (int u = -cnt.x; u < cnt.y; u++) {
+            const int x = b[3 * u], y = b[3 * u + 1], len = b[3 * u + 2];
+            const int ys = same ? y : lY - y - len;
+            local_fence(f, aX, aY, bX, bY, x, x + len, ys, ys + len);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        f.xR = min(f.xR, __shfl_xor(f.xR, o));
+        f.yR = min(f.yR, __shfl_xor(f.yR, o));
+        f.xL = max(f.xL, __shfl_xor(f.xL, o));
+        f.yL = max(f.yL, __shfl_xor(f.yL, o));
+    }
+    const int mR = f.xR - aX, nR = f.yR - aY, mL = bX - f.xL, nL = bY - f.yL;  // each within 0 .. m or 0 .. n
+
+    uint8_t *traceR = trace + (size_t)(row0 - lo) * 64, *traceL = traceR + (size_t)rowsR * 64;
+    int32_t *blocksR = blocks + 3 * row0, *blocksL = blocks + 3 * mid;
+    AnchorReach R = {0, 0, 0}, L = {0, 0, 0};
+    if (right) R = anchor_gapped_walk(sym, sc, pr.xOff + aX, pr.yOff + aY, 1, mR, nR, pr.yDrop, min(mR + nR, maxDiags), traceR);
+    if (left) L = anchor_gapped_walk(sym, sc, pr.xOff + bX - 1, pr.yOff + bY - 1, -1, mL, nL, pr.yDrop, min(mL + nL, maxDiags), traceL);
+    if (R.i + L.i > m || R.j + L.j > n) {  // 5b's test on the whole gap: the smaller best goes, the left one on a tie
+        if (R.best < L.best) R.best = 0;
+        else L.best = 0;
+    }
+    __threadfence();  // the bytes other lanes stored are read below
+    const int kR = R.best > 0 ? anchor_gapped_blocks(traceR, R, false, aX, aY, blocksR, rows) : 0;
+    const int kL = L.best > 0 ? anchor_gapped_blocks(traceL, L, true, bX, bY, blocksL, rows) : 0;
+    if (lane == 0) counts[q] = make_int2(kR, kL);
+}
+
+// Assembly, merging and step 5 of one chain, as cpk_anchor_assemble does them for a problem: per gap the right blocks, the
+// left blocks, then the next HSP.  out == nullptr counts only.  rect: the start of the first merged block and the end of the
+// last, untrimmed.
+__device__ __forceinline__ int local_chain_runs(const int32_t *chain, int c, int64_t gapFirst, const int64_t *gapRow,
+                                                const int32_t *blocks, const int2 *counts, int trim, int32_t *out, int4 *rect) {
+    int nRuns = 0, x = 0, y = 0, len = 0;
+    bool first = true;
+    auto flush = [&]() {
+        if (len > 0 && first) rect->x = x, rect->y = y, first = false;
+        if (len > 0) rect->z = x + len, rect->w = y + len;
+        if (len - 2 * trim > 0) {
+            if (out) {
+                out[3 * nRuns] = x + trim;
+                out[3 * nRuns + 1] = y + trim;
+                out[3 * nRuns + 2] = len - 2 * trim;
+            }
+            nRuns++;
+        }
+    };
+    auto put = [&](int bx, int by, int blen) {
+        if (len > 0 && x + len == bx && y + len == by) {
+            len += blen;
+        } else {
+            flush();
+            x = bx, y = by, len = blen;
+        }
+    };
+    for (int g = 0; g <= c; g++) {
+        const int2 cnt = counts[gapFirst + g];
+        const int32_t *b = blocks + 3 * gapRow[2 * (gapFirst + g) + 1];
+        for (int t = -cnt.x; t < cnt.y; t++) put(b[3 * t], b[3 * t + 1], b[3 * t + 2]);  // the right ones end where the left ones start
+        if (g < c) put(chain[3 * g], chain[3 * g + 1], chain[3 * g + 2]);
+    }
+    flush();
+    return nRuns;
+}
+
+// One wave per caller problem, lane j for chain j: count the chain's runs, a prefix sum over the lanes, write them.  The
+// runs of problem k go to runBase[k] of runsOut, chain by chain; the chain records get their rectangle, runOff and nRuns, the
+// problem its run count.
+__global__ void __launch_bounds__(64) cpk_local_gapped_assemble(const CpkAnchorProblem *probs, CpkLocalProblem *lprobs,
+                                                                CpkLocalChain *chainsAll, const int32_t *hspAll,
+                                                                const int64_t *gapBase, const int64_t *gapRow, const int64_t *runBase,
+                                                                const int32_t *blocks, const int2 *counts, int32_t *runsOut,
+                                                                int maxChains, int trim) {
+    const int k = blockIdx.x, j = threadIdx.x;
+    const CpkLocalProblem lp = lprobs[k];
+    const bool mine = j < lp.nChains;
+    CpkLocalChain *rec = chainsAll + (int64_t)k * maxChains + (mine ? j : 0);
+    const CpkLocalChain me = *rec;
+    const int32_t *chain = hspAll + 3 * (probs[lp.first].hspOff + me.runOff);
+    const int64_t gapFirst = gapBase[(int64_t)k * maxChains + (mine ? j : 0)];
+    int4 rect = make_int4(0, 0, 0, 0);
+    const int made = mine ? local_chain_runs(chain, me.nHsps, gapFirst, gapRow, blocks, counts, trim, nullptr, &rect) : 0;
+    int before = 0, total = 0;
+    for (int o = 0; o < CPK_LOCAL_MAX_CHAINS; o++) {
+        const int v = __shfl(made, o);
+        before += o < j ? v : 0;
+        total += v;
+    }
+    if (mine) {
+        local_chain_runs(chain, me.nHsps, gapFirst, gapRow, blocks, counts, trim, runsOut + 3 * (runBase[k] + before), &rect);
+        rec->x0 = rect.x;
+        rec->y0 = rect.y;
+        rec->x1 = rect.z;
+        rec->y1 = rect.w;
+        rec->runOff = before;
+        rec->nRuns = made;
+    }
+    if (j == 0) lprobs[k].nRuns = total;
+}

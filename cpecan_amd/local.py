@@ -13,7 +13,8 @@ from . import api
 from . import realign
 
 # Every symbol include/cpecan_local.h declares (checked by tests/test_local_cpu.py).
-EXPORTS = ["cpecan_local_options_default", "cpecan_find_local_chains_many", "cpecan_cigar_from_local_chain"]
+EXPORTS = ["cpecan_local_options_default", "cpecan_find_local_chains_many", "cpecan_find_local_chains_many_gapped",
+           "cpecan_cigar_from_local_chain"]
 
 MAX_CHAINS = 16
 
@@ -52,6 +53,7 @@ def _lib():
             C.POINTER(api.AnchorProblem), C.c_int64, C.c_int64, C.c_int64, C.POINTER(api.AnchorParams),
             C.POINTER(api.AnchorOptions), C.POINTER(LocalOptions), C.c_int, C.c_int, C.POINTER(C.POINTER(LocalChain)), i64p,
             C.POINTER(i64p), i64p, C.POINTER(LocalStats)]
+        L.cpecan_find_local_chains_many_gapped.argtypes = L.cpecan_find_local_chains_many.argtypes
         L.cpecan_cigar_from_local_chain.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(LocalChain), i64p,
                                                     C.POINTER(realign._Cigar)]
         _bound = True
@@ -70,21 +72,29 @@ def local_options(**overrides):
 
 
 def find_local_chains(problems, trim=api.CONSTRAINT_DIAGONAL_TRIM, expansion=20, params=None, anchor_options=None, options=None,
-                      device=0, strand="both"):
+                      device=0, strand="both", gapped=False):
     """cpecan_find_local_chains_many on (sX, sY, ...) tuples: ([chains per problem], [statistics dict per problem]).  A chain
     is a dict: strand "plus" / "minus", score, nHsps, the rectangle x0, x1, y0, y1 and runs, int64[n, 4] of (x, y, length,
-    expansion); rectangle and runs of a minus chain are in the coordinates of (sX, reverse_complement(sY))."""
+    expansion); rectangle and runs of a minus chain are in the coordinates of (sX, reverse_complement(sY)).
+    gapped: cpecan_find_local_chains_many_gapped instead, which extends every chain into its gaps and outwards (DESIGN.md
+    section 7, step 7b) as anchor_options' gappedExtension, yDrop and gappedMaxDiagonals say; without anchor_options that is
+    gappedExtension = 1 at the defaults."""
     L = _lib()
+    entry, name = L.cpecan_find_local_chains_many, "cpecan_find_local_chains_many"
+    if gapped:
+        entry, name = L.cpecan_find_local_chains_many_gapped, "cpecan_find_local_chains_many_gapped"
+        if anchor_options is None:
+            anchor_options = api.anchor_options(gappedExtension=1)
     arr, n, keep = api._anchor_problems(problems)
     i64p = C.POINTER(C.c_int64)
     chains, nChains = (C.POINTER(LocalChain) * max(1, n))(), (C.c_int64 * max(1, n))()
     runs, nRuns = (i64p * max(1, n))(), (C.c_int64 * max(1, n))()
     stats = (LocalStats * max(1, n))()
     try:
-        api._check(L.cpecan_find_local_chains_many(
+        api._check(entry(
             arr, n, trim, expansion, C.byref(params) if params is not None else None,
             C.byref(anchor_options) if anchor_options is not None else None, C.byref(options) if options is not None else None,
-            device, api._strand_mode(strand), chains, nChains, runs, nRuns, stats), "cpecan_find_local_chains_many")
+            device, api._strand_mode(strand), chains, nChains, runs, nRuns, stats), name)
         out = []
         for i in range(n):
             all_runs = np.zeros((0, 4), dtype=np.int64)
@@ -121,20 +131,22 @@ def cigar_of_chain(contig1, contig2, lY, chain):
 
 
 def local_cigars(targets, queries, trim=0, expansion=20, params=None, anchor_options=None, options=None, device=0,
-                 strand="both"):
+                 strand="both", gapped=False):
     """The cigars of every chain of every (target, query) pair from ONE find_local_chains call: queries outer, targets inner,
-    the chains of a pair in round order; a chain without runs has no cigar.  targets, queries: {name: sequence}."""
+    the chains of a pair in round order; a chain without runs has no cigar.  targets, queries: {name: sequence}.  gapped: as
+    in find_local_chains."""
     pairs = [(t, q) for q in queries for t in targets]
     chains, _ = find_local_chains([(targets[t], queries[q]) for t, q in pairs], trim, expansion, params, anchor_options, options,
-                                  device, strand)
+                                  device, strand, gapped)
     return [cigar_of_chain(t, q, len(queries[q]), c) for (t, q), mine in zip(pairs, chains) for c in mine if len(c["runs"])]
 
 
 def align_local(targets, queries, sM=None, realign_options=None, trim=0, expansion=20, params=None, anchor_options=None,
-                options=None, device=0, strand="both"):
+                options=None, device=0, strand="both", gapped=False):
     """chains -> cigars -> Realigner.realign: one anchor call and one realign call; the realigned realign.Cigar list in the
-    order of local_cigars.  realign_options: a realign.RealignOptions (default: cPecanRealign's)."""
-    cigars = local_cigars(targets, queries, trim, expansion, params, anchor_options, options, device, strand)
+    order of local_cigars.  realign_options: a realign.RealignOptions (default: cPecanRealign's).  gapped: as in
+    find_local_chains."""
+    cigars = local_cigars(targets, queries, trim, expansion, params, anchor_options, options, device, strand, gapped)
     with realign.Realigner(sM, realign_options, device) as r:
         for name, seq in list(targets.items()) + list(queries.items()):
             r.add_sequence(name, seq)

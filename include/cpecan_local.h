@@ -1,6 +1,6 @@
 /*
  * cpecan_local.h -- local chains: the K best mutually disjoint colinear chains of a pair, over one or both orientations
- * (DESIGN.md section 7, step 7), and the cigars that hand them to the realigner of cpecan_realign.h.
+ * (DESIGN.md section 7, steps 7 and 7b), and the cigars that hand them to the realigner of cpecan_realign.h.
  *
  * The reference never finds these itself: lastz hands cPecanRealign local alignments on both strands, many per pair, and
  * cPecanRealign realigns each (cPecanRealign.c:509-600).  cpecan_find_anchor_runs_many (cpecan_hip.h) keeps ONE chain per
@@ -19,7 +19,8 @@
  *              Otherwise record the chain, then kill every live HSP of either orientation whose X interval meets the X
  *              interval of a chained HSP or whose forward-Y interval meets the forward-Y interval of one.
  * So chain scores never increase, and all chained HSPs of a problem are pairwise disjoint on X and on forward Y.
- * Step 6 (the recursion into gaps) is not run, and cpecan_anchor_options.gappedExtension is refused here.
+ * Step 6 (the recursion into gaps) is not run.  cpecan_anchor_options.gappedExtension is refused by
+ * cpecan_find_local_chains_many and served by cpecan_find_local_chains_many_gapped (step 7b, below).
  */
 #ifndef CPECAN_LOCAL_H_
 #define CPECAN_LOCAL_H_
@@ -38,7 +39,8 @@ typedef struct cpecan_local_options {
 /* maxChains 1, minChainScore 0 */
 int cpecan_local_options_default(cpecan_local_options *o);
 
-/* One chain.  The rectangle [x0, x1) x [y0, y1) goes from the start of its first HSP to the end of its last; it and the runs
+/* One chain.  The rectangle [x0, x1) x [y0, y1) goes from the start of its first HSP to the end of its last (of its first and
+ * last merged block where chains are extended); it and the runs
  * are in the coordinates of the chain's orientation: (X, Y) for plus, (X, rc(Y)) for minus.  The runs are step 5 on the
  * chain's HSPs with the call's trim: quadruples runOff .. runOff + nRuns - 1 of the problem's run array.  A chain whose runs
  * all trim away is still reported, with nRuns 0. */
@@ -63,13 +65,35 @@ typedef struct cpecan_local_stats {
  * runs[i]: a malloc'd array of nRuns[i] quadruples (x, y, length, expansion); both are released with cpecan_free.  stats: n
  * records, or NULL.  params, anchorOptions, localOptions: NULL = the defaults.  strandMode: CPECAN_STRAND_*.
  * CPECAN_EINVAL, before a device is looked for: what cpecan_find_anchor_runs_many_with_options refuses; maxChains outside
- * 1 .. 16; minChainScore negative, or positive and under hspThreshold; anchorOptions->gappedExtension = 1 (extending K chains
- * into each other's gaps needs a rule of its own; not built); a nonzero reserved word.  CPECAN_ENODEVICE after those. */
+ * 1 .. 16; minChainScore negative, or positive and under hspThreshold; anchorOptions->gappedExtension = 1 (the entry point
+ * below takes it); a nonzero reserved word.  CPECAN_ENODEVICE after those. */
 int cpecan_find_local_chains_many(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
                                   const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
                                   const cpecan_local_options *localOptions, int device, int strandMode,
                                   cpecan_local_chain **chains, int64_t *nChains, int64_t **runs, int64_t *nRuns,
                                   cpecan_local_stats *stats);
+
+/* The same, and with anchorOptions->gappedExtension = 1 every chain is extended into the gaps between its HSPs and outwards
+ * from its ends.  After the last round the chains are extended in round order.  When chain r
+ * is extended the occupied set is every chained HSP of every other chain of the problem, later rounds included, and every
+ * extension block that chains 1 .. r - 1 kept, each with its X interval and its forward-Y interval (above), mapped into the
+ * orientation of chain r.  The gaps are those of step 5b (cpecan_hip.h) on the chain's HSPs in its own orientation, the end
+ * gaps reaching to (0, 0) and (lX, lY).  A right extension runs from the gap's lower corner up to the smallest occupied
+ * start inside the gap on either axis, a left extension from the upper corner down to the largest occupied end; the walk
+ * is step 5b's -- band, gap costs, tie rules, yDrop, gappedMaxDiagonals on the fenced sides -- and so is the test on two
+ * extensions of one gap, on the whole gap.  Blocks are assembled, merged and trimmed as in 5b.
+ * So all untrimmed blocks of a problem are pairwise disjoint on X and on forward Y, a chain's blocks ascend on both axes of
+ * its orientation, and every chained HSP lies inside a block of its chain.  strand, score and nHsps of a record and the
+ * statistics are those of cpecan_find_local_chains_many; the rectangle goes from the start of the chain's first merged block
+ * to the end of its last, and nRuns may exceed nHsps.  One chain on the plus strand has the runs of
+ * cpecan_find_anchor_runs_once(softMask = 1) with the same options.  With gappedExtension = 0 the call is
+ * cpecan_find_local_chains_many.  yDrop, gappedMaxDiagonals: meaning, defaults and CPECAN_EINVAL cases as in
+ * cpecan_find_anchor_runs_many_with_options; every other refusal as above, before a device is looked for. */
+int cpecan_find_local_chains_many_gapped(const cpecan_anchor_problem *problems, int64_t n, int64_t trim, int64_t expansion,
+                                         const cpecan_anchor_params *params, const cpecan_anchor_options *anchorOptions,
+                                         const cpecan_local_options *localOptions, int device, int strandMode,
+                                         cpecan_local_chain **chains, int64_t *nChains, int64_t **runs, int64_t *nRuns,
+                                         cpecan_local_stats *stats);
 
 /* The cigar of a chain; touches no device.  runs: the problem's run array, of which the chain's runOff and nRuns name a part
  * (a caller may pass a copy of the chain that names fewer).  The cigar spans from the start of the first of those runs to
