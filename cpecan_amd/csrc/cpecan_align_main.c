@@ -23,6 +23,10 @@
  * --local --extendChains [--chainYDrop N]: the chains are extended into their gaps and outwards before they become cigars
  * (cpecan_find_local_chains_many_gapped), as lastz's cigars are gapped; --chainYDrop sets what
  * ends such an extension (default 9400).  Both need --local, --chainYDrop needs --extendChains.
+ * --viterbi: anchors are found as above (--strand, --seedTransitions, --gapped and --diagonalExpansion apply), then all pairs go
+ * through one cpecan_viterbi object (include/cpecan_viterbi.h) instead of the DP batch, both ends ragged: a pair's cigar is
+ * made of the match steps of its most probable state path (cpecan_viterbi_pairs), columns between two regions unaligned, and
+ * its score is the path's log-probability.  Refused with --local and with --adaptiveBand.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <ctype.h>
@@ -33,6 +37,7 @@
 
 #include "cpecan_local.h"
 #include "cpecan_realign.h"
+#include "cpecan_viterbi.h"
 
 typedef struct {
     char *name, *seq;
@@ -58,7 +63,9 @@ static void usage(void) {
                     "   --maxChains K (1..16, default 1)  --minChainScore S (default: the HSP threshold, 800); both need --local;\n"
                     "   --local does not go with --gapped or --adaptiveBand\n"
                     "   --extendChains (with --local: gapped extension of every chain into its gaps and outwards, each chain kept clear\n"
-                    "   of the others)  --chainYDrop N (with --extendChains; default 9400)\n");
+                    "   of the others)  --chainYDrop N (with --extendChains; default 9400)\n"
+                    "--viterbi (the most probable state path of every pair instead of its posterior pairs; the cigar's score is the\n"
+                    "   path's log-probability; does not go with --local or --adaptiveBand)\n");
 }
 
 static int fail(const char *what) {
@@ -197,6 +204,62 @@ static int align_pairs(const cpecan_model *model, const cpecan_params *params, d
     return status;
 }
 
+/* --viterbi: all n pairs through one cpecan_viterbi object, both ends ragged; texts[i] receives pair i's cigar. */
+static int viterbi_pairs(const cpecan_model *model, const cpecan_params *params, int device, const cpecan_problem_runs *pr,
+                         const int32_t *yMinus, const Records *targets, const Records *queries, int64_t n, char **texts) {
+    int status = 0;
+    cpecan_viterbi *v = NULL;
+    if (cpecan_viterbi_create(&v, model, params, device) != CPECAN_OK) return fail("viterbi");
+    for (int64_t i = 0; status == 0 && i < n; i++) {
+        int64_t nAnchors = 0;
+        for (int64_t q = 0; q < pr[i].nRuns; q++) nAnchors += pr[i].runs[4 * q + 2];
+        int64_t *a = malloc(sizeof *a * 3 * (size_t)(nAnchors ? nAnchors : 1));
+        char *rc = yMinus[i] ? malloc((size_t)(pr[i].lY ? pr[i].lY : 1)) : NULL;
+        if (!a || (yMinus[i] && !rc)) status = 1;
+        else if (rc && cpecan_reverse_complement(pr[i].sY, pr[i].lY, rc) != CPECAN_OK) status = fail("reverse complement");
+        for (int64_t q = 0, k = 0; status == 0 && q < pr[i].nRuns; q++)
+            for (int64_t j = 0; j < pr[i].runs[4 * q + 2]; j++, k++) {
+                a[3 * k] = pr[i].runs[4 * q] + j;
+                a[3 * k + 1] = pr[i].runs[4 * q + 1] + j;
+                a[3 * k + 2] = pr[i].runs[4 * q + 3];
+            }
+        if (status == 0 && cpecan_viterbi_add(v, pr[i].sX, pr[i].lX, rc ? rc : pr[i].sY, pr[i].lY, a, nAnchors, 1, 1) != i) status = fail("add");
+        free(a);
+        free(rc);
+    }
+    if (status == 0 && cpecan_viterbi_run(v) != CPECAN_OK) status = fail("run");
+    for (int64_t i = 0; status == 0 && i < n; i++) {
+        cpecan_viterbi_result_t res;
+        if (cpecan_viterbi_result(v, i, &res) != CPECAN_OK) {
+            status = fail("result");
+            break;
+        }
+        const int64_t cnt = cpecan_viterbi_pairs(&res, NULL, 0);
+        int64_t *xy = malloc(sizeof *xy * 2 * (size_t)(cnt > 0 ? cnt : 1));
+        cpecan_cigar c;
+        memset(&c, 0, sizeof c);
+        if (!xy || cnt < 0 || cpecan_viterbi_pairs(&res, xy, cnt) != cnt) status = 1;
+        else if (cpecan_cigar_from_aligned_pairs_stranded(targets->r[i % targets->n].name, queries->r[i / targets->n].name, res.logP,
+                                                          pr[i].lX, pr[i].lY, !yMinus[i], xy, cnt, &c) != CPECAN_OK) {
+            status = fail("cigar");
+        } else {
+            const int64_t need = cpecan_cigar_format(&c, NULL, 0) + 1;
+            char *text = malloc((size_t)need);
+            if (text) {
+                cpecan_cigar_format(&c, text, need);
+                free(texts[i]);
+                texts[i] = text;
+            } else {
+                status = 1;
+            }
+            cpecan_cigar_clear(&c);
+        }
+        free(xy);
+    }
+    cpecan_viterbi_destroy(v);
+    return status;
+}
+
 /* --local: chains -> cigars -> one realign call; prints the realigned cigars. */
 static int run_local(const cpecan_model *model, const cpecan_anchor_problem *ap, int64_t n, const Records *targets,
                      const Records *queries, int64_t expansion, int64_t runExpansion, double gapGamma,
@@ -271,7 +334,7 @@ int main(int argc, char **argv) {
     int haveAdaptive = 0, haveMinEdge = 0;
     int localMode = 0, haveMaxChains = 0, haveMinChainScore = 0;
     long long maxChains = 1, minChainScore = 0, chainYDrop = 0;
-    int extendChains = 0, haveChainYDrop = 0;
+    int extendChains = 0, haveChainYDrop = 0, viterbiMode = 0;
     static struct option longOpts[] = {{"help", no_argument, 0, 'h'},
                                        {"loadHmm", required_argument, 0, 'y'},
                                        {"device", required_argument, 0, 'g'},
@@ -288,6 +351,7 @@ int main(int argc, char **argv) {
                                        {"minChainScore", required_argument, 0, 1004},
                                        {"extendChains", no_argument, 0, 1005},
                                        {"chainYDrop", required_argument, 0, 1006},
+                                       {"viterbi", no_argument, 0, 1007},
                                        {0, 0, 0, 0}};
     for (int key; (key = getopt_long(argc, argv, "hy:g:s:tT:GY:r:", longOpts, NULL)) != -1;) {
         switch (key) {
@@ -324,6 +388,7 @@ int main(int argc, char **argv) {
         case 1004: if (sscanf(optarg, "%lld", &minChainScore) != 1 || minChainScore < 1 || minChainScore > 0x7fffffffLL) { usage(); return 1; } haveMinChainScore = 1; break;
         case 1005: extendChains = 1; break;
         case 1006: if (sscanf(optarg, "%lld", &chainYDrop) != 1 || chainYDrop < 1 || chainYDrop > 0x7fffffffLL) { usage(); return 1; } haveChainYDrop = 1; break;
+        case 1007: viterbiMode = 1; break;
         default: usage(); return 1;
         }
     }
@@ -353,6 +418,10 @@ int main(int argc, char **argv) {
     }
     if (localMode && (gapped || haveAdaptive)) {
         fprintf(stderr, "cpecan_align: --local does not go with --gapped or --adaptiveBand\n");
+        return 1;
+    }
+    if (viterbiMode && (localMode || haveAdaptive)) {
+        fprintf(stderr, "cpecan_align: --viterbi does not go with --local or --adaptiveBand\n");
         return 1;
     }
     if (argc - optind != 2) { /* cPecanAlign.c:93-96 */
@@ -436,8 +505,9 @@ int main(int argc, char **argv) {
             yMinus[i] = strands[i].strand == CPECAN_STRAND_MINUS;
             idx[i] = i;
         }
-        status = align_pairs(&model, &params, gapGamma, (int)device, pr, yMinus, &targets, &queries, idx, n, texts,
-                             haveAdaptive ? edgeSum : NULL);
+        status = viterbiMode ? viterbi_pairs(&model, &params, (int)device, pr, yMinus, &targets, &queries, n, texts)
+                             : align_pairs(&model, &params, gapGamma, (int)device, pr, yMinus, &targets, &queries, idx, n, texts,
+                                           haveAdaptive ? edgeSum : NULL);
     }
     for (long long k = 1; status == 0 && k <= adaptiveBand; k++) { /* the pairs flagged in round k - 1, the expansion doubled */
         int64_t m = 0;

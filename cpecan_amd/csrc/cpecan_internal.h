@@ -567,6 +567,44 @@ int cpk_dense_run(int device, const CpkModel *model, const CpkDenseJob *job, dou
 void cpk_kernel_model(const cpecan_model *m, double threshold, CpkModel *k);
 uint8_t cpk_symbol_of(unsigned char c);
 
+/* ---- Viterbi decoding (cpk_viterbi.inl; host side in cpecan_viterbi.c) ---- */
+#define CPK_VIT_BLOCK_DIAGS 64   /* diagonals whose pointer bytes the traceback stages in LDS at a time */
+#define CPK_VIT_LDS_MAX_WIDTH 256 /* CPECAN_VITERBI_LDS_MAX_WIDTH */
+/* One anti-diagonal of a region: its band and the band cells on the region's earlier diagonals. */
+typedef struct {
+    int32_t xmyL, width;
+    int64_t cellOff;
+} CpkVitDiag;
+/* One region of a launch.  All offsets are into the launch's own arrays. */
+typedef struct {
+    int64_t symX, symY; /* first byte of the padded symbol strings (symbol[0] = N, symbol[i] = base i - 1, symbol[l + 1] = N) */
+    int64_t diagOff;    /* first of the region's lX + lY + 1 CpkVitDiag */
+    int64_t ptrBase;    /* first of its pointer bytes, one per band cell */
+    int64_t rollBase;   /* first double of its three global rolling rows (3 * S * maxWidth) */
+    int64_t opBase;     /* first (state, length) pair of its ops: room for lX + lY pairs, written last run first */
+    int32_t lX, lY;
+    int32_t raggedLeft, raggedRight;
+    int32_t maxWidth, pad;
+} CpkVitRegion;
+/* What the kernels leave per region. */
+typedef struct {
+    double logP;
+    int32_t startState, endState, nOps, pad;
+} CpkVitOut;
+/* The regions of one launch: the sweep over `order[0 .. nLds)` with the rows in LDS and over `order[nLds .. nRegions)` with
+ * the rows in global memory, then the traceback over all.  Host arrays in, host arrays out (out: nRegions; ops: 2 * nOpPairs). */
+typedef struct {
+    const CpkVitRegion *regions;
+    const CpkVitDiag *diags;
+    const uint8_t *symbols;
+    const int32_t *order;
+    int64_t nRegions, nLds, nDiags, nSymbolBytes, nPtrBytes, nRollDoubles, nOpPairs;
+    int32_t ldsMaxWidth; /* widest diagonal among the LDS-form regions */
+    CpkVitOut *out;
+    int32_t *ops;
+} CpkVitJob;
+int cpk_viterbi_launch(int device, const CpkModel *model, const CpkVitJob *job, double *sweepMs, double *tracebackMs);
+
 #ifdef __cplusplus
 }
 #endif

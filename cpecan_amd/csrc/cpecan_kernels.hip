@@ -83,6 +83,7 @@ extern "C" const char *cpk_last_error(void) { return g_err; }
 #include "cpk_anchor.inl"
 #include "cpk_local.inl"
 #include "cpk_dense.inl"
+#include "cpk_viterbi.inl"
 
 // ------------------------------------------------------------------------------------------------
 // host side of the HIP TU: memory, launch, timing
@@ -1933,6 +1934,60 @@ extern "C" int cpk_dense_run(int device, const CpkModel *model, const CpkDenseJo
     for (int i = 0; i < 8; i++) cache_free(device, dp[i], bytes[i]);
     if (e != hipSuccess) {
         cpk_set_error("cpk_dense_run: %s", hipGetErrorString(e));
+        return CPECAN_EHIP;
+    }
+    return CPECAN_OK;
+}
+
+// Viterbi decoding (cpk_viterbi.inl): one launch of a cpecan_viterbi run -- blocking copies around the sweep (its LDS-form and
+// its global-form regions) and the traceback on the null stream.  The caller has checked that a device exists.
+extern "C" int cpk_viterbi_launch(int device, const CpkModel *model, const CpkVitJob *j, double *sweepMs, double *tracebackMs) {
+    const int nDev = cpk_device_count();
+    if (nDev <= 0 || device < 0 || device >= nDev) {
+        cpk_set_error("no usable HIP device (count=%d, requested=%d): the HIP path has no CPU fallback", nDev, device);
+        return CPECAN_ENODEVICE;
+    }
+    if (j->nRegions <= 0) return CPECAN_OK;
+    CPK_ON_DEVICE(device);
+    const int S = model->nStates;
+    const size_t bytes[8] = {sizeof(CpkVitRegion) * (size_t)j->nRegions, sizeof(CpkVitDiag) * (size_t)j->nDiags, (size_t)j->nSymbolBytes,
+                             sizeof(int32_t) * (size_t)j->nRegions, (size_t)j->nPtrBytes, sizeof(double) * (size_t)j->nRollDoubles,
+                             sizeof(CpkVitOut) * (size_t)j->nRegions, sizeof(int32_t) * 2 * (size_t)j->nOpPairs};
+    const void *src[4] = {j->regions, j->diags, j->symbols, j->order};
+    void *dp[8] = {};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 8 && e == hipSuccess; i++) e = cache_alloc(device, &dp[i], bytes[i] ? bytes[i] : 8);
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMemcpy(dp[i], src[i], bytes[i], hipMemcpyHostToDevice);
+    hipEvent_t ev[3] = {};
+    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+    if (e == hipSuccess) {
+        VitArgs a = {(const CpkVitRegion *)dp[0], (const CpkVitDiag *)dp[1], (const uint8_t *)dp[2], (const int32_t *)dp[3],
+                     (uint8_t *)dp[4], (double *)dp[5], (CpkVitOut *)dp[6], (int32_t *)dp[7], j->ldsMaxWidth};
+        const size_t ldsRows = sizeof(double) * (kVitEm + (size_t)3 * S * (size_t)j->ldsMaxWidth), ldsNone = sizeof(double) * kVitEm;
+        (void)hipEventRecord(ev[0], nullptr);
+        if (j->nLds > 0) hipLaunchKernelGGL(cpecan_viterbi_sweep<true>, dim3((unsigned)j->nLds), dim3(CPK_WAVE), ldsRows, nullptr, *model, a);
+        if (j->nRegions > j->nLds) {
+            VitArgs g = a;
+            g.order = a.order + j->nLds;
+            hipLaunchKernelGGL(cpecan_viterbi_sweep<false>, dim3((unsigned)(j->nRegions - j->nLds)), dim3(CPK_WAVE), ldsNone, nullptr, *model, g);
+        }
+        (void)hipEventRecord(ev[1], nullptr);
+        hipLaunchKernelGGL(cpecan_viterbi_traceback, dim3((unsigned)j->nRegions), dim3(CPK_WAVE), 0, nullptr, S, a);
+        e = hipGetLastError();
+        (void)hipEventRecord(ev[2], nullptr);
+    }
+    if (e == hipSuccess) e = hipMemcpy(j->out, dp[6], bytes[6], hipMemcpyDeviceToHost);  // waits for the kernels (null stream)
+    if (e == hipSuccess && bytes[7]) e = hipMemcpy(j->ops, dp[7], bytes[7], hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+        float ms = 0.f;
+        if (sweepMs && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *sweepMs = ms;
+        if (tracebackMs && hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) *tracebackMs = ms;
+    }
+    for (int i = 0; i < 3; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    for (int i = 0; i < 8; i++) cache_free(device, dp[i], bytes[i] ? bytes[i] : 8);
+    if (e != hipSuccess) {
+        cpk_set_error("cpk_viterbi_launch: %s", hipGetErrorString(e));
         return CPECAN_EHIP;
     }
     return CPECAN_OK;
