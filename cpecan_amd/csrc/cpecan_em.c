@@ -14,6 +14,7 @@
 #include <time.h>
 
 #include "cpecan_internal.h"
+#include "cpecan_viterbi.h"
 
 #define EM_PSEUDO 0.000000000001 /* hmm_constructEmpty's pseudo-count of one cPecanRealign --outputExpectations job */
 
@@ -255,6 +256,9 @@ struct cpecan_em_trainer {
     /* cpecan_em_trainer_alignments: the anchors of the last E-step of the last trial (malloc'd; NULL before a training) */
     int64_t *lastRuns, *lastNRuns;
     int64_t lastN;
+    /* cpecan_em_trainer_set_viterbi_training: the E-step counts along the most probable paths */
+    int viterbiTraining;
+    double viterbiPseudoCount;
 };
 
 static char *dup_str(const char *s) {
@@ -351,6 +355,42 @@ int cpecan_em_trainer_set_concurrent_trials(cpecan_em_trainer *t, int n) {
         return CPECAN_EINVAL;
     }
     t->concurrentTrials = n;
+    return CPECAN_OK;
+}
+
+/* What Viterbi training does not go with; checked where it is switched on and again where a training starts, before any
+ * device is looked for. */
+static int viterbi_training_refusal(const cpecan_em_trainer *t) {
+    if (!t->viterbiTraining) return CPECAN_OK;
+    if (t->opt.updateTheBand) {
+        cpk_set_error("Viterbi training does not go with updateTheBand: the realignment between iterations is not built for it");
+        return CPECAN_EINVAL;
+    }
+    if (t->concurrentTrials > 1) {
+        cpk_set_error("Viterbi training with %d concurrent trials: one resident Viterbi object serves one model at a time", t->concurrentTrials);
+        return CPECAN_EINVAL;
+    }
+    if (cpk_realigner_device_count(t->r) > 1) {
+        cpk_set_error("Viterbi training on %d devices: the resident Viterbi object lives on one", cpk_realigner_device_count(t->r));
+        return CPECAN_EINVAL;
+    }
+    return CPECAN_OK;
+}
+
+int cpecan_em_trainer_set_viterbi_training(cpecan_em_trainer *t, int on, double pseudoCount) {
+    if (!t) return CPECAN_EINVAL;
+    if (!isfinite(pseudoCount) || pseudoCount < 0.0) {
+        cpk_set_error("Viterbi training: a pseudo-count of %g, it must be finite and >= 0", pseudoCount);
+        return CPECAN_EINVAL;
+    }
+    const int before = t->viterbiTraining;
+    t->viterbiTraining = on != 0;
+    const int rc = viterbi_training_refusal(t);
+    if (rc != CPECAN_OK) {
+        t->viterbiTraining = before;
+        return rc;
+    }
+    t->viterbiPseudoCount = pseudoCount;
     return CPECAN_OK;
 }
 
@@ -470,6 +510,30 @@ static int run_trial(cpecan_em_trainer *t, cpecan_expect_set *first, const cpeca
     return rc;
 }
 
+/* One trial of Viterbi training (hard EM): run_trial, except that the E-step decodes the most probable path of every sampled
+ * alignment under the current model and counts along it (cpecan_viterbi_run_counts over the resident object vit), on top of
+ * the pseudo-count in every bin.  The running likelihood is the sum of the paths' log-probabilities. */
+static int run_trial_viterbi(cpecan_em_trainer *t, cpecan_viterbi *vit, cpecan_hmm *h, double *running, const char *path) {
+    int rc = cpecan_em_write_model(h, NULL, 0, path);
+    cpecan_model m;
+    if (rc == CPECAN_OK)
+        rc = t->opt.useDefaultModelAsStart ? cpecan_model_default(&m, t->type) : cpecan_model_from_hmm(&m, h);
+    for (int it = 0; rc == CPECAN_OK && it < t->opt.iterations; it++) {
+        cpecan_hmm acc;
+        cpecan_viterbi_counts counts;
+        rc = cpecan_hmm_init(&acc, t->type, t->viterbiPseudoCount);
+        if (rc == CPECAN_OK) rc = cpecan_viterbi_set_model(vit, &m);
+        if (rc == CPECAN_OK) rc = cpecan_viterbi_run_counts(vit, &counts);
+        if (rc == CPECAN_OK) rc = cpecan_viterbi_counts_add_to_hmm(&counts, &acc);
+        if (rc != CPECAN_OK) break;
+        m_step(t, &acc, h, &running[it]);
+        rc = cpecan_em_write_model(h, NULL, 0, path);
+        if (rc == CPECAN_OK) rc = cpecan_model_from_hmm(&m, h);
+    }
+    if (rc == CPECAN_OK) rc = cpecan_em_write_model(h, running, t->opt.iterations, path);
+    return rc;
+}
+
 /* A round of n trials side by side: every iteration is ONE cpecan_expect_set_run_models over the round's models plus the
  * M-step of each -- what run_trial does for one trial, file for file. */
 static int run_round(cpecan_em_trainer *t, cpecan_expect_set *set, int64_t nJobs, cpecan_hmm *hmms, int n, double *runs,
@@ -505,6 +569,7 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
                       t->concurrentTrials);
         return CPECAN_EINVAL;
     }
+    if (viterbi_training_refusal(t) != CPECAN_OK) return CPECAN_EINVAL;
     keep_alignments(t, NULL, NULL, 0);
     const double t0 = now_ms();
     memset(&t->timing, 0, sizeof t->timing);
@@ -522,8 +587,13 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
         rc = cpecan_em_sample(in, n, t->opt.maxAlignmentLengthPerJob, t->opt.maxAlignmentLengthToSample, t->opt.seed,
                               order, &nSample, &nJobs, NULL);
     cpecan_expect_set *set = NULL;
-    if (rc == CPECAN_OK) {
-        for (int64_t i = 0; i < nSample; i++) sample[i] = in[order[i]]; /* shallow copies: nothing is freed through them */
+    cpecan_viterbi *vit = NULL;
+    for (int64_t i = 0; rc == CPECAN_OK && i < nSample; i++) sample[i] = in[order[i]]; /* shallow copies: nothing is freed through them */
+    if (rc == CPECAN_OK && t->viterbiTraining) { /* planned here; its inputs go to the device with the first E-step and stay */
+        cpecan_model any;
+        rc = cpecan_model_default(&any, t->type);
+        if (rc == CPECAN_OK) rc = cpk_realigner_viterbi_create(t->r, &any, sample, nSample, &vit);
+    } else if (rc == CPECAN_OK) {
         rc = cpecan_expect_set_reserve_models(t->r, conc > 1 ? conc : 0);
         if (rc == CPECAN_OK) rc = cpecan_expect_set_create(&set, t->r, sample, nSample);
     }
@@ -554,7 +624,8 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
         if (trials == 1) strcpy(path, outputModel);
         else if (t->opt.outputTrialHmms) sprintf(path, "%s_%d", outputModel, k);
         else sprintf(path, "%s.trial_%d", outputModel, k);
-        rc = run_trial(t, set, sample, nSample, nJobs, &hmms[k], runs + (size_t)k * (size_t)iters, path, &reanchored);
+        if (t->viterbiTraining) rc = run_trial_viterbi(t, vit, &hmms[k], runs + (size_t)k * (size_t)iters, path);
+        else rc = run_trial(t, set, sample, nSample, nJobs, &hmms[k], runs + (size_t)k * (size_t)iters, path, &reanchored);
         if (trials > 1 && !t->opt.outputTrialHmms) remove(path);
         if (rc == CPECAN_OK && hmms[k].likelihood > hmms[bestTrial].likelihood) bestTrial = k;
     }
@@ -589,6 +660,7 @@ int cpecan_em_train(cpecan_em_trainer *t, const cpecan_cigar *in, int64_t n, con
         t->timing.jobs = nJobs;
     }
     cpecan_expect_set_destroy(set);
+    cpecan_viterbi_destroy(vit);
     free(order);
     free(sample);
     free(runs);

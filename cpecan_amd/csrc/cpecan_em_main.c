@@ -21,6 +21,8 @@ static void usage(void) {
             "--useDefaultModelAsStart  --setJukesCantorStartingEmissions F  --trainEmissions  --tieEmissions\n"
             "--maxAlignmentLengthPerJob N (1000000)  --maxAlignmentLengthToSample N (50000000)  --seed N (0)\n"
             "--updateTheBand (realign the sample after every iteration; not with --concurrentTrials above 1)\n"
+            "--viterbiTraining (hard EM: counts along the most probable paths; not with --updateTheBand, --concurrentTrials\n"
+            "above 1 or several devices)  --viterbiPseudoCount C (1.0, added to every count)\n"
             "--blastScoringMatrixFile FILE  --optionsToRealign \"...\" (default \"--diagonalExpansion=10\n"
             "--splitMatrixBiggerThanThis=3000\"; -r/-o/-t/-l/-L and their long names)  --device N  --devices LIST\n"
             "--logLevel L (ignored)  -h --help\n");
@@ -144,7 +146,7 @@ int main(int argc, char **argv) {
     enum {
         kModelType = 256, kInputModel, kOutputModel, kIterations, kTrials, kRandomStart, kTrialHmms, kDefaultStart,
         kJukesCantor, kTrainEmissions, kTieEmissions, kPerJob, kToSample, kSeed, kBlast, kToRealign, kSequences,
-        kAlignments, kDevice, kDevices, kLogLevel, kXml, kUpdateBand, kConcurrent
+        kAlignments, kDevice, kDevices, kLogLevel, kXml, kUpdateBand, kConcurrent, kViterbi, kViterbiPseudo
     };
     static struct option longOpts[] = {{"modelType", required_argument, 0, kModelType},
                                        {"inputModel", required_argument, 0, kInputModel},
@@ -170,9 +172,13 @@ int main(int argc, char **argv) {
                                        {"logLevel", required_argument, 0, kLogLevel},
                                        {"outputXMLModelFile", required_argument, 0, kXml},
                                        {"updateTheBand", no_argument, 0, kUpdateBand},
+                                       {"viterbiTraining", no_argument, 0, kViterbi},
+                                       {"viterbiPseudoCount", required_argument, 0, kViterbiPseudo},
                                        {"help", no_argument, 0, 'h'},
                                        {0, 0, 0, 0}};
     long long v, concurrent = 1;
+    int viterbiTraining = 0;
+    double viterbiPseudoCount = 1.0;
     for (int key; (key = getopt_long(argc, argv, "h", longOpts, NULL)) != -1;) {
         switch (key) {
         case 'h': usage(); return 0;
@@ -223,6 +229,13 @@ int main(int argc, char **argv) {
             fprintf(stderr, "cpecan_em: --updateTheBand: the sampled alignments are realigned after every iteration\n");
             o.updateTheBand = 1;
             break;
+        case kViterbi: viterbiTraining = 1; break;
+        case kViterbiPseudo:
+            if (sscanf(optarg, "%lf", &viterbiPseudoCount) != 1) {
+                fprintf(stderr, "cpecan_em: --viterbiPseudoCount %s: a number >= 0\n", optarg);
+                return 1;
+            }
+            break;
         default: usage(); return 1;
         }
     }
@@ -235,6 +248,7 @@ int main(int argc, char **argv) {
     if (cpecan_em_trainer_create(&t, &o, &ro, (int)device) != CPECAN_OK) return fail("options");
     if (nDevices > 1 && cpecan_em_trainer_set_devices(t, devices, nDevices) != CPECAN_OK) return fail("--devices");
     if (cpecan_em_trainer_set_concurrent_trials(t, (int)concurrent) != CPECAN_OK) return fail("--concurrentTrials");
+    if (viterbiTraining && cpecan_em_trainer_set_viterbi_training(t, 1, viterbiPseudoCount) != CPECAN_OK) return fail("--viterbiTraining");
     int status = 0;
     char *seqs = strdup(sequences), *save = NULL;
     for (char *path = strtok_r(seqs, " \t", &save); status == 0 && path; path = strtok_r(NULL, " \t", &save))

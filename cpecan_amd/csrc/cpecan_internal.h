@@ -296,6 +296,14 @@ struct cpecan_cigar;
  * host: *nRuns n counts, *runs the quadruples one cigar after the other, both malloc'd (cpecan_realign.c). */
 int cpk_realigner_cigar_runs(const struct cpecan_realigner *r, const struct cpecan_cigar *in, int64_t n, int64_t **runs,
                              int64_t **nRuns);
+struct cpecan_viterbi;
+/* A Viterbi object (cpecan_viterbi.h) over n cigars as cpecan_expect_set_create prepares them: the cigars' sub-sequences, their
+ * exact-match anchor runs expanded into triples, the realigner's banding parameters and device, both ends ragged; one
+ * problem per cigar, in order (cpecan_realign.c).  No device is touched. */
+int cpk_realigner_viterbi_create(const struct cpecan_realigner *r, const cpecan_model *m, const struct cpecan_cigar *in, int64_t n,
+                                 struct cpecan_viterbi **out);
+/* The devices a call of the realigner is spread over (1 unless cpecan_realigner_set_devices listed more). */
+int cpk_realigner_device_count(const struct cpecan_realigner *r);
 /* Plans an unfrozen batch as cpecan_batch_upload would and then its launches (cpk_plan.inl, plan_batch) for a device of
  * numCUs compute units and memBytes of free memory that is not there: a kernel is taken to use the registers its build
  * allows.  out receives CPK_LAUNCH_PLAN_FIELDS numbers per launch class, in launch order (cpk_plan_describe); returns
@@ -604,6 +612,27 @@ typedef struct {
     int32_t *ops;
 } CpkVitJob;
 int cpk_viterbi_launch(int device, const CpkModel *model, const CpkVitJob *job, double *sweepMs, double *tracebackMs);
+
+/* The resident form (cpecan_viterbi_run_counts): the inputs of every launch of a planned run uploaded
+ * once, one scratch (pointer bytes, rolling rows, out records, op slots, count slabs) at the largest launch's size, the run's
+ * int64 bins.  The ops never leave the device. */
+#define CPK_VIT_MAX_BINS (25 + 80) /* S * S transitions, then S * 16 emissions */
+typedef struct CpkVitResident CpkVitResident;
+/* inputBytes / scratchBytes: what the uploads and the scratch will take; CPECAN_ENOMEM, with the bytes named, where the
+ * device has not that much free. */
+int cpk_viterbi_resident_create(CpkVitResident **out, int device, int nStates, int64_t nLaunches, int64_t inputBytes, int64_t scratchBytes);
+/* Copies the job's regions, diags, symbols and order to the device as launch `launch`; its out / ops pointers are not read. */
+int cpk_viterbi_resident_upload(CpkVitResident *r, int64_t launch, const CpkVitJob *job);
+/* After the last upload: the scratch. */
+int cpk_viterbi_resident_reserve(CpkVitResident *r);
+/* Zeroes the run's bins. */
+int cpk_viterbi_resident_begin(CpkVitResident *r);
+/* Sweep, traceback, count, reduce of one launch; out: its nRegions records; slabs (or NULL): its nRegions * nBins uint32;
+ * ms[4]: HIP-event times of sweep, traceback, count, reduce. */
+int cpk_viterbi_resident_run(CpkVitResident *r, int64_t launch, const CpkModel *model, CpkVitOut *out, uint32_t *slabs, double ms[4]);
+/* bins[nBins] of the launches since cpk_viterbi_resident_begin. */
+int cpk_viterbi_resident_bins(CpkVitResident *r, int64_t *bins);
+void cpk_viterbi_resident_destroy(CpkVitResident *r);
 
 #ifdef __cplusplus
 }

@@ -1993,6 +1993,159 @@ extern "C" int cpk_viterbi_launch(int device, const CpkModel *model, const CpkVi
     return CPECAN_OK;
 }
 
+// The resident form of a cpecan_viterbi run (cpecan_viterbi_run_counts): every launch's inputs on the device, one scratch, the
+// run's bins.  Everything on the null stream; the copy of a launch's out records home waits for its kernels.
+struct CpkVitResident {
+    int device = 0, nStates = 0, nBins = 0;
+    struct Launch {
+        void *d[4] = {};  // regions, diags, symbols, order
+        size_t bytes[4] = {};
+        int64_t nRegions = 0, nLds = 0, nPtrBytes = 0, nRollDoubles = 0, nOpPairs = 0;
+        int32_t ldsMaxWidth = 0;
+    };
+    std::vector<Launch> launches;
+    void *scratch[5] = {};  // pointer bytes, rolling rows, out records, op slots, count slabs
+    size_t scratchBytes[5] = {};
+    int64_t *bins = nullptr;
+    hipEvent_t ev[5] = {};
+};
+
+extern "C" void cpk_viterbi_resident_destroy(CpkVitResident *r) {
+    if (!r) return;
+    DeviceGuard guard(r->device);
+    (void)hipDeviceSynchronize();
+    for (auto &l : r->launches)
+        for (int i = 0; i < 4; i++) cache_free(r->device, l.d[i], l.bytes[i]);
+    for (int i = 0; i < 5; i++) cache_free(r->device, r->scratch[i], r->scratchBytes[i]);
+    cache_free(r->device, r->bins, sizeof(int64_t) * CPK_VIT_MAX_BINS);
+    for (int i = 0; i < 5; i++)
+        if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
+    delete r;
+}
+
+extern "C" int cpk_viterbi_resident_create(CpkVitResident **out, int device, int nStates, int64_t nLaunches, int64_t inputBytes,
+                                           int64_t scratchBytes) {
+    const int nDev = cpk_device_count();
+    if (nDev <= 0 || device < 0 || device >= nDev) {
+        cpk_set_error("no usable HIP device (count=%d, requested=%d): the HIP path has no CPU fallback", nDev, device);
+        return CPECAN_ENODEVICE;
+    }
+    CPK_ON_DEVICE(device);
+    size_t freeBytes = 0, totalBytes = 0;
+    HIP_TRY(hipMemGetInfo(&freeBytes, &totalBytes));
+    if ((size_t)inputBytes + (size_t)scratchBytes > freeBytes + cache_bytes(device)) {
+        cpk_set_error("cpecan_viterbi_run_counts: the resident inputs need %lld bytes beside %lld bytes of scratch, the device has %lld free",
+                      (long long)inputBytes, (long long)scratchBytes, (long long)(freeBytes + cache_bytes(device)));
+        return CPECAN_ENOMEM;
+    }
+    CpkVitResident *r = new CpkVitResident;
+    r->device = device;
+    r->nStates = nStates;
+    r->nBins = nStates * nStates + nStates * 16;
+    r->launches.resize((size_t)nLaunches);
+    hipError_t e = cache_alloc(device, (void **)&r->bins, sizeof(int64_t) * CPK_VIT_MAX_BINS);
+    for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventCreate(&r->ev[i]);
+    if (e != hipSuccess) {
+        cpk_set_error("cpk_viterbi_resident_create: %s", hipGetErrorString(e));
+        cpk_viterbi_resident_destroy(r);
+        return CPECAN_EHIP;
+    }
+    *out = r;
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_viterbi_resident_upload(CpkVitResident *r, int64_t launch, const CpkVitJob *j) {
+    if (launch < 0 || launch >= (int64_t)r->launches.size() || r->launches[(size_t)launch].d[0]) return CPECAN_EINVAL;
+    CPK_ON_DEVICE(r->device);
+    CpkVitResident::Launch &l = r->launches[(size_t)launch];
+    const size_t bytes[4] = {sizeof(CpkVitRegion) * (size_t)j->nRegions, sizeof(CpkVitDiag) * (size_t)j->nDiags, (size_t)j->nSymbolBytes,
+                             sizeof(int32_t) * (size_t)j->nRegions};
+    const void *src[4] = {j->regions, j->diags, j->symbols, j->order};
+    for (int i = 0; i < 4; i++) {
+        l.bytes[i] = bytes[i] ? bytes[i] : 8;
+        HIP_TRY(cache_alloc(r->device, &l.d[i], l.bytes[i]));
+        HIP_TRY(hipMemcpy(l.d[i], src[i], bytes[i], hipMemcpyHostToDevice));
+    }
+    l.nRegions = j->nRegions;
+    l.nLds = j->nLds;
+    l.nPtrBytes = j->nPtrBytes;
+    l.nRollDoubles = j->nRollDoubles;
+    l.nOpPairs = j->nOpPairs;
+    l.ldsMaxWidth = j->ldsMaxWidth;
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_viterbi_resident_reserve(CpkVitResident *r) {
+    CPK_ON_DEVICE(r->device);
+    size_t need[5] = {8, 8, 8, 8, 8};
+    for (const auto &l : r->launches) {
+        const size_t b[5] = {(size_t)l.nPtrBytes, sizeof(double) * (size_t)l.nRollDoubles, sizeof(CpkVitOut) * (size_t)l.nRegions,
+                             sizeof(int32_t) * 2 * (size_t)l.nOpPairs, sizeof(uint32_t) * (size_t)r->nBins * (size_t)l.nRegions};
+        for (int i = 0; i < 5; i++)
+            if (b[i] > need[i]) need[i] = b[i];
+    }
+    for (int i = 0; i < 5; i++) {
+        if (r->scratch[i]) return CPECAN_ESTATE;
+        r->scratchBytes[i] = need[i];
+        HIP_TRY(cache_alloc(r->device, &r->scratch[i], need[i]));
+    }
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_viterbi_resident_begin(CpkVitResident *r) {
+    CPK_ON_DEVICE(r->device);
+    HIP_TRY(hipMemsetAsync(r->bins, 0, sizeof(int64_t) * CPK_VIT_MAX_BINS, nullptr));
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_viterbi_resident_run(CpkVitResident *r, int64_t launch, const CpkModel *model, CpkVitOut *out, uint32_t *slabs,
+                                        double ms[4]) {
+    if (launch < 0 || launch >= (int64_t)r->launches.size() || !r->scratch[0] || model->nStates != r->nStates) return CPECAN_EINVAL;
+    const CpkVitResident::Launch &l = r->launches[(size_t)launch];
+    for (int i = 0; i < 4; i++) ms[i] = 0.0;
+    if (l.nRegions <= 0) return CPECAN_OK;
+    CPK_ON_DEVICE(r->device);
+    const int S = r->nStates;
+    VitArgs a = {(const CpkVitRegion *)l.d[0], (const CpkVitDiag *)l.d[1], (const uint8_t *)l.d[2], (const int32_t *)l.d[3],
+                 (uint8_t *)r->scratch[0], (double *)r->scratch[1], (CpkVitOut *)r->scratch[2], (int32_t *)r->scratch[3], l.ldsMaxWidth};
+    uint32_t *dSlabs = (uint32_t *)r->scratch[4];
+    const size_t ldsRows = sizeof(double) * (kVitEm + (size_t)3 * S * (size_t)l.ldsMaxWidth), ldsNone = sizeof(double) * kVitEm;
+    (void)hipEventRecord(r->ev[0], nullptr);
+    if (l.nLds > 0) hipLaunchKernelGGL(cpecan_viterbi_sweep<true>, dim3((unsigned)l.nLds), dim3(CPK_WAVE), ldsRows, nullptr, *model, a);
+    if (l.nRegions > l.nLds) {
+        VitArgs g = a;
+        g.order = a.order + l.nLds;
+        hipLaunchKernelGGL(cpecan_viterbi_sweep<false>, dim3((unsigned)(l.nRegions - l.nLds)), dim3(CPK_WAVE), ldsNone, nullptr, *model, g);
+    }
+    (void)hipEventRecord(r->ev[1], nullptr);
+    hipLaunchKernelGGL(cpecan_viterbi_traceback, dim3((unsigned)l.nRegions), dim3(CPK_WAVE), 0, nullptr, S, a);
+    (void)hipEventRecord(r->ev[2], nullptr);
+    hipLaunchKernelGGL(cpecan_viterbi_count, dim3((unsigned)l.nRegions), dim3(CPK_WAVE), 0, nullptr, S, a, dSlabs);
+    (void)hipEventRecord(r->ev[3], nullptr);
+    hipLaunchKernelGGL(cpecan_viterbi_count_reduce, dim3((unsigned)r->nBins), dim3(kVitReduceThreads), 0, nullptr, (const uint32_t *)dSlabs,
+                       (int)l.nRegions, r->nBins, r->bins);
+    hipError_t e = hipGetLastError();
+    (void)hipEventRecord(r->ev[4], nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, r->scratch[2], sizeof(CpkVitOut) * (size_t)l.nRegions, hipMemcpyDeviceToHost);  // waits (null stream)
+    if (e == hipSuccess && slabs)
+        e = hipMemcpy(slabs, dSlabs, sizeof(uint32_t) * (size_t)r->nBins * (size_t)l.nRegions, hipMemcpyDeviceToHost);
+    for (int i = 0; i < 4 && e == hipSuccess; i++) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, r->ev[i], r->ev[i + 1]) == hipSuccess) ms[i] = t;
+    }
+    if (e != hipSuccess) {
+        cpk_set_error("cpk_viterbi_resident_run: %s", hipGetErrorString(e));
+        return CPECAN_EHIP;
+    }
+    return CPECAN_OK;
+}
+
+extern "C" int cpk_viterbi_resident_bins(CpkVitResident *r, int64_t *bins) {
+    CPK_ON_DEVICE(r->device);
+    HIP_TRY(hipMemcpy(bins, r->bins, sizeof(int64_t) * (size_t)r->nBins, hipMemcpyDeviceToHost));
+    return CPECAN_OK;
+}
+
 extern "C" int64_t cpk_device_bytes(const CpkDevice *d) { return d->bytes; }
 static int form_code(const KernelForm &f) {  // CPECAN_FORM_* of a class, from the form of its first launch
     return (f.mode == kModeFused ? CPECAN_FORM_FUSED : f.mode != kModeWhole ? CPECAN_FORM_SPLIT : CPECAN_FORM_WHOLE) | (f.abs ? CPECAN_FORM_ABS : 0);

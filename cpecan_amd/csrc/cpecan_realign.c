@@ -19,6 +19,7 @@
 #include <time.h>
 
 #include "cpecan_internal.h"
+#include "cpecan_viterbi.h"
 
 static double now_ms(void) {
     struct timespec t;
@@ -1526,6 +1527,44 @@ int cpk_realigner_cigar_runs(const cpecan_realigner *r, const cpecan_cigar *in, 
         *runs = *nRuns = NULL;
     }
     return rc;
+}
+
+int cpk_realigner_device_count(const cpecan_realigner *r) { return r && r->nDevices > 1 ? r->nDevices : 1; }
+
+int cpk_realigner_viterbi_create(const cpecan_realigner *r, const cpecan_model *m, const cpecan_cigar *in, int64_t n, cpecan_viterbi **out) {
+    *out = NULL;
+    cpecan_viterbi *v = NULL;
+    int rc = cpecan_viterbi_create(&v, m, &r->opt.params, r->device);
+    if (rc != CPECAN_OK) return rc;
+    Item *items = calloc((size_t)(n ? n : 1), sizeof(Item));
+    rc = items ? prepare_range(r, in, 0, n, items, 0) : CPECAN_ENOMEM;
+    for (int64_t i = 0; rc == CPECAN_OK && i < n; i++) {
+        const Item *it = &items[i];
+        int64_t nTriples = 0;
+        for (int64_t k = 0; k < it->nFiltered; k++) nTriples += it->filtered[4 * k + 2];
+        int64_t *triples = malloc(sizeof(int64_t) * 3 * (size_t)(nTriples ? nTriples : 1));
+        if (!triples) {
+            rc = CPECAN_ENOMEM;
+            break;
+        }
+        for (int64_t k = 0, at = 0; k < it->nFiltered; k++) /* a run (x, y, length, expansion): `length` diagonal neighbours */
+            for (int64_t j = 0; j < it->filtered[4 * k + 2]; j++, at++) {
+                triples[3 * at] = it->filtered[4 * k] + j;
+                triples[3 * at + 1] = it->filtered[4 * k + 1] + j;
+                triples[3 * at + 2] = it->filtered[4 * k + 3];
+            }
+        const int64_t idx = cpecan_viterbi_add(v, it->subX, it->lX, it->subY, it->lY, triples, nTriples, 1, 1); /* both ends ragged */
+        free(triples);
+        if (idx < 0) rc = (int)idx;
+    }
+    for (int64_t i = 0; items && i < n; i++) item_clear(&items[i]);
+    free(items);
+    if (rc != CPECAN_OK) {
+        cpecan_viterbi_destroy(v);
+        return rc;
+    }
+    *out = v;
+    return CPECAN_OK;
 }
 
 int cpecan_expect_set_run(cpecan_expect_set *s, const cpecan_model *m, cpecan_hmm *acc) {

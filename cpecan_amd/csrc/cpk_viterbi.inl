@@ -269,3 +269,125 @@ __global__ void __launch_bounds__(CPK_WAVE) cpecan_viterbi_traceback(const int n
     if (nStates == 5) vit_traceback_region<5>(a, stage, walk);
     else vit_traceback_region<3>(a, stage, walk);
 }
+
+// ---- Counts of the decoded paths: Viterbi training's E-step (include/cpecan_viterbi.h) ----
+//
+//   cpecan_viterbi_count         one wave per region, after the traceback, over the ops it left on the device (run-length
+//                                encoded, last run first).  A pass lays out 64 runs, one per lane: three wave scans give every
+//                                run its end cell -- (lX, lY) minus the steps of the runs stored before it -- and its first
+//                                step among the pass's steps; the source state of a run's first step is the state of the run
+//                                stored after it, startState for the last stored run.  Transitions are arithmetic on the runs:
+//                                1 to trans[prev][s] (a ballot and a population count per pair of states), L - 1 to
+//                                trans[s][s] (a wave sum per state).  The steps of the pass are then spread over the lanes, 64
+//                                at a time whichever run they belong to (a binary search in the scanned lengths, in LDS), each
+//                                lane reads its cell's two symbols, and every emission bin present is counted with a ballot
+//                                and a population count.  Lane l keeps bins l and l + 64 in two registers: no atomics, no
+//                                LDS read-modify-write; the region's S * S + S * 16 bins leave as one slab of plain stores.
+//   cpecan_viterbi_count_reduce  one workgroup per bin: thread t sums the slabs of regions t, t + 256, ... in ascending order,
+//                                the 256 partial sums are folded pairwise in a fixed order, and thread 0 adds the total to
+//                                the run's int64 bin.  Integers: any order gives these bytes; this one is fixed.
+
+__device__ __forceinline__ int vit_scan_inclusive(int v, int lane) {
+#pragma unroll
+    for (int off = 1; off < CPK_WAVE; off <<= 1) {
+        const int t = __shfl_up(v, off);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
+__device__ __forceinline__ int vit_wave_sum(int v) {
+#pragma unroll
+    for (int off = CPK_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+template <int S>
+__device__ __forceinline__ void vit_count_region(const VitArgs &a, uint32_t *slabs, int *sIncl, int *sState, int *sEndX, int *sEndY) {
+    constexpr int kBins = S * S + S * 16;
+    static_assert(kBins <= 2 * CPK_WAVE, "a lane keeps two bins");
+    const int ri = blockIdx.x, lane = threadIdx.x;
+    const CpkVitRegion rg = a.regions[ri];
+    const CpkVitOut o = a.out[ri];
+    const int nOps = o.endState < 0 ? 0 : o.nOps;  // no path: no counts
+    const uint8_t *sx = a.symbols + rg.symX, *sy = a.symbols + rg.symY;
+    const int32_t *ops = a.ops + 2 * rg.opBase;
+    uint32_t acc0 = 0, acc1 = 0;  // bins lane and lane + 64
+    auto add = [&](int bin, int n) {
+        if (lane == (bin & (CPK_WAVE - 1))) {
+            if (bin < CPK_WAVE) acc0 += (uint32_t)n;
+            else acc1 += (uint32_t)n;
+        }
+    };
+    int endX = rg.lX, endY = rg.lY;  // the end cell of the pass's first run
+    for (int base = 0; base < nOps; base += CPK_WAVE) {
+        const int k = base + lane;
+        const bool valid = k < nOps;
+        const int st = valid ? ops[2 * k] : 0, len = valid ? ops[2 * k + 1] : 0;
+        const int prev = !valid ? 0 : k + 1 < nOps ? ops[2 * (k + 1)] : o.startState;
+        const int dx = st == 0 || st == 1 || st == 3 ? len : 0, dy = st == 0 || st == 2 || st == 4 ? len : 0;
+        const int incl = vit_scan_inclusive(len, lane), inclX = vit_scan_inclusive(dx, lane), inclY = vit_scan_inclusive(dy, lane);
+#pragma unroll
+        for (int p = 0; p < S; p++)
+#pragma unroll
+            for (int s = 0; s < S; s++) add(p * S + s, __popcll(__ballot(valid && prev == p && st == s)));
+#pragma unroll
+        for (int s = 0; s < S; s++) add(s * S + s, vit_wave_sum(valid && st == s ? len - 1 : 0));
+        __syncthreads();  // the pass before has read its runs
+        sIncl[lane] = incl;
+        sState[lane] = st;
+        sEndX[lane] = endX - (inclX - dx);
+        sEndY[lane] = endY - (inclY - dy);
+        __syncthreads();
+        const int T = sIncl[CPK_WAVE - 1];
+        for (int t0 = 0; t0 < T; t0 += CPK_WAVE) {
+            const bool active = t0 + lane < T;
+            const int t = active ? t0 + lane : 0;
+            int i = 0;  // the runs that end at or before step t: the index of the run that holds it
+#pragma unroll
+            for (int half = CPK_WAVE / 2; half > 0; half >>= 1)
+                if (sIncl[i + half - 1] <= t) i += half;
+            const int s = sState[i], back = sIncl[i] - 1 - t;  // steps between this one and the run's end cell
+            int x = sEndX[i] - (s == 0 || s == 1 || s == 3 ? back : 0), y = sEndY[i] - (s == 0 || s == 2 || s == 4 ? back : 0);
+            x = x < 0 ? 0 : x > rg.lX ? rg.lX : x;  // ops that are the traceback's never leave the region
+            y = y < 0 ? 0 : y > rg.lY ? rg.lY : y;
+            const int cX = sx[x], cY = sy[y];  // padded: row and column 0 see N
+            const bool emits = active && cX < 4 && cY < 4;
+            const int code = emits ? s * 16 + cX * 4 + cY : -1;
+#pragma unroll
+            for (int q = 0; q < S; q++) {
+                if (!__ballot(emits && s == q)) continue;
+#pragma unroll
+                for (int b = 0; b < 16; b++) add(S * S + q * 16 + b, __popcll(__ballot(code == q * 16 + b)));
+            }
+        }
+        endX -= __shfl(inclX, CPK_WAVE - 1);
+        endY -= __shfl(inclY, CPK_WAVE - 1);
+    }
+    uint32_t *slab = slabs + (int64_t)ri * kBins;
+    if (lane < kBins) slab[lane] = acc0;
+    if (lane + CPK_WAVE < kBins) slab[lane + CPK_WAVE] = acc1;
+}
+
+__global__ void __launch_bounds__(CPK_WAVE) cpecan_viterbi_count(const int nStates, const VitArgs a, uint32_t *slabs) {
+    __shared__ int sIncl[CPK_WAVE], sState[CPK_WAVE], sEndX[CPK_WAVE], sEndY[CPK_WAVE];
+    if (nStates == 5) vit_count_region<5>(a, slabs, sIncl, sState, sEndX, sEndY);
+    else vit_count_region<3>(a, slabs, sIncl, sState, sEndX, sEndY);
+}
+
+constexpr int kVitReduceThreads = 256;
+
+__global__ void __launch_bounds__(kVitReduceThreads) cpecan_viterbi_count_reduce(const uint32_t *slabs, const int nRegions, const int nBins,
+                                                                                 int64_t *bins) {
+    __shared__ int64_t part[kVitReduceThreads];
+    const int bin = blockIdx.x, t = threadIdx.x;
+    int64_t sum = 0;
+    for (int r = t; r < nRegions; r += kVitReduceThreads) sum += slabs[(int64_t)r * nBins + bin];
+    part[t] = sum;
+    __syncthreads();
+    for (int half = kVitReduceThreads / 2; half > 0; half >>= 1) {
+        if (t < half) part[t] += part[t + half];
+        __syncthreads();
+    }
+    if (t == 0) bins[bin] += part[0];  // the launches of a run follow one another on the stream
+}

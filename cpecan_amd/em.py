@@ -15,7 +15,7 @@ EXPORTS = [
     "cpecan_em_write_lastz_matrix", "cpecan_em_fasta_gc", "cpecan_em_write_model", "cpecan_em_trainer_create",
     "cpecan_em_trainer_destroy", "cpecan_em_trainer_read_fasta", "cpecan_em_trainer_add_sequence",
     "cpecan_em_trainer_set_devices", "cpecan_em_train", "cpecan_em_trainer_timing",
-    "cpecan_em_trainer_set_concurrent_trials", "cpecan_em_trainer_alignments",
+    "cpecan_em_trainer_set_concurrent_trials", "cpecan_em_trainer_alignments", "cpecan_em_trainer_set_viterbi_training",
 ]
 
 MODEL_TYPES = {"fiveState": api.fiveState, "fiveStateAsymmetric": api.fiveStateAsymmetric,
@@ -71,6 +71,7 @@ def _lib():
         L.cpecan_em_trainer_add_sequence.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int64]
         L.cpecan_em_trainer_set_devices.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
         L.cpecan_em_trainer_set_concurrent_trials.argtypes = [vp, C.c_int]
+        L.cpecan_em_trainer_set_viterbi_training.argtypes = [vp, C.c_int, C.c_double]
         L.cpecan_em_train.argtypes = [vp, C.POINTER(realign._Cigar), C.c_int64, C.c_char_p, hp, dp]
         L.cpecan_em_trainer_timing.argtypes = [vp, C.POINTER(EmTiming)]
         L.cpecan_em_trainer_alignments.argtypes = [vp, C.POINTER(i64p), C.POINTER(i64p), i64p]
@@ -210,6 +211,12 @@ class Trainer:
     def set_concurrent_trials(self, n):
         """Random-restart trials per kernel launch (1 to 8; 1: one after another); more trials run in rounds."""
         api._check(_lib().cpecan_em_trainer_set_concurrent_trials(self._h, int(n)), "cpecan_em_trainer_set_concurrent_trials")
+
+    def set_viterbi_training(self, on=True, pseudo_count=1.0):
+        """Viterbi training (hard EM): the E-step counts along the most probable path of every sampled alignment, on top of
+        pseudo_count in every bin.  Not with updateTheBand, several concurrent trials or several devices."""
+        api._check(_lib().cpecan_em_trainer_set_viterbi_training(self._h, int(bool(on)), float(pseudo_count)),
+                   "cpecan_em_trainer_set_viterbi_training")
 
     def train(self, cigars, output_model):
         """Runs every trial; returns (best Hmm, its running likelihoods)."""

@@ -11,6 +11,17 @@ a pair-HMM and its log-probability -- on the GPU.
         v.add_many(problems)   # (sx, sy, anchors[, ragged_left, ragged_right])
         v.run()
         results = [v.result(i) for i in range(v.n)]
+
+Viterbi training's E-step: the transitions and emissions along the decoded paths, counted on the GPU
+over inputs that stay there from the first call on; only the model goes down and the bins come up.
+
+    with Viterbi(sM, p) as v:
+        v.add_many(problems)
+        c = v.run_counts()     # Counts: transitions int64[S, S], emissions int64[S, 16], nSteps, nNoPath, logP
+        v.set_model(other)     # same state count; the resident inputs stay
+        c = v.run_counts()
+    counts_of_ops(S, sx, sy, start_state, ops)   # the same count over one region's ops, on the host
+    counts_add_to_hmm(c, hmm)                    # into an api.Hmm accumulator, exactly
 """
 import collections
 import ctypes as C
@@ -24,6 +35,9 @@ EXPORTS = [
     "cpecan_viterbi_create", "cpecan_viterbi_destroy", "cpecan_viterbi_add", "cpecan_viterbi_set_budget",
     "cpecan_viterbi_set_form", "cpecan_viterbi_run", "cpecan_viterbi_launch_forms", "cpecan_viterbi_info",
     "cpecan_viterbi_result", "cpecan_viterbi_kernel_ms", "cpecan_viterbi_replay", "cpecan_viterbi_pairs",
+    "cpecan_viterbi_set_model", "cpecan_viterbi_run_counts", "cpecan_viterbi_resident_bytes",
+    "cpecan_viterbi_set_keep_problem_counts", "cpecan_viterbi_problem_counts", "cpecan_viterbi_count_ms",
+    "cpecan_viterbi_counts_of_ops", "cpecan_viterbi_counts_add_to_hmm",
 ]
 
 MAX_BYTES = 4 << 30  # CPECAN_VITERBI_MAX_BYTES
@@ -51,6 +65,14 @@ class ViterbiResult(C.Structure):
                 ("ops", C.POINTER(C.c_int32))]
 
 
+class ViterbiCounts(C.Structure):
+    """cpecan_viterbi_counts."""
+    _fields_ = [("transitions", C.c_int64 * 25), ("emissions", C.c_int64 * 80), ("nSteps", C.c_int64), ("nNoPath", C.c_int64),
+                ("nStates", C.c_int64), ("logP", C.c_double)]
+
+
+# transitions int64[S, S] (from, to); emissions int64[S, 16] (state, cX * 4 + cY)
+Counts = collections.namedtuple("Counts", "transitions emissions nSteps nNoPath logP")
 Region = collections.namedtuple("Region", "x1 y1 x2 y2 logP startState endState opOff nOps")
 Result = collections.namedtuple("Result", "logP regions ops")
 LaunchForms = collections.namedtuple("LaunchForms", "launches lds global_")
@@ -80,8 +102,24 @@ def _lib():
                                             C.c_int, C.c_int, i32p, C.c_int64, dp]
         L.cpecan_viterbi_pairs.argtypes = [C.POINTER(ViterbiResult), i64p, C.c_int64]
         L.cpecan_viterbi_pairs.restype = C.c_int64
+        # a library built before the counts (CPECAN_LIB, the A/B runs of tools/) has the decoding half only: its plain run works
+        if hasattr(L, "cpecan_viterbi_run_counts"):
+            _bind_counts(L)
         _bound = True
     return L
+
+
+def _bind_counts(L):
+    vp, i64p, i32p, dp = C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    cp = C.POINTER(ViterbiCounts)
+    L.cpecan_viterbi_set_model.argtypes = [vp, C.POINTER(api.StateMachine)]
+    L.cpecan_viterbi_run_counts.argtypes = [vp, cp]
+    L.cpecan_viterbi_resident_bytes.argtypes = [vp, i64p, i64p]
+    L.cpecan_viterbi_set_keep_problem_counts.argtypes = [vp, C.c_int]
+    L.cpecan_viterbi_problem_counts.argtypes = [vp, C.c_int64, cp]
+    L.cpecan_viterbi_count_ms.argtypes = [vp, dp, dp]
+    L.cpecan_viterbi_counts_of_ops.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int, i32p, C.c_int64, cp]
+    L.cpecan_viterbi_counts_add_to_hmm.argtypes = [cp, C.POINTER(api.Hmm)]
 
 
 class Viterbi:
@@ -133,6 +171,38 @@ class Viterbi:
     def run(self):
         api._check(_lib().cpecan_viterbi_run(self._h), "cpecan_viterbi_run")
 
+    def set_model(self, sM):
+        """Another model of the same state count for the next run; what run_counts keeps on the device stays."""
+        api._check(_lib().cpecan_viterbi_set_model(self._h, C.byref(sM)), "cpecan_viterbi_set_model")
+        self._sM = sM
+
+    def set_keep_problem_counts(self, on=True):
+        api._check(_lib().cpecan_viterbi_set_keep_problem_counts(self._h, int(bool(on))), "cpecan_viterbi_set_keep_problem_counts")
+
+    def run_counts(self):
+        """Decodes every region and counts along the paths on the device (Counts of all problems); the inputs stay there."""
+        c = ViterbiCounts()
+        api._check(_lib().cpecan_viterbi_run_counts(self._h, C.byref(c)), "cpecan_viterbi_run_counts")
+        return _counts(c)
+
+    def problem_counts(self, problem):
+        """Counts of one problem of the last run_counts (set_keep_problem_counts must be on)."""
+        c = ViterbiCounts()
+        api._check(_lib().cpecan_viterbi_problem_counts(self._h, int(problem), C.byref(c)), "cpecan_viterbi_problem_counts")
+        return _counts(c)
+
+    def resident_bytes(self):
+        """(bytes of the inputs run_counts keeps on the device, bytes of the one scratch beside them)."""
+        a, b = C.c_int64(), C.c_int64()
+        api._check(_lib().cpecan_viterbi_resident_bytes(self._h, C.byref(a), C.byref(b)), "cpecan_viterbi_resident_bytes")
+        return a.value, b.value
+
+    def count_ms(self):
+        """(count, reduce) HIP-event milliseconds of the last run_counts."""
+        a, b = C.c_double(), C.c_double()
+        api._check(_lib().cpecan_viterbi_count_ms(self._h, C.byref(a), C.byref(b)), "cpecan_viterbi_count_ms")
+        return a.value, b.value
+
     def launch_forms(self):
         """Of the last run: LaunchForms(launches, regions run in the LDS form, regions run in the global form)."""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
@@ -172,6 +242,42 @@ def _copy(r):
     regions = tuple(Region(*(getattr(r.regions[i], k) for k in Region._fields)) for i in range(r.nRegions))
     ops = np.ctypeslib.as_array(r.ops, shape=(2 * r.nOps,)).copy().reshape(-1, 2) if r.nOps else np.zeros((0, 2), np.int32)
     return Result(float(r.logP), regions, ops.astype(np.int32, copy=False))
+
+
+def _counts(c):
+    S = int(c.nStates)
+    return Counts(np.array(c.transitions[:S * S], dtype=np.int64).reshape(S, S), np.array(c.emissions[:S * 16], dtype=np.int64).reshape(S, 16),
+                  int(c.nSteps), int(c.nNoPath), float(c.logP))
+
+
+def _raw_counts(counts):
+    S = counts.transitions.shape[0]
+    c = ViterbiCounts()
+    c.transitions[:S * S] = [int(t) for t in np.asarray(counts.transitions).reshape(-1)]
+    c.emissions[:S * 16] = [int(t) for t in np.asarray(counts.emissions).reshape(-1)]
+    c.nSteps, c.nNoPath, c.nStates, c.logP = int(counts.nSteps), int(counts.nNoPath), S, float(counts.logP)
+    return c
+
+
+def counts_of_ops(n_states, sx, sy, start_state, ops):
+    """cpecan_viterbi_counts_of_ops over ONE region (sx, sy: the region's own stretch; ops first step first): Counts with
+    logP 0.  Pure host code."""
+    x, y = api._bytes(sx), api._bytes(sy)
+    o = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1)
+    n = o.size // 2
+    if n == 0:
+        o = np.zeros(2, dtype=np.int32)
+    c = ViterbiCounts()
+    api._check(_lib().cpecan_viterbi_counts_of_ops(int(n_states), x, len(x), y, len(y), int(start_state),
+                                                   o.ctypes.data_as(C.POINTER(C.c_int32)), n, C.byref(c)), "cpecan_viterbi_counts_of_ops")
+    return _counts(c)
+
+
+def counts_add_to_hmm(counts, hmm):
+    """cpecan_viterbi_counts_add_to_hmm: the Counts added to the api.Hmm in place."""
+    c = _raw_counts(counts)
+    api._check(_lib().cpecan_viterbi_counts_add_to_hmm(C.byref(c), C.byref(hmm)), "cpecan_viterbi_counts_add_to_hmm")
+    return hmm
 
 
 def viterbi_path(sM, sx, sy, anchors=(), p=None, raggedLeft=False, raggedRight=False, device=0):

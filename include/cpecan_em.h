@@ -122,6 +122,18 @@ int cpecan_em_trainer_timing(const cpecan_em_trainer *t, cpecan_em_timing *out);
  * valid until the next cpecan_em_train or cpecan_em_trainer_destroy; CPECAN_ESTATE when the last training ran without
  * the option, failed, or never happened. */
 int cpecan_em_trainer_alignments(const cpecan_em_trainer *t, const int64_t **runs, const int64_t **nRuns, int64_t *n);
+/* Viterbi training (hard EM).  on != 0: a trial is the same loop, except that its E-step is
+ *     cpecan_hmm_init(&acc, type, pseudoCount)
+ *     one cpecan_viterbi_run_counts (cpecan_viterbi.h) over a Viterbi object that cpecan_em_train creates once from the sampled
+ *         cigars as cpecan_expect_set_create prepares them -- the sub-sequences, the exact-match anchors, the realigner's
+ *         banding parameters, both ends ragged -- and that stays on the device for the whole training
+ *     cpecan_viterbi_counts_add_to_hmm
+ * The M-step, the model files and the choice of the best trial are untouched; the running likelihood of an iteration is the
+ * sum of the most probable paths' log-probabilities.  pseudoCount is added to every transition and emission bin (1.0: add-one
+ * smoothing, so that a transition no path took keeps a probability); not finite or < 0 is CPECAN_EINVAL.  With updateTheBand,
+ * with more than one concurrent trial and with more than one device it is CPECAN_EINVAL with a message, here and in
+ * cpecan_em_train, before any device is looked for: none of the three is built.  Off by default; on = 0 restores Baum-Welch. */
+int cpecan_em_trainer_set_viterbi_training(cpecan_em_trainer *t, int on, double pseudoCount);
 
 #ifdef __cplusplus
 }

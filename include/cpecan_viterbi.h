@@ -104,6 +104,63 @@ int cpecan_viterbi_replay(const cpecan_model *model, const char *sX, int64_t lX,
  * there are, or < 0. */
 int64_t cpecan_viterbi_pairs(const cpecan_viterbi_result_t *res, int64_t *xy, int64_t cap);
 
+/*
+ * ---- Viterbi training's E-step: the counts of the decoded paths ----
+ *
+ * A region with a path (endState >= 0) has the start state q_0 and the steps t = 1 .. T; step t is in state q_t and ends at the
+ * cell (x_t, y_t) of the region, which sees cX = symbol(sX[x_t - 1]) if x_t > 0, else N, and cY likewise
+ * (impl/pairwiseAligner.c:597-607).  Its counts are updateExpectations (:418-432) with p = 1 for the transition taken:
+ *     transitions[q_{t-1} * S + q_t] += 1              every step
+ *     emissions[q_t * 16 + cX * 4 + cY] += 1           only where cX < 4 and cY < 4 -- the cell's symbols, not the state's: a
+ *                                                      step on row or column 0, or on an N, counts its transition alone
+ *     nSteps += T
+ * The start and end priors count nothing.  A region without a path counts nothing, adds nothing to logP and one to nNoPath.
+ * A problem's counts are the sums over its regions, the object's over its problems; logP is 0.0 plus the logP of the
+ * contributing regions, one after the other in region order, whatever the cut into launches.
+ */
+typedef struct cpecan_viterbi_counts {
+    int64_t transitions[25]; /* [from * nStates + to] */
+    int64_t emissions[80];   /* [state * 16 + cX * 4 + cY] */
+    int64_t nSteps, nNoPath;
+    int64_t nStates;
+    double logP;
+} cpecan_viterbi_counts;
+
+/* Another model of the same state count (CPECAN_EINVAL otherwise) for the next run.  Results of an earlier run are dropped;
+ * what cpecan_viterbi_run_counts keeps on the device stays. */
+int cpecan_viterbi_set_model(cpecan_viterbi *v, const cpecan_model *model);
+
+/* Decodes every region and counts along the paths, on the device.  The first call plans the launches under the budget as
+ * cpecan_viterbi_run does and uploads every launch's region records, band records, symbols and order; they stay there, beside
+ * one scratch of the largest launch's size, until the next cpecan_viterbi_add, cpecan_viterbi_destroy, or a
+ * cpecan_viterbi_set_budget / cpecan_viterbi_set_form that changes the value.  Later calls move the model down and the
+ * per-region records and the bins up; the ops never leave the device, so cpecan_viterbi_result stays CPECAN_ESTATE
+ * (cpecan_viterbi_launch_forms and cpecan_viterbi_kernel_ms answer for this run).  CPECAN_ENODEVICE without the device, after
+ * the refusals cpecan_viterbi_run makes without one; CPECAN_ENOMEM, with the bytes named, where the resident inputs and the
+ * scratch do not fit the device -- nothing is planned again.  The counts do not depend on the budget or the form. */
+int cpecan_viterbi_run_counts(cpecan_viterbi *v, cpecan_viterbi_counts *total);
+
+/* What cpecan_viterbi_run_counts keeps on the device under the present budget and form: the inputs of all launches, and the one
+ * scratch beside them.  Host arithmetic; the refusals of cpecan_viterbi_run that need no device. */
+int cpecan_viterbi_resident_bytes(const cpecan_viterbi *v, int64_t *inputBytes, int64_t *scratchBytes);
+
+/* on != 0: cpecan_viterbi_run_counts also brings every region's bins home and sums them per problem.  Off by default. */
+int cpecan_viterbi_set_keep_problem_counts(cpecan_viterbi *v, int on);
+/* Of the last cpecan_viterbi_run_counts; CPECAN_ESTATE with the switch off or before that run. */
+int cpecan_viterbi_problem_counts(const cpecan_viterbi *v, int64_t problem, cpecan_viterbi_counts *out);
+
+/* HIP-event times of the last cpecan_viterbi_run_counts' count and reduce kernels, summed over its launches, milliseconds. */
+int cpecan_viterbi_count_ms(const cpecan_viterbi *v, double *countMs, double *reduceMs);
+
+/* Pure host code, no device: the definition above over ONE region's ops (first step first, as cpecan_viterbi_result gives
+ * them); out->logP = 0.  CPECAN_EINVAL for ops that do not end at (lX, lY). */
+int cpecan_viterbi_counts_of_ops(int nStates, const char *sX, int64_t lX, const char *sY, int64_t lY, int startState, const int32_t *ops,
+                                 int64_t nOps, cpecan_viterbi_counts *out);
+
+/* acc->transitions[i] += (double)transitions[i], acc->emissions[i] += (double)emissions[i], acc->likelihood += logP: exact below
+ * 2^53.  CPECAN_EINVAL when the state numbers differ. */
+int cpecan_viterbi_counts_add_to_hmm(const cpecan_viterbi_counts *counts, cpecan_hmm *acc);
+
 #ifdef __cplusplus
 }
 #endif
